@@ -7,19 +7,31 @@ scene, inputs resident in HBM before the timed region.  Prints ONE JSON line on 
 
 `value` is the PRODUCT loop, psgsdf_optimize -- what voxelPS calls: the host takes the stop decision after every iteration
 (VERDICT r02 item 5).  The K timed steps are iterations W+1 .. W+K of one psgsdf_optimize call, bracketed through its per-iteration
-callback (device drained + barrier on both sides).  The same scene through psgsdf_iterate (no stop decision, nothing to wait for)
-is reported next to it (`iterate_ms_per_step`).  The LED (configs[3]) and SH2 workloads ride along as `extra`.
+callback (device drained + barrier on both sides).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--grid 256] [--frames 50] [--model SH1]
+A plain run does what `value` needs and nothing else: it synthesises the scene, warms up, times the K steps (one repetition unless --reps
+says otherwise), writes the outputs if asked to and prints the line.  `--full` adds everything else the benchmark measures: the same scene
+through psgsdf_iterate (no stop decision, nothing to wait for: `iterate_ms_per_step`), five repetitions by default, the kernel breakdown,
+the roofline of the dominant kernel (with live rocprofv3 counter passes), the CPU baseline, and the LED (configs[3]) / SH2 workloads and the
+others as `extra`; on N > 1 ranks the full-size check and the weak-scaling and configs[4] runs.  What a plain run spends outside its steps grows
+with K: the loop ends itself after ~18 iterations, so every ~15 timed steps take a fresh context (~20 ms at 256^3 x 50 keyframes: allocation, upload, set-up).
+
+`--dump-outputs DIR` writes what the timed loop hands its caller after the last timed step, as DIR/<name>.npy: `dist`, `grad` (3 x S) and
+`albedo` (3 x S) at the band voxels (float32), `band_index` (their linear voxel indices, float64), `poses` (F x 16) and `light` (float32), and
+`records` (float64, one row per timed step: the REC_FIELDS below, then e_after[0..3]).  The inputs are seeded: the same arguments give the same
+inputs in every run.  More than 64 MB in all: a fixed, seeded sample of the band voxels.  On N > 1 ranks every rank writes its own slab's
+arrays as <name>_rank<r>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--grid 256] [--frames 50] [--model SH1] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself, one process per device; with fewer than N devices visible it exits
 non-zero (PSGSDF_BENCH_SHARE_GPU=1: all ranks on GPU 0 over the gloo test transport -- a functional check, not a measurement).  The line never
-reports an n_gpus other than --gpus.  `value` is the MEDIAN over R repetitions of the K-step bracket (fresh contexts each), `spread` their min / max.
+reports an n_gpus other than --gpus.  `value` is the MEDIAN over R repetitions of the K-step bracket (fresh contexts each; R = --reps, default 1, 5 with --full), `spread` their min / max.
 
 N > 1: `value` = STRONG scaling of the metric's own problem -- the ONE 256^3 volume with its 50 keyframes cut into N z-slabs of equal
-band count, one process per GPU, every rank synthesising and uploading only its own planes -- it/s of that one job (`scaling: "strong"`).  The
-same line carries, as `extra`, the weak-scaling run (`extra.weak`: N copies of the scene stacked along z, 50*N keyframes, N x it/s -- round 4's
+band count, one process per GPU, every rank synthesising and uploading only its own planes -- it/s of that one job (`scaling: "strong"`).  With
+--full the line carries, as `extra`, the weak-scaling run (`extra.weak`: N copies of the scene stacked along z, 50*N keyframes, N x it/s -- round 4's
 default, `--weak` makes it `value` again) and BASELINE configs[4] (`extra.configs4_strong`: 512^3, SH2, 100 keyframes cut into N slabs; `--strong`
 alone makes it `value`), each with its own pre-timing self-check and `degraded` flag.  The engine's C++ host runs the slab loop natively; Python only
 launches the ranks, hands the RCCL id around and takes the time.
@@ -65,7 +77,7 @@ def live_traffic(args):
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
-            cmd = [exe, "--pmc", counter, "-d", d, "-o", "pmc", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__), "--steps", "4", "--warmup", "1", "--reps", "1",
+            cmd = [exe, "--pmc", counter, "-d", d, "-o", "pmc", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__), "--steps", "4", "--warmup", "1", "--reps", "1", "--full",
                    "--no-cpu-baseline", "--no-breakdown", "--no-extra", "--grid", str(args.grid), "--frames", str(args.frames), "--width", str(args.width), "--height", str(args.height), "--model", args.model]
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=float(os.environ.get("PSGSDF_BENCH_PMC_TIMEOUT_S", "240")))
             path = next((os.path.join(dp, f) for dp, _, fs in os.walk(d) for f in fs if f.endswith("counter_collection.csv")), None)
@@ -110,15 +122,16 @@ def algorithmic_bytes(kernel, S, n_obs, W, H, F, laplacian=False, pcg_passes=1.0
     return table.get(kernel)
 
 
-def timed_optimize(make_engine, torch, dist, steps, warmup, reps=1, before_timed=None, after_call=None):
+def timed_optimize(make_engine, torch, dist, steps, warmup, reps=1, before_timed=None, after_call=None, on_last=None):
     """`reps` repetitions of: K = `steps` iterations of the product loop psgsdf_optimize, bracketed by device synchronisation (+ barrier over the
     ranks) on both sides.  The loop leaves on its own when the energy stops falling (the reference's divergence exit, PsOptimizer.cpp:377-384; ~18
     iterations on the headline scene), so: one UNTIMED call first (the warm-up: >= `warmup` iterations, and it tells how many iterations a call
     survives), then as many timed calls as needed, each on a FRESH context (psgsdf_optimize normalises the regulariser weights in place), each
     skipping its first iteration and ending ITSELF after its share of the K steps, before the divergence exit would.  The brackets are taken in a
     passive record observer (psgsdf_set_record_observer), so the loop being timed is the callback-free one with its speculative start of the next
-    iteration.  Returns (list of elapsed seconds per repetition -- None if the loop does not survive 3 iterations --, records of the timed
-    iterations of the first repetition, calls)."""
+    iteration.  on_last(engine, records of the repetition's timed iterations) sees the context of the last timed call before it is closed.
+    Returns (list of elapsed seconds per repetition -- None if the loop does not survive 3 iterations --, records of the timed iterations
+    of the first repetition, calls)."""
     import time as _t
 
     def sync():
@@ -160,6 +173,8 @@ def timed_optimize(make_engine, torch, dist, steps, warmup, reps=1, before_timed
             sync()
             if after_call:
                 after_call(eng, calls - 1)
+            if on_last and seg["t1"] is not None and rep == reps - 1 and len(timed) + len(seg["recs"]) >= steps:
+                on_last(eng, timed + seg["recs"])
             eng.close()
             calls += 1
             if seg["t1"] is None:                   # the loop ended earlier than the untimed call did (cannot happen: same scene, same bits)
@@ -212,9 +227,43 @@ def self_check(dist, rank, world, device, share, model="SH1", F=8):
 
 STATE_STATS = ("cross_rank_ready", "cross_rank_mem_kind")      # states, not counters: never summed over contexts
 
+# --dump-outputs: the columns of records.npy (then e_after[0..3]) and the size cap of all arrays together
+REC_FIELDS = ("e_total", "e_r", "e_n", "e_l", "e_n_in", "e_l_in", "rel_diff", "reg_weight_n", "reg_weight_l", "cg_iters", "converged", "diverged", "upsampled")
+DUMP_CAP_BYTES = 64 << 20
 
-def measure(args, model, torch, dist, rank, world, device, slab, share, headline):
-    """one workload: scene, contexts, the timed loop; returns the fields of the JSON line for it"""
+
+def collect_outputs(eng, recs, slab, cap_bytes):
+    """what a caller of the timed loop receives after its last step: the band's distances, gradients and albedo, the poses, the light and the
+    records of the timed iterations.  A slab rank returns its own band voxels.  Beyond cap_bytes: a fixed, seeded sample of the band voxels."""
+    n = None
+    if slab:
+        mi = eng.mg_info()
+        n = int(mi["row1"] - mi["row0"])
+    band = eng.download_band(n)
+    vol = eng.download_volume()
+    small = {"poses": eng.download_poses(), "light": eng.download_light(),
+             "records": np.array([[float(r[k]) for k in REC_FIELDS] + [float(x) for x in r["e_after"]] for r in recs], np.float64)}
+    per_voxel = 4 * (1 + 3 + 3) + 8                                   # dist, grad, albedo (float32) + band_index (float64)
+    room = max(cap_bytes - sum(a.nbytes for a in small.values()), 0) // per_voxel
+    rows = np.arange(len(band))
+    if len(band) > room:
+        rows = np.sort(np.random.default_rng(0).choice(len(band), size=room, replace=False))
+    vox = band[rows]
+    return dict(small, band_index=vox.astype(np.float64), dist=vol["dist"][vox], grad=np.ascontiguousarray(vol["grad"][:, vox]),
+                albedo=np.ascontiguousarray(vol["rgb"][:, vox]))
+
+
+def write_outputs(folder, outputs, rank, world):
+    for name, a in outputs.items():
+        np.save(os.path.join(folder, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
+
+
+def measure(args, model, torch, dist, rank, world, device, slab, share, headline, collect=None):
+    """one workload: scene, contexts, the timed loop; returns the fields of the JSON line for it.  A plain run times the loop `value` is about and
+    nothing else; the psgsdf_iterate context (kernel breakdown, iterate_ms_per_step, the solve model) runs with --full, when it IS the timed loop
+    (--loop iterate), or when psgsdf_optimize does not survive 3 iterations.  collect(engine, records): what the timed loop hands its caller,
+    taken from the context of its last timed step (res["outputs"])."""
+    full = args.full
     reps = max(1, args.reps)
     planes_of = None
     t_gen = time.time()
@@ -256,89 +305,126 @@ def measure(args, model, torch, dist, rank, world, device, slab, share, headline
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- context 1: psgsdf_iterate (no stop decision): kernel breakdown, the dominant kernel, the round-2 figure
-    eng = context(st)
-    eng.init_albedo()
-    eng.normalize_weights()
-    S = eng.info().n_band // world              # per-slab band size (weak: every slab holds one copy of the scene; strong: the mean)
-    n_obs = eng.step(capi.ALBEDO)["n_obs"] // world
-    own_rows = None
-    if slab:
+    def band_rows(eng):
+        if not slab:
+            return None
         mi = eng.mg_info()
-        own_rows = [int(mi["row1"] - mi["row0"])]
-        if dist is not None:
-            gathered = [None] * world
-            dist.all_gather_object(gathered, own_rows[0])
-            own_rows = [int(x) for x in gathered]
-    eng.iterate(capi.ALL, args.warmup)
-    kernels, dom = {}, "sweep_dist"
-    nprof = 0
-    if headline and not args.no_breakdown:
-        # the dominant kernel (largest total time per iteration) from a short synchronous-event pass; THAT kernel is then timed inside the
-        # timed region with HIP events recorded on the launch stream (no host sync)
-        eng.set_profiling(True)
-        eng.reset_kernel_times()
-        nprof = 3
-        eng.iterate(capi.ALL, nprof)
-        kt = eng.kernel_times()
-        eng.set_profiling(False)
-        kernels = {k: {"ms_per_iter": v[0] / nprof, "launches_per_iter": v[1] / nprof} for k, v in kt.items()}
-        dom = max(kernels, key=lambda k: kernels[k]["ms_per_iter"] if algorithmic_bytes(k, 1, 1, 1, 1, 1) else -1)
-    kernels_per_rank = None
-    if dist is not None and headline and not args.no_breakdown:      # every rank's own breakdown: a measured N-GPU curve can be attributed kernel by kernel
-        kernels_per_rank = [None] * world
-        dist.all_gather_object(kernels_per_rank, {k: round(1e3 * v["ms_per_iter"], 1) for k, v in kernels.items()})
-    watch = dom + ("/16" if dom == "pcg_pass" else "/4")   # HIP events around every 16th (4th) launch (each pair breaks the back-to-back dispatch: ~6 us of stream time)
-    use_watch = headline and os.environ.get("PSGSDF_NO_WATCH") != "1"
+        return int(mi["row1"] - mi["row0"])
+
     timing_iterate = args.loop == "iterate"
-    eng.reset_kernel_times()
-    if use_watch and timing_iterate:
-        eng.watch_kernel(watch)
-    barrier()
-    coll0 = eng.comm_stats()
-    t0 = time.perf_counter()
-    recs_it = eng.iterate(capi.ALL, args.steps)
-    torch.cuda.synchronize()
-    t_iter = time.perf_counter() - t0
-    coll1 = eng.comm_stats()
-    barrier()
-    watched = eng.kernel_times().get(dom, (0.0, 0)) if (use_watch and timing_iterate) else (0.0, 0)
-    eng.watch_kernel("")
-    sync_stats = eng.debug_sync_stats()
-    solve_model = None
-    if headline and dom == "pcg_solve" and not slab and os.environ.get("PSGSDF_BENCH_NO_SOLVE_MODEL") != "1":      # (off under the kernel trace of tools/profile_round.sh: the forced-pass launches would sit in the solve's statistics)
-        # what the dominant kernel's time is made of, measured live: the same launch forced to 16 and to 48 passes (stop rule off) -> time per pass
-        # and the fixed part (assembly of the system from the sweep's voxel blocks, first records, distance update, launch ramp)
-        try:
-            t16 = min(eng.debug_time_pcg_solve(passes=16, reps=4)[0] for _ in range(3)); t48 = min(eng.debug_time_pcg_solve(passes=48, reps=4)[0] for _ in range(3))
-            per = (t48 - t16) / 32.0
-            solve_model = {"us_per_pass": 1e3 * per, "fixed_us": 1e3 * (t16 - 16.0 * per), "solve_16_passes_us": 1e3 * t16, "solve_48_passes_us": 1e3 * t48}
-        except capi.PsgsdfError:
-            solve_model = None
-    tuning = eng.get_tuning()
-    eng.close()
+    use_watch = headline and full and os.environ.get("PSGSDF_NO_WATCH") != "1"
+    it = {"t_iter": None, "recs": None, "kernels": {}, "dom": "sweep_dist", "watched": (0.0, 0), "kernels_per_rank": None, "solve_model": None,
+          "collectives_per_step": None, "n_obs": None, "outputs": None}
+
+    def iterate_context(want_outputs):
+        # ---- context 1: psgsdf_iterate (no stop decision): kernel breakdown, the dominant kernel, the round-2 figure
+        eng = context(st)
+        eng.init_albedo()
+        eng.normalize_weights()
+        it["S"] = eng.info().n_band // world              # per-slab band size (weak: every slab holds one copy of the scene; strong: the mean)
+        it["n_obs"] = eng.step(capi.ALBEDO)["n_obs"] // world
+        it["own_rows"] = band_rows(eng)
+        eng.iterate(capi.ALL, args.warmup)
+        kernels, dom = {}, "sweep_dist"
+        nprof = 0
+        if headline and full and not args.no_breakdown:
+            # the dominant kernel (largest total time per iteration) from a short synchronous-event pass; THAT kernel is then timed inside the
+            # timed region with HIP events recorded on the launch stream (no host sync)
+            eng.set_profiling(True)
+            eng.reset_kernel_times()
+            nprof = 3
+            eng.iterate(capi.ALL, nprof)
+            kt = eng.kernel_times()
+            eng.set_profiling(False)
+            kernels = {k: {"ms_per_iter": v[0] / nprof, "launches_per_iter": v[1] / nprof} for k, v in kt.items()}
+            dom = max(kernels, key=lambda k: kernels[k]["ms_per_iter"] if algorithmic_bytes(k, 1, 1, 1, 1, 1) else -1)
+        if dist is not None and headline and full and not args.no_breakdown:      # every rank's own breakdown: a measured N-GPU curve can be attributed kernel by kernel
+            it["kernels_per_rank"] = [None] * world
+            dist.all_gather_object(it["kernels_per_rank"], {k: round(1e3 * v["ms_per_iter"], 1) for k, v in kernels.items()})
+        it["kernels"], it["dom"] = kernels, dom
+        it["watch"] = dom + ("/16" if dom == "pcg_pass" else "/4")   # HIP events around every 16th (4th) launch (each pair breaks the back-to-back dispatch: ~6 us of stream time)
+        eng.reset_kernel_times()
+        if use_watch and timing_iterate:
+            eng.watch_kernel(it["watch"])
+        barrier()
+        coll0 = eng.comm_stats()
+        t0 = time.perf_counter()
+        it["recs"] = eng.iterate(capi.ALL, args.steps)
+        torch.cuda.synchronize()
+        it["t_iter"] = time.perf_counter() - t0
+        coll1 = eng.comm_stats()
+        barrier()
+        it["collectives_per_step"] = (coll1 - coll0) / max(args.steps, 1)
+        if use_watch and timing_iterate:
+            it["watched"] = eng.kernel_times().get(dom, (0.0, 0))
+        eng.watch_kernel("")
+        it["sync_stats"] = eng.debug_sync_stats()
+        if collect and want_outputs:
+            it["outputs"] = collect(eng, it["recs"])
+        if headline and full and dom == "pcg_solve" and not slab and os.environ.get("PSGSDF_BENCH_NO_SOLVE_MODEL") != "1":      # (off under the kernel trace of tools/profile_round.sh: the forced-pass launches would sit in the solve's statistics)
+            # what the dominant kernel's time is made of, measured live: the same launch forced to 16 and to 48 passes (stop rule off) -> time per pass
+            # and the fixed part (assembly of the system from the sweep's voxel blocks, first records, distance update, launch ramp)
+            try:
+                t16 = min(eng.debug_time_pcg_solve(passes=16, reps=4)[0] for _ in range(3)); t48 = min(eng.debug_time_pcg_solve(passes=48, reps=4)[0] for _ in range(3))
+                per = (t48 - t16) / 32.0
+                it["solve_model"] = {"us_per_pass": 1e3 * per, "fixed_us": 1e3 * (t16 - 16.0 * per), "solve_16_passes_us": 1e3 * t16, "solve_48_passes_us": 1e3 * t48}
+            except capi.PsgsdfError:
+                it["solve_model"] = None
+        it["tuning"] = eng.get_tuning()
+        eng.close()
+
+    if full or timing_iterate:
+        iterate_context(timing_iterate)
+    sync_stats, tuning = it.get("sync_stats"), it.get("tuning")
 
     # ---- context 2: psgsdf_optimize, the loop voxelPS runs (initAlbedo + weight normalisation + iterations with the stop decision)
-    st2 = capi.default_settings(model_id)
-    st2.reg_weight_n, st2.reg_weight_l, st2.damping = st.reg_weight_n, st.reg_weight_l, st.damping
-    st2.max_it, st2.conv_threshold, st2.upsample = args.warmup + args.steps + 4, 0.0, 0
+    t_reps, recs_opt, opt_calls, opt = None, None, 1, {"outputs": None, "S": None, "own_rows": None}
     watched_opt = [(0.0, 0)]
+    if full or not timing_iterate:
+        st2 = capi.default_settings(model_id)
+        st2.reg_weight_n, st2.reg_weight_l, st2.damping = st.reg_weight_n, st.reg_weight_l, st.damping
+        st2.max_it, st2.conv_threshold, st2.upsample = args.warmup + args.steps + 4, 0.0, 0
 
-    def before_timed(e):
+        def before_timed(e):
+            if use_watch and not timing_iterate:
+                e.reset_kernel_times()
+                e.watch_kernel(it["watch"])
+
+        def after_call(e, call):
+            nonlocal sync_stats, tuning
+            if call == 0 and use_watch and not timing_iterate:
+                watched_opt[0] = e.kernel_times().get(it["dom"], (0.0, 0))
+                e.watch_kernel("")
+            if call == 0 and opt["S"] is None:
+                opt["S"], opt["own_rows"] = e.info().n_band // world, band_rows(e)
+            if tuning is None:
+                tuning = e.get_tuning()
+            s2 = e.debug_sync_stats()
+            if sync_stats is None:
+                sync_stats = s2
+                return
+            for k in sync_stats:
+                sync_stats[k] = max(sync_stats[k], s2[k]) if k in STATE_STATS else sync_stats[k] + s2[k]
+
+        def on_last(e, recs):
+            opt["outputs"] = collect(e, recs)
+        t_reps, recs_opt, opt_calls = timed_optimize(lambda: context(st2), torch, dist, args.steps, args.warmup, reps if headline else 1, before_timed, after_call,
+                                                     on_last if (collect and not timing_iterate) else None)
         if use_watch and not timing_iterate:
-            e.reset_kernel_times()
-            e.watch_kernel(watch)
+            it["watched"] = watched_opt[0]
+        if t_reps is None and (it["t_iter"] is None or (collect and it["outputs"] is None)):      # (psgsdf_optimize does not survive 3 iterations on this scene: the line falls back to psgsdf_iterate)
+            iterate_context(True)
+            sync_stats, tuning = it["sync_stats"], it["tuning"]
 
-    def after_call(e, call):
-        if call == 0 and use_watch and not timing_iterate:
-            watched_opt[0] = e.kernel_times().get(dom, (0.0, 0))
-            e.watch_kernel("")
-        s2 = e.debug_sync_stats()
-        for k in sync_stats:
-            sync_stats[k] = max(sync_stats[k], s2[k]) if k in STATE_STATS else sync_stats[k] + s2[k]
-    t_reps, recs_opt, opt_calls = timed_optimize(lambda: context(st2), torch, dist, args.steps, args.warmup, reps if headline else 1, before_timed, after_call)
-    if use_watch and not timing_iterate:
-        watched = watched_opt[0]
+    S = it.get("S", opt["S"])
+    own_rows = it.get("own_rows", opt["own_rows"])
+    if slab and dist is not None:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, own_rows)
+        own_rows = [int(x) for x in gathered]
+    elif slab:
+        own_rows = [own_rows]
+    t_iter = it["t_iter"]
 
     def over_ranks(x):      # MAX over the ranks (the contract's clock: the slowest rank)
         if dist is None or x is None:
@@ -357,23 +443,25 @@ def measure(args, model, torch, dist, rank, world, device, slab, share, headline
         for k in sync_stats:
             sync_stats[k] = max(g[k] for g in gathered) if (k in STATE_STATS or k == "persist_fallbacks") else sync_stats[k]
 
-    loop = f"psgsdf_optimize ({opt_calls - 1} timed call{'s' if opt_calls != 2 else ''} on fresh contexts after one untimed, {reps if headline else 1} repetition{'s' if (reps if headline else 1) != 1 else ''} of the {args.steps}-step bracket)"
+    n_reps = reps if headline else 1
+    loop = f"psgsdf_optimize ({opt_calls - 1} timed call{'s' if opt_calls != 2 else ''} on fresh contexts after one untimed, {n_reps} repetition{'s' if n_reps != 1 else ''} of the {args.steps}-step bracket)"
     if timing_iterate or t_opt is None:
-        elapsed, recs = t_iter, recs_it
+        elapsed, recs, outputs = t_iter, it["recs"], it["outputs"]
         loop = "psgsdf_iterate" + ("" if timing_iterate else " (psgsdf_optimize does not survive 3 iterations on this scene)")
     else:
-        elapsed, recs = t_opt, recs_opt
+        elapsed, recs, outputs = t_opt, recs_opt, opt["outputs"]
     cg_iters = float(np.mean([r["cg_iters"] for r in recs]))
     mult = 1 if args.strong else world
     spread = None
     if t_reps and not (timing_iterate or t_opt is None):
         vals = [mult * args.steps / t for t in t_reps]
         spread = {"reps": len(vals), "min": min(vals), "max": max(vals), "values": [round(v, 1) for v in vals], "statistic": "value = median over the repetitions of the K-step bracket (fresh contexts each)"}
-    res = dict(model=model, value=mult * args.steps / elapsed, ms_per_step=1e3 * elapsed / args.steps, spread=spread, loop=loop, S=int(S), n_obs=int(n_obs), cg_iters=cg_iters,
-               iterate_ms_per_step=1e3 * t_iter / args.steps, optimize_ms_per_step=(1e3 * t_opt / args.steps) if t_opt else None,
-               kernels=kernels, dom=dom, watched=watched, t_gen=t_gen, st=st, sc=sc, sync_stats=sync_stats,
-               collectives_per_step=(coll1 - coll0) / max(args.steps, 1), use_u8=use_u8, own_rows=own_rows,
-               scene_kw=scene_kw, solve_model=solve_model, tuning=tuning, make_context=lambda: context(st), kernels_per_rank=kernels_per_rank)
+    res = dict(model=model, value=mult * args.steps / elapsed, ms_per_step=1e3 * elapsed / args.steps, spread=spread, loop=loop, S=int(S),
+               n_obs=None if it["n_obs"] is None else int(it["n_obs"]), cg_iters=cg_iters,
+               iterate_ms_per_step=None if t_iter is None else 1e3 * t_iter / args.steps, optimize_ms_per_step=(1e3 * t_opt / args.steps) if t_opt else None,
+               kernels=it["kernels"], dom=it["dom"], watched=it["watched"], t_gen=t_gen, st=st, sc=sc, sync_stats=sync_stats,
+               collectives_per_step=it["collectives_per_step"], use_u8=use_u8, own_rows=own_rows, outputs=outputs,
+               scene_kw=scene_kw, solve_model=it["solve_model"], tuning=tuning, make_context=lambda: context(st), kernels_per_rank=it["kernels_per_rank"])
     return res
 
 
@@ -504,7 +592,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step bracket (fresh contexts each): value = their median, spread = min / max")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the K-step bracket (fresh contexts each): value = their median, spread = min / max (default 1; 5 with --full)")
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--width", type=int, default=640)
@@ -520,7 +608,14 @@ def main():
     ap.add_argument("--configs4", default="512:100", help="grid:keyframes of the BASELINE configs[4] extra of the N > 1 line (SH2; tests pass a small one)")
     ap.add_argument("--probe-only", action="store_true", help="no measurement: the first-contact probe of a multi-GPU node (tools/first_contact.py: communicator, one collective, the in-kernel hand-off forms per memory kind between every neighbour pair, two iterations with every in-kernel exchange against one context), one JSON line, every phase under a wall-clock bound")
     ap.add_argument("--loop", default="optimize", choices=["optimize", "iterate"], help="which loop `value` times (iterate: the round-2 figure, no stop decision)")
+    ap.add_argument("--full", action="store_true", help="everything else the benchmark measures next to `value`: the psgsdf_iterate figure, the kernel breakdown and roofline (with live counter passes), the CPU baseline, "
+                    "the other models / solvers / workloads as `extra`, and on N > 1 ranks the full-size check and the weak-scaling and configs[4] runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed loop computed in its last step as DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.probe_only:
         import subprocess
         sys.exit(subprocess.call([sys.executable, os.path.join(ROOT, "tools", "first_contact.py"), "--gpus", str(max(args.gpus, 2))]))
@@ -611,8 +706,11 @@ def main():
                 if rank == 0:
                     print("bench.py: the self-check fails on the communicator paths too: " + "; ".join(f"rank {i}: {v[1]}" for i, v in enumerate(votes) if v[1]), file=sys.stderr)
                 sys.exit(4)
-    m = measure(args, args.model, torch, dist, rank, world, device, slab, share, headline=True)
-    if world > 1 and args.strong and os.environ.get("PSGSDF_BENCH_NO_FULL_CHECK") != "1":
+    collect = (lambda eng, recs: collect_outputs(eng, recs, slab, DUMP_CAP_BYTES // world)) if args.dump_outputs else None
+    m = measure(args, args.model, torch, dist, rank, world, device, slab, share, headline=True, collect=collect)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, m.pop("outputs"), rank, world)
+    if world > 1 and args.full and args.strong and os.environ.get("PSGSDF_BENCH_NO_FULL_CHECK") != "1":
         check = [check, full_size_check(m["make_context"], m, args, args.model, torch, dist, rank, world, device)]
     S, n_obs, cg_iters, kernels, dom, watched, st, sc = m["S"], m["n_obs"], m["cg_iters"], m["kernels"], m["dom"], m["watched"], m["st"], m["sc"]
     use_u8 = m["use_u8"]
@@ -626,15 +724,16 @@ def main():
         "config": {"workload": f"synthetic {args.width}x{args.height} RGB-D bumpy sphere, {args.grid}^3 grid, {args.model}, {args.frames} keyframes, "
                                "albedo+light+distance+pose blocks, Cauchy IRLS, Eikonal reg (config_skorates.json settings)",
                    "loop": m["loop"] + ": stop decision (convergence / divergence test on the host) after every iteration; each timed call ends itself before the loop's own divergence exit would",
-                   "band_voxels": int(S), "observations": int(n_obs), "pcg_iters_per_step": cg_iters,
+                   "band_voxels": int(S), "observations": None if n_obs is None else int(n_obs), "pcg_iters_per_step": cg_iters,
                    "parallelism": "single GPU" if world == 1 else
                    (f"strong scaling: ONE {args.grid}^3 volume with {args.frames} keyframes cut into {world} z-slabs of equal band count (one per GPU; every rank synthesises and uploads only its own planes), native slab loop of the C++ host; exchanges inside the kernels over IPC-mapped peer memory, RCCL for set-up and as the fallback" if args.strong else
                     f"{world} z-slabs (one per GPU), grid {args.grid}x{args.grid}x{args.grid * world}, {args.frames * world} keyframes, native slab loop of the C++ host; exchanges inside the kernels over IPC-mapped peer memory, RCCL for set-up and as the fallback")},
-        "iterate_ms_per_step": m["iterate_ms_per_step"],      # psgsdf_iterate: the same iterations without a stop decision (round-2 `value`)
-        "iterate_value": (1 if args.strong else world) * 1e3 / m["iterate_ms_per_step"],
         "optimize_ms_per_step": m["optimize_ms_per_step"],
         "spread": m["spread"],
     }
+    if m["iterate_ms_per_step"] is not None:      # psgsdf_iterate: the same iterations without a stop decision (round-2 `value`; --full or --loop iterate)
+        out["iterate_ms_per_step"] = m["iterate_ms_per_step"]
+        out["iterate_value"] = (1 if args.strong else world) * 1e3 / m["iterate_ms_per_step"]
     if world > 1:
         # degraded: the line is not the design's N-GPU figure -- the cross-rank persistent solve is off or fell back, or the N-rank result is wrong
         out["multi_gpu"], out["degraded"] = multi_gpu_block(m, check, world, share)
@@ -642,6 +741,17 @@ def main():
             out["multi_gpu"]["fallback"] = fallback; out["degraded"] = True
 
     if rank == 0:
+        if slab:
+            out["config"]["collectives_per_step"] = m["collectives_per_step"]
+            out["config"]["band_rows_per_rank"] = m["own_rows"]
+        out["config"]["frame_solver"] = m["tuning"]["effective"].get("frame_solve", "ldlt") + (
+            " (light / pose blocks: every frame's block solved directly, LDL^T in double, inside the sweep; the reference's own solver -- ONE global float Jacobi-PCG, PSGSDF_FRAME_SOLVE=eigen -- is measured under extra.reference_frame_solver)"
+            if m["tuning"]["effective"].get("frame_solve", "ldlt") == "ldlt" else " (the reference's solver of the light / pose blocks: one global float Jacobi-PCG over all frames, csrc/frame_solve.hip)")
+        out["sync_stats"] = m["sync_stats"]      # scalar read-backs validated / found late / persistent-solve fallbacks in this run (include/psgsdf.h)
+        out["tuning"] = {"build": m["tuning"]["build"], "env": m["tuning"]["env"], "ignored_dev_only": m["tuning"]["ignored_dev_only"]}      # psgsdf_get_tuning: every PSGSDF_* knob that was in force
+        out["setup_s"] = {"scene_generation": round(m["t_gen"], 1)}
+
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, timed live with HIP events inside the timed region
         lap = st.reg_weight_l != 0.0
         # event pairs recorded on the launch stream around every 16th launch: the pair also reads the dispatch latency, so this is
@@ -706,9 +816,6 @@ def main():
         # whole-iteration algorithmic bytes (SURVEY.md §8d formula) for reference
         U = min(48 * n_obs, 12 * args.width * args.height * args.frames)
         B_iter = 4 * (S * 60 + U) + 120 * S + 124 * cg_iters * S   # SURVEY §8d per-pass figure kept (the fused pass moves 144 B/row)
-        if slab:
-            out["config"]["collectives_per_step"] = m["collectives_per_step"]
-            out["config"]["band_rows_per_rank"] = m["own_rows"]
         out["iteration"] = {"algorithmic_bytes": B_iter, "achieved_GBs": B_iter * (m["value"] / world) / 1e9,
                             "frac_of_hbm_peak": B_iter * (m["value"] / world) / 1e9 / HBM_PEAK_GBS}
         if pj:      # the same fraction from the COUNTERS (archived passes): what really crosses the HBM interface per iteration -- nothing on this path is bandwidth-bound
@@ -731,12 +838,6 @@ def main():
             # per-kernel roofline fractions from the same synchronous-event pass (events add ~4 us per launch: fractions err low)
             out["kernel_roofline_frac"] = {k: round(algorithmic_bytes(k, S, n_obs, args.width, args.height, args.frames, lap, pcg_passes=cg_iters + 1.0) / (v["ms_per_iter"] / max(v["launches_per_iter"], 1e-9) * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
                                            for k, v in kernels.items() if algorithmic_bytes(k, 1, 1, 1, 1, 1) and v["ms_per_iter"] > 0}
-        out["config"]["frame_solver"] = m["tuning"]["effective"].get("frame_solve", "ldlt") + (
-            " (light / pose blocks: every frame's block solved directly, LDL^T in double, inside the sweep; the reference's own solver -- ONE global float Jacobi-PCG, PSGSDF_FRAME_SOLVE=eigen -- is measured under extra.reference_frame_solver)"
-            if m["tuning"]["effective"].get("frame_solve", "ldlt") == "ldlt" else " (the reference's solver of the light / pose blocks: one global float Jacobi-PCG over all frames, csrc/frame_solve.hip)")
-        out["sync_stats"] = m["sync_stats"]      # scalar read-backs validated / found late / persistent-solve fallbacks in this run (include/psgsdf.h)
-        out["tuning"] = {"build": m["tuning"]["build"], "env": m["tuning"]["env"], "ignored_dev_only": m["tuning"]["ignored_dev_only"]}      # psgsdf_get_tuning: every PSGSDF_* knob that was in force
-        out["setup_s"] = {"scene_generation": round(m["t_gen"], 1)}
 
         # ---- CPU baseline: the oracle (a port of the reference's arithmetic) on the host cores, bounded sample
         if world == 1 and not slab and not args.no_cpu_baseline and not args.strong:
@@ -781,7 +882,7 @@ def main():
     m.pop("make_context", None)
     del m, sc
     # ---- the other shading models on the same grid / keyframe shape (BASELINE configs[3] = LED; SH2 = configs[4]'s model at the headline size)
-    if world == 1 and not slab and not args.no_extra and not args.strong and (args.grid, args.frames, args.model) == (256, 50, "SH1"):
+    if args.full and world == 1 and not slab and not args.no_extra and not args.strong and (args.grid, args.frames, args.model) == (256, 50, "SH1"):
         extra = {}
         for mod in ("LED", "SH2"):
             e = measure(args, mod, torch, dist, rank, world, device, slab, share, headline=False)
@@ -825,7 +926,7 @@ def main():
             extra["voxelps_e2e"] = {"error": repr(ex)[:300]}
         if rank == 0:
             out["extra"] = extra
-    if world > 1 and not args.no_extra and not explicit_strong and not args.weak:
+    if args.full and world > 1 and not args.no_extra and not explicit_strong and not args.weak:
         # ---- the other two N-rank workloads ride along, each with its own self-check and `degraded`
         import copy
         extra = {}

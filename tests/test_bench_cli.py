@@ -19,3 +19,9 @@ def test_world_size_that_disagrees_with_gpus_is_refused(built):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=300, cwd=ROOT,
                        env=dict(CLEAN, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and r.stdout.strip() == "" and "WORLD_SIZE" in r.stderr
+
+
+def test_full_and_dump_outputs_are_options():
+    """a plain run measures the headline only; --full adds the rest, --dump-outputs DIR writes what the timed loop computed"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT, env=CLEAN)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _one_json(out):
 
 
 def test_single_gpu_line(built):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--grid", "64", "--frames", "8"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--grid", "64", "--frames", "8", "--full"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json(r.stdout)
@@ -33,6 +34,34 @@ def test_single_gpu_line(built):
     rf = d["roofline"]
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9 and rf["launches_timed"] > 0
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_line_times_the_steps_and_dumps_the_outputs(built, tmp_path):
+    """Without --full the line carries the headline only: one repetition of exactly --steps timed steps, nothing measured beside them.  --dump-outputs
+    writes what the timed loop hands its caller after the last step; two runs with the same arguments write the same bits (seeded inputs, and the
+    engine is reproducible across processes: tests/test_repro_gpu.py)."""
+    lines, dumps = [], []
+    for run in range(2):
+        dump = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--grid", "64", "--frames", "8", "--dump-outputs", str(dump)],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_one_json(r.stdout))
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(dump.iterdir())})
+    d = lines[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"} <= set(d)
+    assert d["steps"] == 5 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "it/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["spread"]["reps"] == 1 and "1 repetition of the 5-step bracket" in d["config"]["loop"]
+    assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
+    assert not {"cpu_baseline", "roofline", "extra", "iterate_ms_per_step", "kernels_sync_pass", "pmc_live"} & set(d)
+    out = dumps[0]
+    assert set(out) == {"dist", "grad", "albedo", "band_index", "poses", "light", "records"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    S = d["config"]["band_voxels"]
+    assert out["dist"].shape == (S,) and out["grad"].shape == (3, S) and out["albedo"].shape == (3, S) and out["poses"].shape == (8, 16)
+    assert out["records"].shape[0] == 5 and np.all(np.diff(out["band_index"]) > 0) and np.isfinite(out["dist"]).all()
+    for k in out:
+        assert np.array_equal(out[k], dumps[1][k]), k
 
 
 @pytest.mark.parametrize("world", [2, 8])
@@ -45,7 +74,7 @@ def test_n_ranks_share_the_gpu(built, world):
     env = dict(os.environ, PSGSDF_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", PSGSDF_FAULT_DUMP="400", GLOO_SOCKET_IFNAME="lo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PSGSDF_CU_MASK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--reps", "2", "--grid", "64", "--frames", "8", "--configs4", "48:70"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--reps", "2", "--grid", "64", "--frames", "8", "--configs4", "48:70", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=560, cwd=ROOT, env=env)
     if r.returncode != 0 and "gave up" in r.stderr:
         # N processes time-share ONE GPU here and every in-kernel wait for another rank is bounded: once in ~80 runs of the whole suite (round 6: 1 of 25 suite
@@ -80,6 +109,28 @@ def test_n_ranks_share_the_gpu(built, world):
     assert d["spread"]["reps"] == 2 and d["spread"]["min"] <= d["value"] <= d["spread"]["max"]
 
 
+def test_plain_line_two_ranks_share_the_gpu(built, tmp_path):
+    """the plain N-rank line: the pre-timing self-check and the strong-scaling measurement, nothing beside them; --dump-outputs writes every rank's
+    own slab (its band voxels are its own: the two index sets do not overlap)"""
+    env = dict(os.environ, PSGSDF_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", PSGSDF_FAULT_DUMP="300", GLOO_SOCKET_IFNAME="lo")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PSGSDF_CU_MASK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--grid", "64", "--frames", "8", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _one_json(r.stdout)
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and d["scaling"] == "strong" and d["spread"]["reps"] == 1
+    assert not {"extra", "roofline", "cpu_baseline", "iterate_ms_per_step"} & set(d)
+    mg = d["multi_gpu"]
+    assert mg["ranks"] == 2 and mg["self_check"]["ok"] and mg["cross_rank_ready"] == 1 and mg["cross_rank_solves"] > 0
+    rows = d["config"]["band_rows_per_rank"]
+    assert len(rows) == 2 and min(rows) > 0
+    bands = [np.load(tmp_path / f"band_index_rank{k}.npy") for k in range(2)]
+    assert [len(b) for b in bands] == rows and not np.intersect1d(bands[0], bands[1]).size
+    for k in range(2):
+        assert np.load(tmp_path / f"records_rank{k}.npy").shape[0] == 3 and np.load(tmp_path / f"dist_rank{k}.npy").shape == (rows[k],)
+
+
 def test_more_ranks_than_devices_is_refused(built):
     """`--gpus 2` on the one-GPU box without PSGSDF_BENCH_SHARE_GPU: non-zero exit and no line -- never an n_gpus other than --gpus -- and the
     same when a launcher's WORLD_SIZE disagrees with --gpus"""
@@ -103,7 +154,7 @@ def test_strong_scaling_mode_two_ranks_share_the_gpu(built):
         env = dict(os.environ, PSGSDF_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", PSGSDF_FAULT_DUMP="120", GLOO_SOCKET_IFNAME="lo",
                    RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=port)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--strong", "--steps", "3", "--warmup", "1", "--grid", "48", "--frames", "6", "--model", "SH2",
-                                       "--width", "160", "--height", "120"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
+                                       "--width", "160", "--height", "120", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
     try:
         outs = [p.communicate(timeout=150) for p in procs]
     finally:
@@ -147,7 +198,7 @@ def test_failed_in_kernel_exchange_falls_back_to_the_communicator(built):
                PSGSDF_BENCH_FAULT="1:PSGSDF_FAULT_HALO=2", PSGSDF_BENCH_WATCHDOG_S="400", PSGSDF_DESTROY_TIMEOUT_S="3")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PSGSDF_CU_MASK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--reps", "1", "--grid", "64", "--frames", "8", "--no-extra"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--reps", "1", "--grid", "64", "--frames", "8", "--no-extra", "--full"],
                        capture_output=True, text=True, timeout=450, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_json(r.stdout)

@@ -3,7 +3,7 @@
 tag=$1; shift
 out=gpurun_out/ab_${tag}.txt; mkdir -p gpurun_out; : > $out
 for v in "$@"; do
-  env $v python bench.py --no-cpu-baseline --no-extra --reps 3 2>/dev/null | python -c "
+  env $v python bench.py --full --no-cpu-baseline --no-extra --reps 3 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 k = d.get('kernels_sync_pass') or {}

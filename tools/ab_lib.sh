@@ -3,7 +3,7 @@
 tag=$1; A=$2; B=$3; n=${4:-3}
 out=gpurun_out/ab_${tag}.txt; mkdir -p gpurun_out; : > $out
 for r in $(seq 1 $n); do for lib in $A $B; do
-  PSGSDF_ENGINE_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-extra --reps 3 2>/dev/null | python -c "
+  PSGSDF_ENGINE_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-extra --reps 3 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 rf = d['roofline']

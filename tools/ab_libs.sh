@@ -4,7 +4,7 @@
 tag=$1; n=$2; shift 2
 out=gpurun_out/ab_${tag}.txt; mkdir -p gpurun_out; : > $out
 for r in $(seq 1 $n); do for lib in "$@"; do
-  PSGSDF_ENGINE_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-extra --reps 3 $AB_BENCH_ARGS 2>/dev/null | python -c "
+  PSGSDF_ENGINE_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-extra --reps 3 $AB_BENCH_ARGS 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 k = d.get('kernels_sync_pass') or {}

@@ -51,7 +51,7 @@ def per_iteration(agg, json_out, commit):
         src_hash = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "psgradientsdf_amd", "csrc", ".build_hash")).read().strip()[:12]
     except OSError:
         src_hash = None
-    json.dump({"source": "rocprofv3 --kernel-trace of `python bench.py --no-cpu-baseline --no-extra` (tools/profile_round.sh)", "commit": commit, "source_hash": src_hash, "iterations_traced": solves,
+    json.dump({"source": "rocprofv3 --kernel-trace of `python bench.py --full --no-cpu-baseline --no-extra` (tools/profile_round.sh)", "commit": commit, "source_hash": src_hash, "iterations_traced": solves,
                "kernels": per, "us_per_iteration": round(once, 1), "note": "us_per_iteration = sum of the average durations of the kernels that run once per iteration (launches >= iterations_traced)"}, open(json_out, "w"), indent=1)
 
 
