@@ -16,6 +16,11 @@ import numpy as np
 ALBEDO, LIGHT, DIST, POSE, ALL = 1, 2, 4, 8, 15
 SH1, SH2, LED = 0, 1, 2
 L2, CAUCHY, HUBER, TUKEY, TRUNC_L2 = 0, 1, 2, 3, 4
+# output planes of Api.render (include/psgsdf_render.h), in bit order, with their channel counts
+R_DEPTH, R_NORMAL, R_ALBEDO, R_SHADING, R_RENDERED, R_RESIDUAL, R_VOXEL = 1, 2, 4, 8, 16, 32, 64
+R_ALL = 127
+_R_PLANES = [("depth", R_DEPTH, 1), ("normal", R_NORMAL, 3), ("albedo", R_ALBEDO, 3), ("shading", R_SHADING, 1),
+             ("rendered", R_RENDERED, 3), ("residual", R_RESIDUAL, 3), ("voxel", R_VOXEL, 1)]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ENGINE_LIB = os.environ.get("PSGSDF_ENGINE_LIB") or os.path.join(_HERE, "csrc", "libpsgsdf.so")      # (the override is for A/B runs of two BUILDS on one box: tools/)
@@ -62,6 +67,21 @@ class Info(C.Structure):
     _fields_ = [("dim", C.c_int32 * 3), ("voxel_size", C.c_float), ("origin", C.c_float * 3), ("n_frames", C.c_int32),
                 ("n_band", C.c_int32), ("light_stride", C.c_int32), ("vis_words", C.c_int32),
                 ("reg_weight_n", C.c_float), ("reg_weight_l", C.c_float)]
+
+
+class View(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("pose", C.c_float * 16), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("light_frame", C.c_int32)]
+
+
+class RenderStats(C.Structure):
+    _fields_ = [("n_pixels", C.c_int64), ("n_hits", C.c_int64), ("n_hits_off_band", C.c_int64),
+                ("sum_r2", C.c_double * 3), ("sum_abs_r", C.c_double * 3), ("robust", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["sum_r2"], d["sum_abs_r"] = list(self.sum_r2), list(self.sum_abs_r)
+        return d
 
 
 def default_settings(model=SH1, **kw):
@@ -321,6 +341,49 @@ class Api:
                                                  weight.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p),
                                                  vis.ctypes.data_as(C.c_void_p) if want_vis else None), "download_volume")
         return dict(dist=dist, grad=grad, weight=weight, rgb=rgb, vis=vis)
+
+    # -- view rendering (include/psgsdf_render.h)
+    def render(self, frame=None, pose=None, K=None, size=None, channels=None, light_frame=0):
+        """frame: a keyframe view; otherwise a caller's camera: pose (4x4 or 16 camera->world), K (3x3 or [fx, fy, cx, cy]), size (W, H),
+        shaded with the light of keyframe light_frame.  channels: R_* bits (default: every plane the view has).  Returns {plane name: array [ch, H, W] (voxel: int32 [H, W], depth / shading: [H, W])}
+        plus "stats" (RenderStats.as_dict)."""
+        v = View()
+        if frame is not None:
+            v.frame = int(frame)
+            w_, h_ = C.c_int32(), C.c_int32()
+            self._check(self._fn("render_size")(self.ctx, C.byref(v), C.byref(w_), C.byref(h_)), "render_size")
+            W, H = w_.value, h_.value
+            channels = R_ALL if channels is None else channels
+        else:
+            if pose is None or K is None or size is None:
+                raise ValueError("render: a keyframe or (pose, K, size)")
+            channels = (R_ALL & ~R_RESIDUAL) if channels is None else channels
+            v.frame = -1
+            v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
+            k = np.asarray(K, np.float64).reshape(-1)
+            v.fx, v.fy, v.cx, v.cy = (k[0], k[4], k[2], k[5]) if k.size == 9 else tuple(k[:4])
+            v.width, v.height = int(size[0]), int(size[1])
+            v.light_frame = int(light_frame)
+            W, H = v.width, v.height
+        nch = sum(n for _, bit, n in _R_PLANES if channels & bit)
+        out = np.zeros((max(nch, 1), H, W), np.float32)
+        st = RenderStats()
+        self._check(self._fn("render")(self.ctx, C.byref(v), C.c_uint32(channels), out.ctypes.data_as(C.c_void_p) if nch else None, C.byref(st)), "render")
+        res, q = {}, 0
+        for name, bit, n in _R_PLANES:
+            if channels & bit:
+                a = out[q:q + n]
+                res[name] = a.view(np.int32)[0].copy() if name == "voxel" else (a[0].copy() if n == 1 else a.copy())
+                q += n
+        res["stats"] = st.as_dict()
+        return res
+
+    def render_report(self):
+        """per keyframe: RenderStats.as_dict of the re-rendering of that keyframe (one batched pass)"""
+        F = self.info().n_frames
+        arr = (RenderStats * F)()
+        self._check(self._fn("render_report")(self.ctx, arr), "render_report")
+        return [arr[f].as_dict() for f in range(F)]
 
     # -- the writers' geometry, extracted on the device (valid until the next extraction: copied here)
     def extract_mesh(self):

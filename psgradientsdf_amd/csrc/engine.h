@@ -277,5 +277,33 @@ void launch_track(const DenseView& d, const GridP& g, const Cam& cam, const Fram
 void launch_integrate(const DenseView& d, uint64_t* vis_seq, int wpv_seq, const GridP& g, const Cam& cam, const FrameP& fp,
                       const float* rgb, const float* depth, const float* normals, int counter, float z_min, float z_max, hipStream_t s);
 
+// ---- view rendering (render.hip; include/psgsdf_render.h) -------------------------------------
+constexpr int kRenderBrick = 8;      // brick edge (voxels) of the empty-space map
+constexpr int kRenderTile = 8;       // one wavefront per 8 x 8 pixel tile
+constexpr int kRenderStats = 9;      // per-tile partials: hits, off-band hits, sum r^2 [3], sum |r| [3], robust
+enum { RP_DEPTH = 0, RP_NORMAL, RP_ALBEDO, RP_SHADING, RP_RENDERED, RP_RESIDUAL, RP_VOXEL, RP_COUNT };
+struct RenderArgs {
+    DenseView d;                     // dense planes, the band written back into them
+    const float4* vp[3];             // Band::vp (band rows: nfd and rho at the hit)
+    GridP grid;
+    const FrameP* frames;            // current poses and lights
+    ImgSrc im; int img_w, img_h;     // keyframe stack
+    Robust rob;
+    const unsigned char* bricks;     // [nb2][nb1][nb0] 1 = the brick may hold a hit
+    const int* bbox;                 // occupied bricks: min brick index [3], -(max brick index) [3]
+    int nb[3];
+    Cam cam;                         // the view's intrinsics and size
+    int frame;                       // keyframe view (k_render: the keyframe; k_render_report: -1, the keyframe is blockIdx.y); -1 = a caller's camera
+    int light_frame;                 // keyframe whose light shades the view
+    FrameP pose;                     // a caller's camera: R, t
+    int tiles_x, tiles_y;
+    float* planes[RP_COUNT];         // [ch][H][W] device planes (nullptr: not asked for)
+    double* part;                    // [frames][tiles][kRenderStats] per-workgroup partials
+};
+void launch_render_bricks(const DenseView& d, const GridP& g, float thr, unsigned char* bricks, int* bbox, hipStream_t s);   // bbox: 6 ints, pre-filled with 0x7f bytes
+void launch_render(const RenderArgs& a, int model, hipStream_t s);
+void launch_render_report(const RenderArgs& a, int model, int F, hipStream_t s);
+void launch_render_fold(const double* part, int tiles, int F, double* out /*[F][kRenderStats]*/, hipStream_t s);
+
 
 }  // namespace psg

@@ -1,0 +1,262 @@
+// render.hip -- view rendering of the engine's state (include/psgsdf_render.h):
+//   k_render_bricks   the empty-space map: bricks of 8^3 voxels that may hold a hit, and their bounding box (the rays' clip interval)
+//   k_render          one view: one wavefront per 8 x 8 pixel tile, one ray per lane, the planes asked for + per-tile stat partials
+//   k_render_report   the same traversal for every keyframe at once (keyframe = blockIdx.y), partials only
+//   k_render_fold     the partials of each view summed in one fixed order (one workgroup per view: strided per-thread sums, then an LDS tree):
+//                     reproducible sums, the same for a single view and for its row of the report
+#include "device_common.h"
+
+namespace psg {
+
+// A cell can only hold a hit when phi can reach zero inside it: |p - x_v| <= (sqrt(3) / 2) vs and |g| = 1, so d_v <= (sqrt(3) / 2) vs.  The host
+// passes that bound with a relative margin of 1e-3: a brick is skipped only when no voxel of it can be hit, whatever the rounding.
+__global__ void __launch_bounds__(kBlock) k_render_bricks(DenseView d, GridP g, float thr, int nb0, int nb1, int nb2, unsigned char* __restrict__ bricks, int* __restrict__ bbox) {
+    const int lane = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (b >= (long long)nb0 * nb1 * nb2) return;                     // (wavefront-uniform)
+    const int bz = (int)(b / ((long long)nb0 * nb1)), rest = (int)(b - (long long)bz * nb0 * nb1);
+    const int by = rest / nb0, bx = rest - by * nb0;
+    const int y = by * kRenderBrick + (lane & 7), z = bz * kRenderBrick + (lane >> 3);
+    bool occ = false;
+    if (y < g.dim[1] && z < g.dim[2]) {
+        const long long row = ((long long)z * g.dim[1] + y) * g.dim[0];
+        for (int i = 0; i < kRenderBrick; ++i) {
+            const int x = bx * kRenderBrick + i;
+            if (x < g.dim[0]) occ |= d.weight[row + x] > 0.f && d.dist[row + x] <= thr;
+        }
+    }
+    const bool any = __ballot(occ) != 0ull;
+    if (lane == 0) {
+        bricks[b] = any ? 1 : 0;
+        if (any) {
+            atomicMin(bbox + 0, bx); atomicMin(bbox + 1, by); atomicMin(bbox + 2, bz);
+            atomicMin(bbox + 3, -bx); atomicMin(bbox + 4, -by); atomicMin(bbox + 5, -bz);
+        }
+    }
+}
+void launch_render_bricks(const DenseView& d, const GridP& g, float thr, unsigned char* bricks, int* bbox, hipStream_t s) {
+    int nb[3];
+    for (int k = 0; k < 3; ++k) nb[k] = (g.dim[k] + kRenderBrick - 1) / kRenderBrick;
+    const long long n = (long long)nb[0] * nb[1] * nb[2];
+    hipLaunchKernelGGL(k_render_bricks, dim3((unsigned)((n + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, s, d, g, thr, nb[0], nb[1], nb[2], bricks, bbox);
+}
+
+// The ray u(t) = uo + t uw in voxel units shifted by one half (cell of voxel c: c <= u < c + 1, VoxelGrid::world2voxel), t = camera z.
+// Returns the first t at which phi_v(p) = d_v + g_v.(p - x_v) <= 0 inside an observed cell, and that cell's voxel.  Every boundary crossing is
+// computed from uo and uw directly (no accumulated increments), the same arithmetic as the plain restatement in tests/_render_ref.py.
+__device__ __forceinline__ bool render_trace(const RenderArgs& a, const float* uo, const float* uw, float& t_hit, long long& lin_hit) {
+#pragma clang fp contract(off)
+    // the occupied-brick box, validated BEFORE any arithmetic on it: with no occupied brick the six words keep their 0x7f7f7f7f fill (bbox[k] >= nb[k]),
+    // and only a box of brick indices inside [0, nb) turns into cell bounds inside [0, dim)
+    int lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int b0 = a.bbox[k], b1 = -a.bbox[3 + k];
+        if (b0 < 0 || b0 >= a.nb[k] || b1 < b0 || b1 >= a.nb[k]) return false;
+        lo[k] = b0 * kRenderBrick; hi[k] = min((b1 + 1) * kRenderBrick, a.grid.dim[k]);
+    }
+    float t0 = 0.f, t1 = FLT_MAX, inv[3];
+    int step[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (uw[k] == 0.f) {
+            if (!(uo[k] >= (float)lo[k] && uo[k] < (float)hi[k])) return false;
+            inv[k] = 0.f; step[k] = 0;
+        } else {
+            inv[k] = 1.f / uw[k]; step[k] = uw[k] > 0.f ? 1 : -1;
+            const float ta = ((float)lo[k] - uo[k]) * inv[k], tb = ((float)hi[k] - uo[k]) * inv[k];
+            t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb));
+        }
+    }
+    if (!(t0 < t1)) return false;
+    int c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = min(max((int)floorf(uo[k] + t0 * uw[k]), lo[k]), hi[k] - 1);
+    float t = t0;
+    const int nx = a.grid.dim[0];
+    const long long nxy = (long long)a.grid.dim[0] * a.grid.dim[1];
+    const int max_steps = (hi[0] - lo[0]) + (hi[1] - lo[1]) + (hi[2] - lo[2]) + 8;
+    for (int it = 0; it < max_steps; ++it) {
+        const int bc[3] = {c[0] / kRenderBrick, c[1] / kRenderBrick, c[2] / kRenderBrick};
+        if (!a.bricks[bc[0] + a.nb[0] * (bc[1] + a.nb[1] * bc[2])]) {
+            // empty brick: on to the first cell behind its exit face
+            float tb = FLT_MAX; int ax = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (!step[k]) continue;
+                const float bound = (float)((bc[k] + (step[k] > 0 ? 1 : 0)) * kRenderBrick);
+                const float tt = (bound - uo[k]) * inv[k];
+                if (tt < tb) { tb = tt; ax = k; }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (k == ax) c[k] = step[k] > 0 ? (bc[k] + 1) * kRenderBrick : bc[k] * kRenderBrick - 1;
+                else {
+                    const int b0 = bc[k] * kRenderBrick;
+                    c[k] = min(max((int)floorf(uo[k] + tb * uw[k]), max(b0, lo[k])), min(b0 + kRenderBrick, hi[k]) - 1);
+                }
+            }
+            if (c[ax] < lo[ax] || c[ax] >= hi[ax]) return false;
+            t = fmaxf(t, tb);
+            continue;
+        }
+        float te = FLT_MAX; int ax = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (!step[k]) continue;
+            const float tt = ((float)(c[k] + (step[k] > 0 ? 1 : 0)) - uo[k]) * inv[k];
+            if (tt < te) { te = tt; ax = k; }
+        }
+        const long long lin = (long long)c[0] + (long long)c[1] * nx + (long long)c[2] * nxy;
+        if (a.d.weight[lin] > 0.f) {
+            const float gr[3] = {a.d.g[0][lin], a.d.g[1][lin], a.d.g[2][lin]};
+            float gn[3]; normalized3(gr, gn);
+            float loc[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) loc[k] = (uo[k] + t * uw[k]) - ((float)c[k] + 0.5f);
+            const float phi0 = a.d.dist[lin] + a.grid.vs * dot3(gn, loc);
+            if (phi0 <= 0.f) { t_hit = t; lin_hit = lin; return true; }
+            const float s = a.grid.vs * dot3(gn, uw);
+            if (s < 0.f) {
+                const float th = t - phi0 / s;
+                if (th <= te) { t_hit = th; lin_hit = lin; return true; }
+            }
+        }
+        c[ax] += step[ax];
+        if (c[ax] < lo[ax] || c[ax] >= hi[ax]) return false;
+        t = fmaxf(t, te);
+    }
+    return false;
+}
+
+// One 8 x 8 tile of view `frame` (-1: the caller's camera a.pose, light of a.light_frame); partials of the tile into part slot `slot`.
+// k_render and k_render_report run exactly this code, so that the report's rows equal the single views' stats bit for bit.
+template <int MODEL, int IMG>
+__device__ __forceinline__ void render_tile(const RenderArgs& a, int frame, int tile, long long slot) {
+#pragma clang fp contract(off)
+    constexpr int NB = ModelTraits<MODEL>::NB;
+    const int lane = threadIdx.x & 63;
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const int x = tx * kRenderTile + (lane & 7), y = ty * kRenderTile + (lane >> 3);
+    const bool inside = x < a.cam.W && y < a.cam.H;
+    FrameP fp = frame >= 0 ? a.frames[frame] : a.pose;
+    const int lf = frame >= 0 ? frame : a.light_frame;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) fp.l[i] = a.frames[lf].l[i];
+    const float dc[3] = {((float)x - a.cam.cx) / a.cam.fx, ((float)y - a.cam.cy) / a.cam.fy, 1.f};
+    float w[3]; mul3(fp.R, dc, w);
+    float uo[3], uw[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { uo[k] = (fp.t[k] - a.grid.origin[k]) / a.grid.vs + 0.5f; uw[k] = w[k] / a.grid.vs; }
+    float t = 0.f; long long lin = -1;
+    const bool hit = inside && render_trace(a, uo, uw, t, lin);
+    float n[3] = {0.f, 0.f, 0.f}, rho[3] = {0.f, 0.f, 0.f}, ren[3] = {0.f, 0.f, 0.f}, res[3] = {0.f, 0.f, 0.f}, shade = 0.f;
+    double st[kRenderStats];
+#pragma unroll
+    for (int k = 0; k < kRenderStats; ++k) st[k] = 0.0;
+    if (hit) {
+        const int row = a.d.row_of[lin];
+        if (row >= 0) {      // band voxel: what the energy renders with (Band::vp: nfd, rho)
+            const float4 v0 = a.vp[0][row], v1 = a.vp[1][row], v2 = a.vp[2][row];
+            n[0] = v2.x; n[1] = v2.y; n[2] = v2.z;
+            rho[0] = v0.w; rho[1] = v1.w; rho[2] = v2.w;
+        } else {             // fused voxel outside the band: normalised stored gradient, fused colour
+            const float gr[3] = {a.d.g[0][lin], a.d.g[1][lin], a.d.g[2][lin]};
+            normalized3(gr, n);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) rho[k] = a.d.rho[k][lin];
+            st[1] = 1.0;
+        }
+        st[0] = 1.0;
+        Proj pr{};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pr.p[k] = t * dc[k];
+        float shb[NB];
+        SH<NB>(n, shb);
+        rendered<MODEL>(fp, pr, n, shb, rho, ren);
+        // the scalar shading: the same forward model with unit albedo (and unit LED intensity)
+        const float one[3] = {1.f, 1.f, 1.f};
+        float o[3];
+        if (ModelTraits<MODEL>::LED) { FrameP fu = fp; fu.l[0] = fu.l[1] = fu.l[2] = 1.f; rendered<MODEL>(fu, pr, n, shb, one, o); }
+        else rendered<MODEL>(fp, pr, n, shb, one, o);
+        shade = o[0];
+        if (frame >= 0) {
+            float I[3];
+            const size_t px = ((size_t)frame * a.img_h + y) * a.img_w + x;
+            if (IMG == 1) unpack_rgb8(a.im.u8[px], a.im.scale, I);
+            else { I[0] = a.im.f32[3 * px]; I[1] = a.im.f32[3 * px + 1]; I[2] = a.im.f32[3 * px + 2]; }
+            float rob = 0.f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                res[k] = I[k] - ren[k];
+                st[2 + k] = (double)(res[k] * res[k]);
+                st[5 + k] = (double)fabsf(res[k]);
+                rob += robust_loss<-1>(a.rob, res[k]);
+            }
+            st[8] = (double)rob;
+        }
+    }
+    if (inside) {
+        const size_t HW = (size_t)a.cam.W * a.cam.H, px = (size_t)y * a.cam.W + x;
+        if (a.planes[RP_DEPTH]) a.planes[RP_DEPTH][px] = hit ? t : 0.f;
+        if (a.planes[RP_SHADING]) a.planes[RP_SHADING][px] = shade;
+        if (a.planes[RP_VOXEL]) a.planes[RP_VOXEL][px] = __int_as_float(hit ? (int)lin : -1);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (a.planes[RP_NORMAL]) a.planes[RP_NORMAL][k * HW + px] = n[k];
+            if (a.planes[RP_ALBEDO]) a.planes[RP_ALBEDO][k * HW + px] = rho[k];
+            if (a.planes[RP_RENDERED]) a.planes[RP_RENDERED][k * HW + px] = ren[k];
+            if (a.planes[RP_RESIDUAL]) a.planes[RP_RESIDUAL][k * HW + px] = res[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kRenderStats; ++k) {
+        const double v = wave_sum(st[k]);
+        if (lane == 0) a.part[slot * kRenderStats + k] = v;
+    }
+}
+
+template <int MODEL, int IMG>
+__global__ void __launch_bounds__(64) k_render(RenderArgs a) {
+    render_tile<MODEL, IMG>(a, a.frame, blockIdx.x, blockIdx.x);
+}
+template <int MODEL, int IMG>
+__global__ void __launch_bounds__(64) k_render_report(RenderArgs a) {
+    render_tile<MODEL, IMG>(a, blockIdx.y, blockIdx.x, (long long)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+#define PSG_RENDER_LAUNCH(K, grid, a, model) do { \
+        const bool u8_ = (a).im.u8 != nullptr; \
+        if ((model) == 0) { if (u8_) hipLaunchKernelGGL((K<0, 1>), grid, dim3(64), 0, s, a); else hipLaunchKernelGGL((K<0, 0>), grid, dim3(64), 0, s, a); } \
+        else if ((model) == 1) { if (u8_) hipLaunchKernelGGL((K<1, 1>), grid, dim3(64), 0, s, a); else hipLaunchKernelGGL((K<1, 0>), grid, dim3(64), 0, s, a); } \
+        else { if (u8_) hipLaunchKernelGGL((K<2, 1>), grid, dim3(64), 0, s, a); else hipLaunchKernelGGL((K<2, 0>), grid, dim3(64), 0, s, a); } \
+    } while (0)
+
+void launch_render(const RenderArgs& a, int model, hipStream_t s) {
+    PSG_RENDER_LAUNCH(k_render, dim3(a.tiles_x * a.tiles_y), a, model);
+}
+void launch_render_report(const RenderArgs& a, int model, int F, hipStream_t s) {
+    PSG_RENDER_LAUNCH(k_render_report, dim3(a.tiles_x * a.tiles_y, F), a, model);
+}
+
+__global__ void __launch_bounds__(kBlock) k_render_fold(const double* __restrict__ part, int tiles, double* __restrict__ out) {
+    __shared__ double red[kBlock];
+    const size_t base = (size_t)blockIdx.x * tiles;
+    for (int k = 0; k < kRenderStats; ++k) {
+        double v = 0.0;
+        for (int i = threadIdx.x; i < tiles; i += kBlock) v += part[(base + i) * kRenderStats + k];
+        red[threadIdx.x] = v;
+        __syncthreads();
+        for (int h = kBlock / 2; h > 0; h >>= 1) {
+            if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[(size_t)blockIdx.x * kRenderStats + k] = red[0];
+        __syncthreads();
+    }
+}
+void launch_render_fold(const double* part, int tiles, int F, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_render_fold, dim3(F), dim3(kBlock), 0, s, part, tiles, out);
+}
+
+}  // namespace psg

@@ -25,6 +25,7 @@
 #include <thread>
 #include <cstdint>
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 #include <fstream>
 #include <iostream>
@@ -33,7 +34,9 @@
 #include <vector>
 
 #include "../../include/psgsdf.h"
+#include "../../include/psgsdf_render.h"
 #include "marching_cubes.hpp"
+#include "png_writer.hpp"
 
 namespace psgsdf_host {
 
@@ -559,6 +562,47 @@ public:
     void setPoses(std::vector<Mat4f>& pose) { poses_ = pose; }                                    // Optimizer.h:142-145
     void setKeyframes(std::vector<int>& keyframes) { frame_idx_ = keyframes; }                    // Optimizer.h:147-150
     void setKeytimestamps(std::vector<std::string>& keystamps) { key_stamps_ = keystamps; }      // Optimizer.h:151-154
+
+    // `voxelPS --render-keyframes` (no reference counterpart): every keyframe re-rendered from the final state (include/psgsdf_render.h) as
+    // <prefix>render/<keyframe>_{rendered,albedo,shading,residual}.png and one row per keyframe in <prefix>render_report.txt.  Bytes: values clamped to
+    // [0, 1], then round(255 v); the residual as 0.5 + r.
+    bool renderKeyframes(const std::string& prefix) {
+        if (!ctx_) return false;
+        const int F = (int)num_frames_;
+        std::vector<psgsdf_render_stats> rows(F);
+        if (int rc = psgsdf_render_report(ctx_, rows.data())) return fail("psgsdf_render_report", rc);
+        const std::string dir = prefix + "render/";
+        ::mkdir(dir.c_str(), 0755);
+        std::ofstream rep(prefix + "render_report.txt");
+        rep << "# keyframe hits off_band_hits rmse psnr_db robust_energy  (residual = keyframe - albedo x shading over the hit pixels, RGB in [0, 1])\n";
+        psgsdf_view v0{}; int32_t W = 0, H = 0;
+        if (int rc = psgsdf_render_size(ctx_, &v0, &W, &H)) return fail("psgsdf_render_size", rc);
+        const size_t HW = (size_t)W * H;
+        std::vector<float> planes(10 * HW);
+        std::vector<uint8_t> px(3 * HW);
+        bool ok = rep.is_open();
+        for (int f = 0; f < F; ++f) {
+            const std::string name = f < (int)key_stamps_.size() ? key_stamps_[f] : std::to_string(f);
+            psgsdf_view v{}; v.frame = f;
+            psgsdf_render_stats st{};
+            if (int rc = psgsdf_render(ctx_, &v, PSGSDF_R_ALBEDO | PSGSDF_R_SHADING | PSGSDF_R_RENDERED | PSGSDF_R_RESIDUAL, planes.data(), &st)) return fail("psgsdf_render", rc);
+            // planes in bit order: albedo 3 | shading 1 | rendered 3 | residual 3
+            auto rgb = [&](size_t plane0, float bias, const char* what) {
+                for (size_t i = 0; i < HW; ++i) for (int c = 0; c < 3; ++c) px[3 * i + c] = psgsdf_host::unit_to_u8(bias + planes[(plane0 + c) * HW + i]);
+                ok &= psgsdf_host::write_png(dir + name + "_" + what + ".png", W, H, 3, px.data());
+            };
+            rgb(4, 0.f, "rendered"); rgb(0, 0.f, "albedo"); rgb(7, 0.5f, "residual");
+            for (size_t i = 0; i < HW; ++i) px[i] = psgsdf_host::unit_to_u8(planes[3 * HW + i]);
+            ok &= psgsdf_host::write_png(dir + name + "_shading.png", W, H, 1, px.data());
+            const double r2 = rows[f].sum_r2[0] + rows[f].sum_r2[1] + rows[f].sum_r2[2];
+            const double mse = rows[f].n_hits ? r2 / (3.0 * rows[f].n_hits) : 0.0;
+            char line[256];
+            snprintf(line, sizeof(line), "%s %lld %lld %.6g %.4f %.6g\n", name.c_str(), (long long)rows[f].n_hits, (long long)rows[f].n_hits_off_band, std::sqrt(mse),
+                     mse > 0 ? 10.0 * std::log10(1.0 / mse) : 0.0, rows[f].robust);
+            rep << line;
+        }
+        return ok;
+    }
 
     // PsOptimizer::init / LedOptimizer::init (PsOptimizer.cpp:25-42): with zero keyframes (the constructor-time
     // call of the reference) this is a no-op; with keyframes it creates the device context and uploads everything.

@@ -52,6 +52,13 @@ static int selftest_png(const char* path) {
     unsigned long long sum = 0; for (uint16_t v : p.px) sum += v;
     std::cout << p.width << " " << p.height << " " << p.channels << " " << p.bit_depth << " " << sum << std::endl; return 0;
 }
+// `--selftest-png-write out.png`: a 37 x 23 RGB pattern through the PNG writer (tests/test_render_cpu.py decodes it with PIL)
+static int selftest_png_write(const char* path) {
+    const int W = 37, H = 23;
+    std::vector<uint8_t> px(3 * W * H);
+    for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) { uint8_t* p = &px[3 * (y * W + x)]; p[0] = (uint8_t)(7 * x); p[1] = (uint8_t)(11 * y); p[2] = (uint8_t)(x * y); }
+    return psgsdf_host::write_png(path, W, H, 3, px.data()) ? 0 : 1;
+}
 static int selftest_mc() {
     int dim[3] = {24, 24, 24}; float size[3] = {24, 24, 24}, org[3] = {0, 0, 0};
     MarchingCubes mc(dim, size, org);
@@ -197,15 +204,18 @@ int main(int argc, char* argv[]) {
     if (argc >= 3 && std::string(argv[1]) == "--selftest-lapm") return selftest_lapm(argv[2]);
     if (argc >= 4 && std::string(argv[1]) == "--selftest-sample") return selftest_sample(atoi(argv[2]), atoi(argv[3]));
     if (argc >= 3 && std::string(argv[1]) == "--selftest-png") return selftest_png(argv[2]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-png-write") return selftest_png_write(argv[2]);
     if (argc >= 2 && std::string(argv[1]) == "--selftest-mc") return selftest_mc();
     if (argc >= 2 && std::string(argv[1]) == "--selftest-mc-table") return selftest_mc_table(false);
     if (argc >= 2 && std::string(argv[1]) == "--selftest-mc-generated") return selftest_mc_table(true);
     if (argc >= 4 && std::string(argv[1]) == "--selftest-mc-ply") return selftest_mc_ply(atoi(argv[2]), argv[3]);
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
+    bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
         else if (a == "--host-writers") host_writers() = true;
+        else if (a == "--render-keyframes") render_keyframes = true;
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
@@ -359,6 +369,10 @@ int main(int argc, char* argv[]) {
     vOpt->setImages(key_images); vOpt->setKeyframes(keyframes); vOpt->setKeytimestamps(key_stamps); vOpt->setPoses(key_poses);
     vOpt->init();
     vOpt->alternatingOptimize(light, albedo, distance, pose);
+    if (render_keyframes) {      // (a multi-rank context holds a slab of the volume: not rendered)
+        if (multi_rank()) { if (lead_rank()) std::cerr << "--render-keyframes: single-process runs only" << std::endl; }
+        else if (!vOpt->renderKeyframes(output)) { std::cerr << "--render-keyframes: rendering failed" << std::endl; return 1; }
+    }
     DumpQueue::get().drain();
     const int write_failures = DumpQueue::get().failures();      // (a rank whose piece of a shared output file could not be written: the file has a hole where it belongs)
     if (write_failures) std::cerr << "rank " << rank_info().rank << ": " << write_failures << " output file piece(s) could not be written" << std::endl;
