@@ -15,7 +15,11 @@
  *     and the band albedo (what the energy renders with), outside it the normalised stored gradient and the fused
  *     colour; rendered = albedo x shading (x the LED intensity), residual = keyframe pixel - rendered.
  *
- * Both calls are valid after psgsdf_init on a single-rank context (a multi-rank context: PSGSDF_ERR_UNSUPPORTED).
+ * Both calls are valid after psgsdf_init.  On a context attached to a rank, psgsdf_render and psgsdf_render_report are collective calls:
+ * every rank makes them in the same order with the same arguments (the same view on every rank), and every rank gets the whole planes and stats,
+ * bit for bit what a single-rank context holding the same state returns; each rank traces its own slab, the ranks exchange per-pixel hit masks and
+ * the winners' records through the context's communicator ("Multi-rank contexts").  Ranks that pass different views all get PSGSDF_ERR_ARG.
+ * psgsdf_render_size stays local.
  */
 #ifndef PSGSDF_RENDER_H_
 #define PSGSDF_RENDER_H_

@@ -346,7 +346,7 @@ class Api:
     def render(self, frame=None, pose=None, K=None, size=None, channels=None, light_frame=0):
         """frame: a keyframe view; otherwise a caller's camera: pose (4x4 or 16 camera->world), K (3x3 or [fx, fy, cx, cy]), size (W, H),
         shaded with the light of keyframe light_frame.  channels: R_* bits (default: every plane the view has).  Returns {plane name: array [ch, H, W] (voxel: int32 [H, W], depth / shading: [H, W])}
-        plus "stats" (RenderStats.as_dict)."""
+        plus "stats" (RenderStats.as_dict).  On a context attached to a rank: a collective call (every rank the same view), every rank gets the whole view."""
         v = View()
         if frame is not None:
             v.frame = int(frame)
@@ -379,7 +379,7 @@ class Api:
         return res
 
     def render_report(self):
-        """per keyframe: RenderStats.as_dict of the re-rendering of that keyframe (one batched pass)"""
+        """per keyframe: RenderStats.as_dict of the re-rendering of that keyframe (one batched pass; collective on a context attached to a rank)"""
         F = self.info().n_frames
         arr = (RenderStats * F)()
         self._check(self._fn("render_report")(self.ctx, arr), "render_report")

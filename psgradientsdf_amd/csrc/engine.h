@@ -282,10 +282,13 @@ constexpr int kRenderBrick = 8;      // brick edge (voxels) of the empty-space m
 constexpr int kRenderTile = 8;       // one wavefront per 8 x 8 pixel tile
 constexpr int kRenderStats = 9;      // per-tile partials: hits, off-band hits, sum r^2 [3], sum |r| [3], robust
 enum { RP_DEPTH = 0, RP_NORMAL, RP_ALBEDO, RP_SHADING, RP_RENDERED, RP_RESIDUAL, RP_VOXEL, RP_COUNT };
+// multi-rank: the fields of a hit pixel's record, each carried as its float's bit pattern in a double (exact in a sum with zeros); the residual
+// is recomputed from the keyframe and the rendered colour by the composite, so it never travels
+enum { RF_DEPTH = 0, RF_NORMAL = 1, RF_ALBEDO = 4, RF_SHADING = 7, RF_RENDERED = 8, RF_VOXEL = 11, RF_OFF_BAND = 12, RF_COUNT = 13 };
 struct RenderArgs {
     DenseView d;                     // dense planes, the band written back into them
     const float4* vp[3];             // Band::vp (band rows: nfd and rho at the hit)
-    GridP grid;
+    GridP grid;                      // dim: the WHOLE volume (a slab's dense planes hold the global z-planes from koff on)
     const FrameP* frames;            // current poses and lights
     ImgSrc im; int img_w, img_h;     // keyframe stack
     Robust rob;
@@ -299,11 +302,29 @@ struct RenderArgs {
     int tiles_x, tiles_y;
     float* planes[RP_COUNT];         // [ch][H][W] device planes (nullptr: not asked for)
     double* part;                    // [frames][tiles][kRenderStats] per-workgroup partials
+    // multi-rank only (k_render_ranks, k_render_keep, k_render_composite)
+    int zr[2];                       // the global z-planes this rank owns: [z0, z1)
+    int slab;                        // this rank's place in the z order of the slabs (its bit of the hit mask)
+    int f0;                          // report: first keyframe of the chunk (record frame i = keyframe f0 + i)
+    double* mask;                    // [chunk][H][W] sum of 2^slab over the ranks with a hit on the pixel's ray
+    unsigned char* mine;             // [chunk][H][W] this rank's hit: 0 none, 1 ray going +z (or flat), 2 going -z
+    double* rec;                     // [n_rf][chunk][H][W] hit records (RF_* fields as float bits), zero where this rank is not the winner
+    long long rec_px;                // chunk * H * W
+    int rf[RF_COUNT];                // slot of each field in rec, -1: not carried
+    int n_rf;
 };
-void launch_render_bricks(const DenseView& d, const GridP& g, float thr, unsigned char* bricks, int* bbox, hipStream_t s);   // bbox: 6 ints, pre-filled with 0x7f bytes
+// bricks of the global z-planes [z0, z1) (dense planes read at z - g.koff).  marks == nullptr: bricks + bbox (pre-filled with 0x7f bytes) directly;
+// otherwise 1.0 / 0.0 per brick into marks (every brick written); the map and box then come from the ranks' merged marks (launch_render_box)
+void launch_render_bricks(const DenseView& d, const GridP& g, float thr, int z0, int z1, unsigned char* bricks, int* bbox, double* marks, hipStream_t s);
+void launch_render_box(const double* marks, const int* nb, unsigned char* bricks, int* bbox, hipStream_t s);   // occupied = merged marks > 0
 void launch_render(const RenderArgs& a, int model, hipStream_t s);
 void launch_render_report(const RenderArgs& a, int model, int F, hipStream_t s);
 void launch_render_fold(const double* part, int tiles, int F, double* out /*[F][kRenderStats]*/, hipStream_t s);
+// multi-rank: the records of this rank's hits (report: keyframes f0 .. f0 + chunk - 1); after the mask exchange the non-winners' records zeroed;
+// after the record exchange the planes + per-tile partials from the composited records
+void launch_render_ranks(const RenderArgs& a, int model, bool report, int chunk, hipStream_t s);
+void launch_render_keep(const RenderArgs& a, hipStream_t s);
+void launch_render_composite(const RenderArgs& a, bool report, int chunk, hipStream_t s);
 
 
 }  // namespace psg

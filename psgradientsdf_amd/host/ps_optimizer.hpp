@@ -565,27 +565,33 @@ public:
 
     // `voxelPS --render-keyframes` (no reference counterpart): every keyframe re-rendered from the final state (include/psgsdf_render.h) as
     // <prefix>render/<keyframe>_{rendered,albedo,shading,residual}.png and one row per keyframe in <prefix>render_report.txt.  Bytes: values clamped to
-    // [0, 1], then round(255 v); the residual as 0.5 + r.
+    // [0, 1], then round(255 v); the residual as 0.5 + r.  Multi-rank: the render calls are collective (every rank makes them and gets the whole
+    // views), the lead rank writes the files.
     bool renderKeyframes(const std::string& prefix) {
         if (!ctx_) return false;
         const int F = (int)num_frames_;
+        const bool lead = lead_rank();
         std::vector<psgsdf_render_stats> rows(F);
         if (int rc = psgsdf_render_report(ctx_, rows.data())) return fail("psgsdf_render_report", rc);
         const std::string dir = prefix + "render/";
-        ::mkdir(dir.c_str(), 0755);
-        std::ofstream rep(prefix + "render_report.txt");
-        rep << "# keyframe hits off_band_hits rmse psnr_db robust_energy  (residual = keyframe - albedo x shading over the hit pixels, RGB in [0, 1])\n";
+        std::ofstream rep;
+        if (lead) {
+            ::mkdir(dir.c_str(), 0755);
+            rep.open(prefix + "render_report.txt");
+            rep << "# keyframe hits off_band_hits rmse psnr_db robust_energy  (residual = keyframe - albedo x shading over the hit pixels, RGB in [0, 1])\n";
+        }
         psgsdf_view v0{}; int32_t W = 0, H = 0;
         if (int rc = psgsdf_render_size(ctx_, &v0, &W, &H)) return fail("psgsdf_render_size", rc);
         const size_t HW = (size_t)W * H;
         std::vector<float> planes(10 * HW);
         std::vector<uint8_t> px(3 * HW);
-        bool ok = rep.is_open();
+        bool ok = !lead || rep.is_open();
         for (int f = 0; f < F; ++f) {
             const std::string name = f < (int)key_stamps_.size() ? key_stamps_[f] : std::to_string(f);
             psgsdf_view v{}; v.frame = f;
             psgsdf_render_stats st{};
             if (int rc = psgsdf_render(ctx_, &v, PSGSDF_R_ALBEDO | PSGSDF_R_SHADING | PSGSDF_R_RENDERED | PSGSDF_R_RESIDUAL, planes.data(), &st)) return fail("psgsdf_render", rc);
+            if (!lead) continue;
             // planes in bit order: albedo 3 | shading 1 | rendered 3 | residual 3
             auto rgb = [&](size_t plane0, float bias, const char* what) {
                 for (size_t i = 0; i < HW; ++i) for (int c = 0; c < 3; ++c) px[3 * i + c] = psgsdf_host::unit_to_u8(bias + planes[(plane0 + c) * HW + i]);

@@ -369,10 +369,7 @@ int main(int argc, char* argv[]) {
     vOpt->setImages(key_images); vOpt->setKeyframes(keyframes); vOpt->setKeytimestamps(key_stamps); vOpt->setPoses(key_poses);
     vOpt->init();
     vOpt->alternatingOptimize(light, albedo, distance, pose);
-    if (render_keyframes) {      // (a multi-rank context holds a slab of the volume: not rendered)
-        if (multi_rank()) { if (lead_rank()) std::cerr << "--render-keyframes: single-process runs only" << std::endl; }
-        else if (!vOpt->renderKeyframes(output)) { std::cerr << "--render-keyframes: rendering failed" << std::endl; return 1; }
-    }
+    if (render_keyframes && !vOpt->renderKeyframes(output)) { std::cerr << "--render-keyframes: rendering failed" << std::endl; return 1; }   // (collective on a multi-rank run)
     DumpQueue::get().drain();
     const int write_failures = DumpQueue::get().failures();      // (a rank whose piece of a shared output file could not be written: the file has a hole where it belongs)
     if (write_failures) std::cerr << "rank " << rank_info().rank << ": " << write_failures << " output file piece(s) could not be written" << std::endl;
