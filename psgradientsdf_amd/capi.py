@@ -394,6 +394,17 @@ class Api:
             return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
         return np.ctypeslib.as_array(xyz, shape=(n.value, 3)).copy(), np.ctypeslib.as_array(rgb, shape=(n.value, 3)).copy()
 
+    def extract_mesh_indexed(self):
+        """(xyz [V, 3] float32 grid-local, normals [V, 3] float32, rgb [V, 3] uint8, faces [F, 3] int32, first_vertex): the welded mesh of
+        include/psgsdf_mesh.h.  On a context attached to a rank: a collective call returning this rank's share; face indices are global and
+        first_vertex is the global number of the share's vertex 0."""
+        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)()
+        nv, nf, first = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_indexed")(self.ctx, C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(first)), "extract_mesh_indexed")
+        V, F = nv.value, nf.value
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        return arr(xyz, V, np.float32), arr(nrm, V, np.float32), arr(rgb, V, np.uint8), arr(fc, F, np.int32), first.value
+
     def extract_pointcloud(self, which=0):
         """(xyz_nxyz [n, 6] float32, rgb [n, 3] int32); which = 0: the band voxels, 1: every fused voxel (psgsdf_extract_pointcloud)"""
         pn = C.POINTER(C.c_float)(); col = C.POINTER(C.c_int32)(); n = C.c_int64()

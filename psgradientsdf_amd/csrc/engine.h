@@ -326,5 +326,24 @@ void launch_render_ranks(const RenderArgs& a, int model, bool report, int chunk,
 void launch_render_keep(const RenderArgs& a, hipStream_t s);
 void launch_render_composite(const RenderArgs& a, bool report, int chunk, hipStream_t s);
 
+// ---- welded meshes (mesh.hip, psgsdf_extract_mesh_indexed; DESIGN.md "Welded meshes"): the cells of psgsdf_extract_mesh, one vertex per intersected grid
+// edge.  A vertex lives in a key slot: 4 per voxel of the context's crop planes (+x edge, +y edge, +z edge, corner), the planes it owns and the one above;
+// slot s = 4 * ((kz * d1 + j) * d0 + i) + type with kz = cropped plane - kp0, in ascending key order.
+struct WMeshGrid {
+    const float* dist; const float* weight; const float* g[3]; const float* rho[3];   // dense planes (local plane 0 = global zlo)
+    const float* hg[3]; const float* hrho[3];   // gradient / albedo of global plane zh (the upper neighbour's first plane, exchanged); zh = -1: none
+    int nx, ny, zlo, zh;
+    int lo[3], d[3];             // crop box: first voxel (global) and extent
+    int zc0;                     // first cell plane of this context (cropped) = kp0, the cropped plane of key slot plane 0
+    long long nown;              // key slots of the planes this context owns: [0, nown); [nown, nown + 4 d0 d1) is the plane above
+    float voxel[3], origin[3];   // psgsdf_extract_mesh's vertex frame
+};
+// counts of kept faces per cell (cnt[ncell]) and used-key flags (1) in flag (zeroed first)
+void launch_wmesh_mark(const WMeshGrid& g, long long ncell, int* cnt, int* flag, hipStream_t s);
+void launch_wmesh_or(int* dst, const int* src, long long n, hipStream_t s);      // dst[i] |= src[i]
+// faces: vertex number of slot q = q < nown ? num[q] + first : num_up[q - nown] + first_up (num: exclusive scan of the flags)
+void launch_wmesh_faces(const WMeshGrid& g, long long ncell, const int* offs, int n_faces, const int* num, int first, const int* num_up, int first_up, int* faces, hipStream_t s);
+void launch_wmesh_verts(const WMeshGrid& g, const int* num, int n_verts, float* xyz, float* nrm, unsigned char* rgb, hipStream_t s);
+
 
 }  // namespace psg

@@ -14,17 +14,13 @@
 // numbers) and, for the mesh, the albedo of the upper neighbour's first plane (a cell reaches one plane up; the engine itself only keeps the halo
 // planes' DISTANCES current).
 #include "engine_internal.h"
+#include "mc_common.h"
+#include "../../include/psgsdf_mesh.h"
 
 namespace psg {
 namespace {
 
 #pragma clang fp contract(off)
-
-__constant__ signed char kTri[256][16] = {
-#include "../host/mc_tritable.inc"
-};
-__constant__ int kCornerD[8][3] = {{1, 1, 0}, {1, 0, 0}, {0, 0, 0}, {0, 1, 0}, {1, 1, 1}, {1, 0, 1}, {0, 0, 1}, {0, 1, 1}};      // marching_cubes.hpp kCorner (computeLutIndex :511-556)
-__constant__ int kEdgeD[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}, {0, 4}, {1, 5}, {2, 6}, {3, 7}};
 
 // ---- crop box: min / max voxel index over |d| <= sqrt(3) vs (crop_box, ps_optimizer.hpp; the comparison is the host's: double)
 __global__ void __launch_bounds__(kBlock) k_box_part(const float* __restrict__ dist, int nx, int ny, long long nvox, int k0, double lim, int* __restrict__ part) {
@@ -131,16 +127,6 @@ __device__ __forceinline__ unsigned char colour_at(const McGrid& g, int ch, long
     if (cl >= g.total) return 0;
     const int k = (int)(cl / ((long long)g.d[0] * g.d[1])), rest = (int)(cl - (long long)k * g.d[0] * g.d[1]), j = rest / g.d[0], i = rest - j * g.d[0];
     return (unsigned char)(int)(255 * g.rho[ch][dense_lin(g, i, j, k)]);
-}
-// MarchingCubes.cpp:559-579 (marching_cubes.hpp interpolate)
-__device__ __forceinline__ void mc_interp(float t0, float t1, const float* v0, const float* v1, float* out) {
-    const float iso = 0.0f;
-    if ((double)fabsf(iso - t0) < 1e-7) { for (int a = 0; a < 3; ++a) out[a] = v0[a]; return; }
-    if ((double)fabsf(iso - t1) < 1e-7) { for (int a = 0; a < 3; ++a) out[a] = v1[a]; return; }
-    if ((double)fabsf(t0 - t1) < 1e-7) { for (int a = 0; a < 3; ++a) out[a] = v0[a]; return; }
-    double mu = (double)((iso - t0) / (t1 - t0));
-    if (mu > 1.0) mu = 1.0; else if (mu < 0) mu = 0.0;
-    for (int a = 0; a < 3; ++a) out[a] = (float)((double)v0[a] + mu * (double)(v1[a] - v0[a]));
 }
 // one cell: its triangles (non-degenerate ones, in table order) -> count, or written at `out_v / out_c` (3 vertices per face)
 template <bool EMIT>
@@ -434,3 +420,115 @@ int psgsdf_extract_sdf(psgsdf_ctx* c, int32_t lo[3], int32_t dim[3], const float
 }
 
 }  // extern "C"
+
+// ---- welded, indexed meshes (include/psgsdf_mesh.h; kernels: mesh.hip; DESIGN.md "Welded meshes")
+extern "C" int psgsdf_extract_mesh_indexed(psgsdf_ctx* c, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+                                           const int32_t** faces, int64_t* n_faces, int64_t* first_vertex) {
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !first_vertex) return fail(c, PSGSDF_ERR_ARG, "extract_mesh_indexed: null argument");
+    { int rc = extract_ready(c, "extract_mesh_indexed"); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *n_vertices = 0; *n_faces = 0; *first_vertex = 0;
+    int lo[3], hi[3]; bool any = false;
+    { int rc = crop_box_dev(c, lo, hi, &any); if (rc) return rc; }      // (collective: every rank takes the same early returns below)
+    if (!any) return PSGSDF_OK;
+    psg::WMeshGrid g{};
+    g.dist = c->dense.dist; g.weight = c->dense.weight;
+    for (int a = 0; a < 3; ++a) { g.g[a] = c->dense.g[a]; g.rho[a] = c->dense.rho[a]; }
+    g.nx = c->grid.dim[0]; g.ny = c->grid.dim[1]; g.zlo = c->zlo; g.zh = -1;
+    const float vs = c->grid.vs;
+    for (int a = 0; a < 3; ++a) {      // psgsdf_extract_mesh's frame, operation for operation
+        g.lo[a] = lo[a]; g.d[a] = hi[a] - lo[a] + 1;
+        const float size = vs * g.d[a];
+        g.voxel[a] = size / g.d[a];
+        g.origin[a] = -vs * lo[a];
+    }
+    if (g.d[0] < 3 || g.d[1] < 3 || g.d[2] < 3) return PSGSDF_OK;
+    const long long P = 4ll * g.d[0] * g.d[1];      // key slots per plane
+    if (P * (g.d[2] + 1) >= (1ll << 31)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "extract_mesh_indexed: %lld key slots", P * (g.d[2] + 1));
+    // this context: the cells whose lower plane it owns, the key planes it owns [kp0, kp1) and the one above (the upper neighbour's first plane)
+    g.zc0 = std::max(0, c->z0 - lo[2]);
+    const int zc1 = std::min(g.d[2] - 2, c->z1 - lo[2]), kp1 = std::min(g.d[2], c->z1 - lo[2]);
+    const long long ncell = (long long)(g.d[0] - 2) * (g.d[1] - 2) * std::max(0, zc1 - g.zc0);
+    g.nown = P * std::max(0, kp1 - g.zc0);
+    const bool up = c->rank + 1 < c->n_ranks, down = c->rank > 0;
+    const size_t plane = (size_t)g.nx * g.ny;
+    // temporaries: flags / vertex numbers (4 ints per voxel of the crop planes + one plane), face counts (1 int per cell), scan sums, the exchanged planes
+    const long long nflag = g.nown + P, nscan = std::max(g.nown, ncell);
+    int *flag = nullptr, *cnt = nullptr, *sums = nullptr, *xin = nullptr; float* halo = nullptr;
+    bool ok = hipMalloc(&flag, sizeof(int) * (size_t)nflag) == hipSuccess && hipMalloc(&cnt, sizeof(int) * (size_t)std::max(1ll, ncell)) == hipSuccess
+              && hipMalloc(&sums, sizeof(int) * (size_t)((nscan + psg::kTile - 1) / psg::kTile + 1)) == hipSuccess;
+    if (ok && c->n_ranks > 1) ok = hipMalloc(&xin, sizeof(int) * (size_t)(2 * P)) == hipSuccess && (!up || hipMalloc(&halo, sizeof(float) * 6 * plane) == hipSuccess);
+    auto release = [&] { hipFree(flag); hipFree(cnt); hipFree(sums); hipFree(xin); hipFree(halo); };
+    if (c->n_ranks > 1) {      // every rank learns whether all of them have their temporaries before anyone enters an exchange
+        std::vector<double> st(1, ok ? 0.0 : 1.0);
+        if (int rc = host_allreduce(c, st, "extract_mesh_indexed")) { release(); return rc; }
+        if (st[0] != 0.0) { release(); return fail(c, PSGSDF_ERR_DEVICE, "extract_mesh_indexed: out of memory on %d rank(s)", (int)st[0]); }
+    } else if (!ok) { release(); return fail(c, PSGSDF_ERR_DEVICE, "extract_mesh_indexed: out of memory"); }
+    int rc = 0;
+    if (hipMemsetAsync(flag, 0, sizeof(int) * (size_t)nflag, c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "extract_mesh_indexed: memset");
+    if (!rc && ncell > 0) timed(c, "wmesh_mark", [&] { psg::launch_wmesh_mark(g, ncell, cnt, flag, c->stream); });
+    if (c->n_ranks > 1) {      // (entered even after a local failure: the neighbours wait for it)
+        // the used flags of plane z1 go up and are OR-ed into the owner's first plane; the gradient and albedo of plane z0 go down (z-edges z1 - 1 -> z1)
+        std::vector<psgsdf_comm_xfer> sends, recvs;
+        if (up) {
+            sends.push_back({(void*)(flag + g.nown), sizeof(int) * (size_t)P, c->rank + 1});
+            for (int a = 0; a < 3; ++a) {
+                recvs.push_back({(void*)(halo + plane * a), sizeof(float) * plane, c->rank + 1});
+                recvs.push_back({(void*)(halo + plane * (3 + a)), sizeof(float) * plane, c->rank + 1});
+                g.hg[a] = halo + plane * a; g.hrho[a] = halo + plane * (3 + a);
+            }
+            g.zh = c->z1;
+        }
+        if (down) {
+            recvs.push_back({(void*)xin, sizeof(int) * (size_t)P, c->rank - 1});
+            for (int a = 0; a < 3; ++a) {
+                sends.push_back({(void*)(c->dense.g[a] + plane * (size_t)(c->z0 - c->zlo)), sizeof(float) * plane, c->rank - 1});
+                sends.push_back({(void*)(c->dense.rho[a] + plane * (size_t)(c->z0 - c->zlo)), sizeof(float) * plane, c->rank - 1});
+            }
+        }
+        if (int r2 = comm_xfer(c, sends, recvs)) rc = rc ? rc : r2;
+        if (!rc && down && g.nown > 0) psg::launch_wmesh_or(flag, xin, P, c->stream);
+    }
+    int nv = 0, nf = 0;
+    if (!rc && g.nown > 0) rc = scan_counts(c, flag, g.nown, sums, &nv);      // flags -> vertex numbers (key order)
+    if (!rc && ncell > 0) rc = scan_counts(c, cnt, ncell, sums, &nf);         // face counts -> face offsets
+    // the ranks' vertex counts: this share's first global vertex number, the upper neighbour's
+    long long first = 0, first_up = 0, total_v = nv;
+    if (c->n_ranks > 1) {
+        std::vector<double> all((size_t)c->n_ranks + 1, 0.0);
+        all[(size_t)c->rank] = rc ? 0.0 : (double)nv; all[(size_t)c->n_ranks] = rc ? 1.0 : 0.0;
+        if (int r2 = host_allreduce(c, all, "extract_mesh_indexed")) { release(); return r2; }
+        if (all[(size_t)c->n_ranks] != 0.0 && !rc) rc = fail(c, PSGSDF_ERR_COMM, "extract_mesh_indexed: another rank failed");
+        total_v = 0;
+        for (int r = 0; r < c->n_ranks; ++r) { if (r < c->rank) first += (long long)all[(size_t)r]; if (r == c->rank + 1) first_up = first + nv; total_v += (long long)all[(size_t)r]; }
+    }
+    if (!rc && total_v > INT32_MAX) rc = fail(c, PSGSDF_ERR_UNSUPPORTED, "extract_mesh_indexed: %lld vertices", total_v);
+    if (!rc && c->n_ranks > 1) {      // the vertex numbers of plane z1 come back down from its owner (as its local numbers; + first_up)
+        std::vector<psgsdf_comm_xfer> sends, recvs;
+        if (down) sends.push_back({(void*)flag, sizeof(int) * (size_t)P, c->rank - 1});
+        if (up) recvs.push_back({(void*)(xin + P), sizeof(int) * (size_t)P, c->rank + 1});
+        rc = comm_xfer(c, sends, recvs);
+    }
+    float *d_xyz = nullptr, *d_nrm = nullptr; unsigned char* d_rgb = nullptr; int* d_faces = nullptr;
+    if (!rc && (nv > 0 || nf > 0)) {
+        if ((nv > 0 && (hipMalloc(&d_xyz, sizeof(float) * 3 * (size_t)nv) != hipSuccess || hipMalloc(&d_nrm, sizeof(float) * 3 * (size_t)nv) != hipSuccess || hipMalloc(&d_rgb, 3 * (size_t)nv) != hipSuccess))
+            || (nf > 0 && hipMalloc(&d_faces, sizeof(int) * 3 * (size_t)nf) != hipSuccess)) rc = fail(c, PSGSDF_ERR_DEVICE, "extract_mesh_indexed: out of memory (%d vertices, %d faces)", nv, nf);
+        void *hx = nullptr, *hn = nullptr, *hc = nullptr, *hf = nullptr;
+        if (!rc) rc = host_out(c, 5, sizeof(float) * 3 * (size_t)nv, &hx);
+        if (!rc) rc = host_out(c, 6, sizeof(float) * 3 * (size_t)nv, &hn);
+        if (!rc) rc = host_out(c, 7, 3 * (size_t)nv, &hc);
+        if (!rc) rc = host_out(c, 8, sizeof(int) * 3 * (size_t)nf, &hf);
+        if (!rc) {
+            if (nf > 0) timed(c, "wmesh_faces", [&] { psg::launch_wmesh_faces(g, ncell, cnt, nf, flag, (int)first, xin ? xin + P : nullptr, (int)first_up, d_faces, c->stream); });
+            if (nv > 0) timed(c, "wmesh_verts", [&] { psg::launch_wmesh_verts(g, flag, nv, d_xyz, d_nrm, d_rgb, c->stream); });
+            bool cp = true;
+            if (nv > 0) cp = hipMemcpyAsync(hx, d_xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipMemcpyAsync(hn, d_nrm, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess
+                            && hipMemcpyAsync(hc, d_rgb, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+            if (cp && nf > 0) cp = hipMemcpyAsync(hf, d_faces, sizeof(int) * 3 * (size_t)nf, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+            if (!cp || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "extract_mesh_indexed: download");
+        }
+        if (!rc) { *xyz = (const float*)hx; *normals = (const float*)hn; *rgb = (const uint8_t*)hc; *faces = (const int32_t*)hf; *n_vertices = nv; *n_faces = nf; }
+    }
+    if (!rc) *first_vertex = first;
+    release(); hipFree(d_xyz); hipFree(d_nrm); hipFree(d_rgb); hipFree(d_faces);
+    return rc;
+}

@@ -35,6 +35,7 @@
 
 #include "../../include/psgsdf.h"
 #include "../../include/psgsdf_render.h"
+#include "../../include/psgsdf_mesh.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 
@@ -91,6 +92,7 @@ struct OptimizerSettings {                           // OptimizerSettings.h:24-5
 // its files are tens of MB of that.  Same characters here, from snprintf into per-thread buffers (the lines of a file are formatted in parallel
 // chunks and written in order), on a background thread, so that the optimisation goes on while a dump is being formatted.
 inline bool& host_writers() { static bool v = false; return v; }
+inline bool& indexed_mesh() { static bool v = false; return v; }      // voxelPS --indexed-mesh: a <name>_mesh_indexed.ply (psgsdf_extract_mesh_indexed) next to every <name>_mesh.ply
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
 inline bool& skip_sync_back() { static bool v = false; return v; }      // voxelPS --host-writers: round 4's path (dense download, host marching cubes, iostream): the cross-check
@@ -191,6 +193,35 @@ inline bool write_mesh_ply(const std::string& file, const float* xyz, const uint
     bool ok = fwrite(h.data(), 1, h.size(), f) == h.size();
     ok = ok && write_lines(f, nv, 40, [&](TextOut& o, size_t i) { mesh_vertex_line(o, xyz, rgb, i); });
     ok = ok && write_lines(f, nv / 3, 24, [&](TextOut& o, size_t q) { mesh_face_line(o, q); });
+    return fclose(f) == 0 && ok;
+}
+// the welded mesh (include/psgsdf_mesh.h) as a binary little-endian PLY: vertex records x y z nx ny nz (float) red green blue (uchar), 27 B;
+// face records a uchar 3 and three int vertex indices, 13 B.  Coordinates are grid-local like every other writer's: the comment line holds the
+// grid origin and the voxel size (world = origin + the position).  No reference counterpart: `voxelPS --indexed-mesh`.
+constexpr size_t kPlyVertexBytes = 27, kPlyFaceBytes = 13;
+inline std::string mesh_indexed_header(size_t nv, size_t nf, const float origin[3], float vs) {
+    char c[160];
+    snprintf(c, sizeof c, "comment grid origin %.9g %.9g %.9g voxel size %.9g\n", (double)origin[0], (double)origin[1], (double)origin[2], (double)vs);
+    return std::string("ply\nformat binary_little_endian 1.0\n") + c + "element vertex " + std::to_string(nv) + "\n"
+           "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+           "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+           "element face " + std::to_string(nf) + "\nproperty list uchar int vertex_indices\nend_header\n";
+}
+inline std::string mesh_indexed_vertices(const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv) {
+    std::string b(nv * kPlyVertexBytes, '\0'); char* p = &b[0];      // (the host is little-endian: the records are the arrays' bytes)
+    for (size_t i = 0; i < nv; ++i, p += kPlyVertexBytes) { memcpy(p, xyz + 3 * i, 12); memcpy(p + 12, nrm + 3 * i, 12); memcpy(p + 24, rgb + 3 * i, 3); }
+    return b;
+}
+inline std::string mesh_indexed_faces(const int32_t* faces, size_t nf) {
+    std::string b(nf * kPlyFaceBytes, '\0'); char* p = &b[0];
+    for (size_t q = 0; q < nf; ++q, p += kPlyFaceBytes) { p[0] = 3; memcpy(p + 1, faces + 3 * q, 12); }
+    return b;
+}
+inline bool write_mesh_indexed_ply(const std::string& file, const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv, const int32_t* faces, size_t nf,
+                                   const float origin[3], float vs) {
+    FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
+    const std::string h = mesh_indexed_header(nv, nf, origin, vs), v = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
     return fclose(f) == 0 && ok;
 }
 // save_pointcloud / extract_pc (OptimizerAux.cpp:456-511, VolumetricGradSdf.cpp:320-376): x y z nx ny nz r g b
@@ -368,6 +399,7 @@ struct VolumetricGradSdf {
     }
     bool extract_mesh(const std::string& filename) {
         PSG_STAGE("dump: mesh (marching cubes + PLY)");
+        if (ctx && indexed_mesh() && !device_mesh_indexed(ctx, filename)) std::cout << "couldn't save the indexed mesh of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
     }
@@ -377,6 +409,37 @@ struct VolumetricGradSdf {
         return sync_host() && write_sdf(filename, grid_dim_, voxel_size_, dist);
     }
     // the device-side extraction (include/psgsdf.h psgsdf_extract_*): compact arrays come back, a copy of them goes to the background writer
+    // <name>_mesh.ply -> <name>_mesh_indexed.ply: the welded mesh of the same state (include/psgsdf_mesh.h), binary.  A multi-rank run: every rank
+    // writes its records at their place in the one file, which is byte for byte the single-process file.
+    static bool device_mesh_indexed(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: welded mesh (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string file = (mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                  ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file) + "_mesh_indexed.ply";
+        const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr; int64_t nv = 0, nf = 0, first = 0;
+        const bool ok = psgsdf_extract_mesh_indexed(ctx, &xyz, &nrm, &rgb, &nv, &faces, &nf, &first) == 0;
+        if (!ok) { nv = 0; nf = 0; }
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        if (multi_rank()) {
+            std::vector<double> before, total;
+            if (!scan_over_ranks(ctx, {(double)nv, (double)nf}, before, total, ok) || total[1] == 0) return false;
+            const std::string h = mesh_indexed_header((size_t)total[0], (size_t)total[1], info.origin, info.voxel_size);
+            auto V = std::make_shared<std::vector<TextOut>>(1); (*V)[0].s = mesh_indexed_vertices(xyz, nrm, rgb, (size_t)nv);
+            auto F = std::make_shared<std::vector<TextOut>>(1); (*F)[0].s = mesh_indexed_faces(faces, (size_t)nf);
+            const long long fbase = (long long)(h.size() + kPlyVertexBytes * (size_t)total[0]);
+            write_shared_file(file, h, fbase + (long long)(kPlyFaceBytes * (size_t)total[1]),
+                              {{(long long)(h.size() + kPlyVertexBytes * (size_t)before[0]), V}, {fbase + (long long)(kPlyFaceBytes * (size_t)before[1]), F}});
+            return true;
+        }
+        if (!ok || nf == 0) return false;
+        auto vx = std::make_shared<std::vector<float>>(xyz, xyz + 3 * nv), vn = std::make_shared<std::vector<float>>(nrm, nrm + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(rgb, rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(faces, faces + 3 * nf);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            if (!write_mesh_indexed_ply(file, vx->data(), vn->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs)) { std::cout << "couldn't save mesh " << file << std::endl; DumpQueue::get().report_failure(); }
+        });
+        return true;
+    }
     static bool device_mesh(psgsdf_ctx* ctx, const std::string& file) {
         const float* xyz = nullptr; const uint8_t* rgb = nullptr; int64_t nv = 0;
         const bool ok = psgsdf_extract_mesh(ctx, &xyz, &rgb, &nv) == 0;
@@ -771,6 +834,7 @@ public:
     // extract_mesh / saveSDF, OptimizerAux.cpp:278-363,513-577
     bool extract_mesh(std::string filename) {
         PSG_STAGE("dump: mesh (marching cubes + PLY)");
+        if (indexed_mesh() && !VolumetricGradSdf::device_mesh_indexed(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the indexed mesh " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");
             if (!ok) std::cout << "couldn't save mesh " << save_path_ << filename << std::endl;

@@ -106,6 +106,17 @@ static int selftest_mc_ply(int n, const char* path) {
     return mc.savePly(path) ? 0 : 1;
 }
 
+// `--selftest-ply-indexed out.ply`: a fixed octahedron (6 vertices, 8 outward-wound faces, unit normals) through the binary writer of the welded
+// mesh (tests/test_mesh_indexed_cpu.py parses it back)
+static int selftest_ply_indexed(const char* path) {
+    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
+    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
+    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
+    const float origin[3] = {-0.25f, 0.5f, 1.0f};
+    return psgsdf_host::write_mesh_indexed_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f) ? 0 : 1;
+}
+
 // the focus measure of one colour PNG as the keyframe selector computes it (SharpDetector.h:22-37), and the keyframe sub-sampling of
 // main_ps.cpp:392-421 on the index list 0..n-1: tests/test_host_tools.py compares both with numpy / scipy restatements (no GPU needed)
 static int selftest_lapm(const char* path) {
@@ -209,6 +220,7 @@ int main(int argc, char* argv[]) {
     if (argc >= 2 && std::string(argv[1]) == "--selftest-mc-table") return selftest_mc_table(false);
     if (argc >= 2 && std::string(argv[1]) == "--selftest-mc-generated") return selftest_mc_table(true);
     if (argc >= 4 && std::string(argv[1]) == "--selftest-mc-ply") return selftest_mc_ply(atoi(argv[2]), argv[3]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
@@ -216,6 +228,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
         else if (a == "--host-writers") host_writers() = true;
         else if (a == "--render-keyframes") render_keyframes = true;
+        else if (a == "--indexed-mesh") indexed_mesh() = true;      // a <name>_mesh_indexed.ply (welded, normals, binary; include/psgsdf_mesh.h) next to every <name>_mesh.ply
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];

@@ -1,0 +1,61 @@
+"""Cost of the welded mesh (include/psgsdf_mesh.h) against the non-indexed one (psgsdf_extract_mesh) on the same state, and the sizes of both.
+Wall-clock per call (host clock; both calls end in a stream synchronise) and the kernels' own times from psgsdf_kernel_times:
+    python tools/time_mesh.py sokrates [reps]      the sokrates fixture fused at its poses (128^3 at 4 mm), one iteration
+    python tools/time_mesh.py N [reps]             a synthetic SH1 scene on an N^3 grid
+For the kernel times of record run it under the tracer in a run of its own:
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/time_mesh.py 256
+(kernel names: k_wmesh_mark, k_wmesh_faces, k_wmesh_verts, k_wmesh_or (multi-rank only) against k_mc_count, k_mc_emit; both share k_box_*, k_cscan_*)."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from psgradientsdf_amd import capi, synth  # noqa: E402
+
+what = sys.argv[1] if len(sys.argv) > 1 else "256"
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+if what == "sokrates":
+    from test_render_gpu import _load_multiview
+    K, color, depth, poses = _load_multiview(os.path.join(ROOT, "tests", "golden", "sokrates_small"))
+    F, vs = len(poses), 0.004
+    ys, xs = np.nonzero(depth[0] > 0)
+    z = depth[0][ys, xs].astype(np.float64)
+    pc = np.stack([(xs - K[0, 2]) / K[0, 0] * z, (ys - K[1, 2]) / K[1, 1] * z, z], 1)
+    centre = (pc @ poses[0][:3, :3].T.astype(np.float64) + poses[0][:3, 3]).mean(0)
+    g = capi.GridDesc(); g.dim[:] = [128, 128, 128]; g.voxel_size = vs; g.shift[:] = [float(x) for x in centre]; g.truncation = 5 * vs
+    eng = capi.load_engine(g, K.reshape(-1), capi.default_settings(capi.SH1), 0)
+    eng.volume_init(F)
+    for f in range(F):
+        eng.integrate_frame(color[f], depth[f], eng.estimate_normals(depth[f]), poses[f], f, z_min=0.5, z_max=3.5)
+    eng.set_keyframes(np.arange(F, dtype=np.int32), np.stack(color), np.stack(poses).reshape(F, 16))
+    eng.init()
+else:
+    N = int(what)
+    sc = synth.make_scene(N=N, F=8, W=320, H=240, model="SH1")
+    eng = capi.load_engine(sc, sc.K, capi.default_settings(sc.model_id), 0)
+    eng.load_scene(sc)
+eng.init_albedo()
+eng.iterate(capi.ALL, 1)
+xn, _ = eng.extract_mesh()
+xyz, nrm, rgb, faces, _ = eng.extract_mesh_indexed()                   # (warm-up: code objects, allocations)
+eng.reset_kernel_times()
+eng.set_profiling(True)
+t0 = time.perf_counter()
+for _ in range(reps):
+    eng.extract_mesh()
+t_plain = (time.perf_counter() - t0) / reps
+t0 = time.perf_counter()
+for _ in range(reps):
+    eng.extract_mesh_indexed()
+t_idx = (time.perf_counter() - t0) / reps
+kt = eng.kernel_times()
+eng.set_profiling(False)
+V, Fc = len(xyz), len(faces)
+print(json.dumps({"state": what, "grid": list(eng.info().dim), "extract_mesh_ms": round(1e3 * t_plain, 3), "extract_mesh_indexed_ms": round(1e3 * t_idx, 3),
+                  "kernel_ms_per_launch": {k: round(ms / max(n, 1), 4) for k, (ms, n) in kt.items() if k.startswith(("mc_", "wmesh_"))},
+                  "faces": Fc, "vertices_indexed": V, "vertices_non_indexed": len(xn),
+                  "indexed_ply_body_bytes": 27 * V + 13 * Fc}))
