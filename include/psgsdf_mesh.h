@@ -34,6 +34,35 @@ extern "C" {
 int psgsdf_extract_mesh_indexed(psgsdf_ctx* ctx, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
                                 const int32_t** faces, int64_t* n_faces, int64_t* first_vertex);
 
+/* ---- connected components of that mesh, and the mesh without its small pieces (DESIGN.md "Mesh components"; kernels: csrc/mesh_cc.hip)
+ *
+ * Starts from the welded mesh exactly as psgsdf_extract_mesh_indexed defines it (same cells, keys, vertex numbers, face order).
+ *   - Two vertices are connected iff some kept face uses both; a component is a connected component of that graph.  Every vertex belongs to a face,
+ *     so every component has at least one face.  Pieces that touch only in a shared (snapped-corner) vertex are one component.
+ *   - A component's identity is first_vertex, the smallest vertex number in it (counted in the UNFILTERED mesh); components are listed in ascending
+ *     first_vertex, so the labelling does not depend on thread scheduling.
+ *   - Per component: n_vertices, n_faces, n_edges (distinct undirected edges), n_boundary_edges (used by exactly one face), n_nonmanifold_edges (used
+ *     by more than two), area, the bounding box lo / hi of the float32 positions, kept.  Euler characteristic = n_vertices - n_edges + n_faces;
+ *     closed means n_boundary_edges == 0 && n_nonmanifold_edges == 0.
+ *   - area is defined in fixed point so that it is the same bits on every call: area = vs^2 2^-24 sum over the faces of llrint(2^24 A_f / vs^2),
+ *     A_f the triangle's area computed in double from the returned float32 positions, vs the context's float32 voxel size widened to double.
+ *   - filter: a component passes if n_faces >= min_faces and area >= min_area.  If keep_largest > 0, of those that pass only the keep_largest with
+ *     the most faces are kept; ties go to the smaller first_vertex.  A NULL filter, or all zeros, keeps everything.
+ *   - output: the vertices of the kept components in their original order, renumbered densely; the kept faces in their original order with the new
+ *     numbers; vertex_component[v] for every returned vertex, an index into the component list; the component list with ALL components, dropped ones
+ *     too (kept = 0).  With everything kept, xyz / normals / rgb / faces are bit-equal to psgsdf_extract_mesh_indexed on the same state.  Nothing
+ *     kept: 0 vertices, 0 faces, the list still filled.  An empty mesh: 0 components.
+ * The arrays are engine-owned pinned host memory, valid until the next extraction call on the context.  PSGSDF_ERR_STATE before a volume exists;
+ * PSGSDF_ERR_ARG for a NaN min_area or a negative keep_largest; PSGSDF_ERR_DEVICE if a temporary cannot be allocated.  On a context attached to a
+ * rank the call returns PSGSDF_ERR_UNSUPPORTED on every rank before any exchange (components across z-slabs are not merged yet). */
+typedef struct psgsdf_mesh_filter { int64_t min_faces; double min_area; int32_t keep_largest; } psgsdf_mesh_filter;
+typedef struct psgsdf_mesh_component { int64_t first_vertex, n_vertices, n_faces, n_edges, n_boundary_edges,
+    n_nonmanifold_edges; double area; float lo[3], hi[3]; int32_t kept, reserved; } psgsdf_mesh_component;
+int psgsdf_extract_mesh_components(psgsdf_ctx* ctx, const psgsdf_mesh_filter* filter,
+    const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+    const int32_t** faces, int64_t* n_faces, const int32_t** vertex_component,
+    const psgsdf_mesh_component** components, int64_t* n_components);
+
 #ifdef __cplusplus
 }
 #endif

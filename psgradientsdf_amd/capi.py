@@ -74,6 +74,15 @@ class View(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("light_frame", C.c_int32)]
 
 
+class MeshFilter(C.Structure):      # psgsdf_mesh_filter (include/psgsdf_mesh.h)
+    _fields_ = [("min_faces", C.c_int64), ("min_area", C.c_double), ("keep_largest", C.c_int32)]
+
+
+# psgsdf_mesh_component (include/psgsdf_mesh.h), 88 bytes
+MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_faces", "<i8"), ("n_edges", "<i8"), ("n_boundary_edges", "<i8"),
+                                 ("n_nonmanifold_edges", "<i8"), ("area", "<f8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("kept", "<i4"), ("reserved", "<i4")])
+
+
 class RenderStats(C.Structure):
     _fields_ = [("n_pixels", C.c_int64), ("n_hits", C.c_int64), ("n_hits_off_band", C.c_int64),
                 ("sum_r2", C.c_double * 3), ("sum_abs_r", C.c_double * 3), ("robust", C.c_double)]
@@ -404,6 +413,22 @@ class Api:
         V, F = nv.value, nf.value
         arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
         return arr(xyz, V, np.float32), arr(nrm, V, np.float32), arr(rgb, V, np.uint8), arr(fc, F, np.int32), first.value
+
+    def extract_mesh_components(self, min_faces=0, min_area=0.0, keep_largest=0):
+        """The welded mesh without the components the filter drops, and the table of ALL its components (include/psgsdf_mesh.h
+        psgsdf_extract_mesh_components): dict of xyz [V, 3] float32, normals [V, 3] float32, rgb [V, 3] uint8, faces [F, 3] int32 (renumbered),
+        vertex_component [V] int32 (index into components), components (structured array, MESH_COMPONENT_DTYPE).  A component passes if
+        n_faces >= min_faces and area >= min_area; keep_largest > 0 keeps only that many of them, those with the most faces.  Single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest))
+        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)(); vc = C.POINTER(C.c_int32)()
+        comps = C.c_void_p(); nv, nf, nc = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_components")(self.ctx, C.byref(flt), C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf),
+                                                        C.byref(vc), C.byref(comps), C.byref(nc)), "extract_mesh_components")
+        V, F, K = nv.value, nf.value, nc.value
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        table = np.frombuffer(C.string_at(comps, K * MESH_COMPONENT_DTYPE.itemsize), MESH_COMPONENT_DTYPE).copy() if K else np.zeros(0, MESH_COMPONENT_DTYPE)
+        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
+                    vertex_component=np.ctypeslib.as_array(vc, shape=(V,)).copy() if V else np.zeros(0, np.int32), components=table)
 
     def extract_pointcloud(self, which=0):
         """(xyz_nxyz [n, 6] float32, rgb [n, 3] int32); which = 0: the band voxels, 1: every fused voxel (psgsdf_extract_pointcloud)"""

@@ -345,5 +345,22 @@ void launch_wmesh_or(int* dst, const int* src, long long n, hipStream_t s);     
 void launch_wmesh_faces(const WMeshGrid& g, long long ncell, const int* offs, int n_faces, const int* num, int first, const int* num_up, int first_up, int* faces, hipStream_t s);
 void launch_wmesh_verts(const WMeshGrid& g, const int* num, int n_verts, float* xyz, float* nrm, unsigned char* rgb, hipStream_t s);
 
+// ---- connected components of the welded mesh (mesh_cc.hip, psgsdf_extract_mesh_components; DESIGN.md "Mesh components").  Per component kMcompStats
+// 64-bit integers (stat[comp][MC_*], zeroed first; MC_AREA: the sum of llrint(2^24 A_f / vs^2)) and the bounding box as order-preserving unsigned
+// images of the floats (blo[comp][3] pre-filled with 0xff bytes, bhi[comp][3] with zeros).
+enum { MC_FIRST = 0, MC_VERTS, MC_FACES, MC_EDGES, MC_BOUNDARY, MC_NONMANIFOLD, MC_AREA, kMcompStats = 8 };
+void launch_mcomp_init(int* parent, int nv, hipStream_t s);
+void launch_mcomp_hook(const int* faces, int nf, int* parent, hipStream_t s);                  // afterwards the root of every tree is its component's smallest vertex
+void launch_mcomp_flatten(int* parent, int nv, int* flag, hipStream_t s);                     // parent[v] = root(v), flag[v] = (root(v) == v)
+// num: the exclusive scan of the root flags (component numbers in ascending first vertex); vcomp[v] = the component of v
+void launch_mcomp_vstats(const int* parent, const int* num, int nv, const float* xyz, int* vcomp, long long* stat, unsigned* blo, unsigned* bhi, hipStream_t s);
+void launch_mcomp_fstats(const int* faces, int nf, const int* vcomp, const float* xyz, double vs2 /* vs^2 */, long long* stat, hipStream_t s);
+// edge table: cap >= 6 n_faces slots, keys pre-filled with 0xff bytes, uses with zeros
+void launch_mcomp_edges(const int* faces, int nf, unsigned long long* keys, int* uses, unsigned long long cap, hipStream_t s);
+void launch_mcomp_ecount(const unsigned long long* keys, const int* uses, unsigned long long cap, const int* vcomp, long long* stat, hipStream_t s);
+void launch_mcomp_keep(const int* kept, const int* vcomp, int nv, const int* faces, int nf, int* vflag, int* fflag, hipStream_t s);
+void launch_mcomp_compact(const int* kept, const int* vcomp, int nv, const int* faces, int nf, const int* vnum, const int* fnum, const float* xyz, const float* nrm,
+                          const unsigned char* rgb, float* oxyz, float* onrm, unsigned char* orgb, int* ovcomp, int* ofaces, hipStream_t s);
+
 
 }  // namespace psg

@@ -422,11 +422,16 @@ int psgsdf_extract_sdf(psgsdf_ctx* c, int32_t lo[3], int32_t dim[3], const float
 }  // extern "C"
 
 // ---- welded, indexed meshes (include/psgsdf_mesh.h; kernels: mesh.hip; DESIGN.md "Welded meshes")
-extern "C" int psgsdf_extract_mesh_indexed(psgsdf_ctx* c, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
-                                           const int32_t** faces, int64_t* n_faces, int64_t* first_vertex) {
-    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !first_vertex) return fail(c, PSGSDF_ERR_ARG, "extract_mesh_indexed: null argument");
-    { int rc = extract_ready(c, "extract_mesh_indexed"); if (rc) return rc; }
-    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *n_vertices = 0; *n_faces = 0; *first_vertex = 0;
+namespace {
+// the welded mesh of the context's state as device arrays (this rank's share), the kernels launched on the stream and not waited for: what
+// psgsdf_extract_mesh_indexed downloads and psgsdf_extract_mesh_components goes on from.  nv == 0 && nf == 0: nothing was allocated.
+struct WMeshDev {
+    float *xyz = nullptr, *nrm = nullptr; unsigned char* rgb = nullptr; int* faces = nullptr;
+    int nv = 0, nf = 0; long long first = 0;
+    void* tmp[5] = {};      // the extraction's temporaries, freed with the arrays once the stream has been waited for
+    void release() { for (void*& t : tmp) { hipFree(t); t = nullptr; } hipFree(xyz); hipFree(nrm); hipFree(rgb); hipFree(faces); xyz = nrm = nullptr; rgb = nullptr; faces = nullptr; }
+};
+int wmesh_device(psgsdf_ctx* c, WMeshDev* m) {
     int lo[3], hi[3]; bool any = false;
     { int rc = crop_box_dev(c, lo, hi, &any); if (rc) return rc; }      // (collective: every rank takes the same early returns below)
     if (!any) return PSGSDF_OK;
@@ -512,14 +517,35 @@ extern "C" int psgsdf_extract_mesh_indexed(psgsdf_ctx* c, const float** xyz, con
     if (!rc && (nv > 0 || nf > 0)) {
         if ((nv > 0 && (hipMalloc(&d_xyz, sizeof(float) * 3 * (size_t)nv) != hipSuccess || hipMalloc(&d_nrm, sizeof(float) * 3 * (size_t)nv) != hipSuccess || hipMalloc(&d_rgb, 3 * (size_t)nv) != hipSuccess))
             || (nf > 0 && hipMalloc(&d_faces, sizeof(int) * 3 * (size_t)nf) != hipSuccess)) rc = fail(c, PSGSDF_ERR_DEVICE, "extract_mesh_indexed: out of memory (%d vertices, %d faces)", nv, nf);
+        if (!rc) {
+            if (nf > 0) timed(c, "wmesh_faces", [&] { psg::launch_wmesh_faces(g, ncell, cnt, nf, flag, (int)first, xin ? xin + P : nullptr, (int)first_up, d_faces, c->stream); });
+            if (nv > 0) timed(c, "wmesh_verts", [&] { psg::launch_wmesh_verts(g, flag, nv, d_xyz, d_nrm, d_rgb, c->stream); });
+        }
+    }
+    if (rc) { release(); hipFree(d_xyz); hipFree(d_nrm); hipFree(d_rgb); hipFree(d_faces); return rc; }
+    m->xyz = d_xyz; m->nrm = d_nrm; m->rgb = d_rgb; m->faces = d_faces; m->nv = nv; m->nf = nf; m->first = first;
+    m->tmp[0] = flag; m->tmp[1] = cnt; m->tmp[2] = sums; m->tmp[3] = xin; m->tmp[4] = halo;      // (the kernels in flight read them)
+    return PSGSDF_OK;
+}
+}  // namespace
+
+extern "C" int psgsdf_extract_mesh_indexed(psgsdf_ctx* c, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+                                           const int32_t** faces, int64_t* n_faces, int64_t* first_vertex) {
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !first_vertex) return fail(c, PSGSDF_ERR_ARG, "extract_mesh_indexed: null argument");
+    { int rc = extract_ready(c, "extract_mesh_indexed"); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *n_vertices = 0; *n_faces = 0; *first_vertex = 0;
+    WMeshDev m;
+    int rc = wmesh_device(c, &m);
+    if (rc) return rc;
+    const int nv = m.nv, nf = m.nf;
+    float *d_xyz = m.xyz, *d_nrm = m.nrm; unsigned char* d_rgb = m.rgb; int* d_faces = m.faces;
+    if (nv > 0 || nf > 0) {
         void *hx = nullptr, *hn = nullptr, *hc = nullptr, *hf = nullptr;
         if (!rc) rc = host_out(c, 5, sizeof(float) * 3 * (size_t)nv, &hx);
         if (!rc) rc = host_out(c, 6, sizeof(float) * 3 * (size_t)nv, &hn);
         if (!rc) rc = host_out(c, 7, 3 * (size_t)nv, &hc);
         if (!rc) rc = host_out(c, 8, sizeof(int) * 3 * (size_t)nf, &hf);
         if (!rc) {
-            if (nf > 0) timed(c, "wmesh_faces", [&] { psg::launch_wmesh_faces(g, ncell, cnt, nf, flag, (int)first, xin ? xin + P : nullptr, (int)first_up, d_faces, c->stream); });
-            if (nv > 0) timed(c, "wmesh_verts", [&] { psg::launch_wmesh_verts(g, flag, nv, d_xyz, d_nrm, d_rgb, c->stream); });
             bool cp = true;
             if (nv > 0) cp = hipMemcpyAsync(hx, d_xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipMemcpyAsync(hn, d_nrm, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess
                             && hipMemcpyAsync(hc, d_rgb, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
@@ -528,7 +554,122 @@ extern "C" int psgsdf_extract_mesh_indexed(psgsdf_ctx* c, const float** xyz, con
         }
         if (!rc) { *xyz = (const float*)hx; *normals = (const float*)hn; *rgb = (const uint8_t*)hc; *faces = (const int32_t*)hf; *n_vertices = nv; *n_faces = nf; }
     }
-    if (!rc) *first_vertex = first;
-    release(); hipFree(d_xyz); hipFree(d_nrm); hipFree(d_rgb); hipFree(d_faces);
+    if (!rc) *first_vertex = m.first;
+    m.release();
+    return rc;
+}
+
+// ---- connected components of the welded mesh, and the mesh without its small pieces (include/psgsdf_mesh.h; kernels: mesh_cc.hip; DESIGN.md "Mesh components")
+extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+                                              const int32_t** faces, int64_t* n_faces, const int32_t** vertex_component, const psgsdf_mesh_component** components, int64_t* n_components) {
+    const char* me = "extract_mesh_components";
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_component || !components || !n_components) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    // (before anything collective: no rank waits for another)
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): components are not merged across z-slabs yet", me, c->rank, c->n_ranks);
+    psgsdf_mesh_filter flt{0, 0.0, 0};
+    if (filter) flt = *filter;
+    if (flt.min_area != flt.min_area || flt.keep_largest < 0) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_component = nullptr; *components = nullptr; *n_vertices = 0; *n_faces = 0; *n_components = 0;
+    WMeshDev m;
+    int rc = wmesh_device(c, &m);
+    if (rc) return rc;
+    const int nv = m.nv, nf = m.nf;
+    if (nv == 0 || nf == 0) { if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: kernels", me); m.release(); return rc; }      // (every vertex belongs to a face: both or neither)
+    // temporaries: 3 ints per vertex (parent, root flag / component number, component of the vertex), the edge table (6 slots of 12 B per face),
+    // per component 8 x 8 B of counters and 6 x 4 B of box, the scan's sums; with a filter 1 int per vertex and face and the compacted arrays
+    const unsigned long long cap = std::max<unsigned long long>(64, 6ull * (unsigned long long)nf);
+    const long long nscan = std::max(nv, nf);
+    int *parent = nullptr, *num = nullptr, *vcomp = nullptr, *uses = nullptr, *sums = nullptr, *d_kept = nullptr, *vflag = nullptr, *fflag = nullptr, *o_vcomp = nullptr, *o_faces = nullptr;
+    unsigned long long* keys = nullptr; long long* stat = nullptr; unsigned* box = nullptr;
+    float *o_xyz = nullptr, *o_nrm = nullptr; unsigned char* o_rgb = nullptr;
+    auto release = [&] {
+        hipFree(parent); hipFree(num); hipFree(vcomp); hipFree(uses); hipFree(sums); hipFree(d_kept); hipFree(vflag); hipFree(fflag); hipFree(o_vcomp); hipFree(o_faces);
+        hipFree(keys); hipFree(stat); hipFree(box); hipFree(o_xyz); hipFree(o_nrm); hipFree(o_rgb); m.release();
+    };
+    auto oom = [&] { hipStreamSynchronize(c->stream); release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d vertices, %d faces)", me, nv, nf); };
+    if (hipMalloc(&parent, sizeof(int) * (size_t)nv) != hipSuccess || hipMalloc(&num, sizeof(int) * (size_t)nv) != hipSuccess || hipMalloc(&vcomp, sizeof(int) * (size_t)nv) != hipSuccess
+        || hipMalloc(&keys, sizeof(unsigned long long) * (size_t)cap) != hipSuccess || hipMalloc(&uses, sizeof(int) * (size_t)cap) != hipSuccess
+        || hipMalloc(&sums, sizeof(int) * (size_t)((nscan + psg::kTile - 1) / psg::kTile + 1)) != hipSuccess) return oom();
+    bool ok = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)cap, c->stream) == hipSuccess && hipMemsetAsync(uses, 0, sizeof(int) * (size_t)cap, c->stream) == hipSuccess;
+    if (!ok) { hipStreamSynchronize(c->stream); release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me); }
+    timed(c, "mcomp_init", [&] { psg::launch_mcomp_init(parent, nv, c->stream); });
+    timed(c, "mcomp_hook", [&] { psg::launch_mcomp_hook(m.faces, nf, parent, c->stream); });
+    timed(c, "mcomp_flatten", [&] { psg::launch_mcomp_flatten(parent, nv, num, c->stream); });
+    timed(c, "mcomp_edges", [&] { psg::launch_mcomp_edges(m.faces, nf, keys, uses, cap, c->stream); });
+    int nc = 0;
+    rc = scan_counts(c, num, nv, sums, &nc);      // root flags -> component numbers in ascending first vertex
+    if (rc) { hipStreamSynchronize(c->stream); release(); return rc; }
+    if (hipMalloc(&stat, sizeof(long long) * psg::kMcompStats * (size_t)nc) != hipSuccess || hipMalloc(&box, sizeof(unsigned) * 6 * (size_t)nc) != hipSuccess) return oom();
+    unsigned *blo = box, *bhi = box + 3 * (size_t)nc;
+    ok = hipMemsetAsync(stat, 0, sizeof(long long) * psg::kMcompStats * (size_t)nc, c->stream) == hipSuccess && hipMemsetAsync(blo, 0xff, sizeof(unsigned) * 3 * (size_t)nc, c->stream) == hipSuccess
+         && hipMemsetAsync(bhi, 0, sizeof(unsigned) * 3 * (size_t)nc, c->stream) == hipSuccess;
+    if (!ok) { hipStreamSynchronize(c->stream); release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me); }
+    const double vs = (double)c->grid.vs, unit = vs * vs / 16777216.0;      // one unit of the fixed-point area
+    timed(c, "mcomp_vstats", [&] { psg::launch_mcomp_vstats(parent, num, nv, m.xyz, vcomp, stat, blo, bhi, c->stream); });
+    timed(c, "mcomp_fstats", [&] { psg::launch_mcomp_fstats(m.faces, nf, vcomp, m.xyz, vs * vs, stat, c->stream); });
+    timed(c, "mcomp_ecount", [&] { psg::launch_mcomp_ecount(keys, uses, cap, vcomp, stat, c->stream); });
+    std::vector<long long> hstat((size_t)psg::kMcompStats * nc); std::vector<unsigned> hbox((size_t)6 * nc);
+    if (hipMemcpyAsync(hstat.data(), stat, sizeof(long long) * hstat.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess
+        || hipMemcpyAsync(hbox.data(), box, sizeof(unsigned) * hbox.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the component table", me);
+    }
+    void *hx = nullptr, *hn = nullptr, *hc = nullptr, *hf = nullptr, *hv = nullptr, *hl = nullptr;
+    rc = host_out(c, 10, sizeof(psgsdf_mesh_component) * (size_t)nc, &hl);
+    if (rc) { release(); return rc; }
+    psgsdf_mesh_component* list = (psgsdf_mesh_component*)hl;
+    auto unordered = [](unsigned u) { u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; memcpy(&f, &u, 4); return f; };
+    for (int i = 0; i < nc; ++i) {
+        const long long* s = hstat.data() + (size_t)psg::kMcompStats * i;
+        psgsdf_mesh_component& k = list[i];
+        k.first_vertex = s[psg::MC_FIRST]; k.n_vertices = s[psg::MC_VERTS]; k.n_faces = s[psg::MC_FACES]; k.n_edges = s[psg::MC_EDGES];
+        k.n_boundary_edges = s[psg::MC_BOUNDARY]; k.n_nonmanifold_edges = s[psg::MC_NONMANIFOLD];
+        k.area = unit * (double)s[psg::MC_AREA];
+        for (int a = 0; a < 3; ++a) { k.lo[a] = unordered(hbox[(size_t)3 * i + a]); k.hi[a] = unordered(hbox[(size_t)3 * (nc + i) + a]); }
+        k.kept = (k.n_faces >= flt.min_faces && k.area >= flt.min_area) ? 1 : 0; k.reserved = 0;
+    }
+    if (flt.keep_largest > 0) {      // of those that pass: the keep_largest with the most faces, ties to the smaller first vertex (= the smaller index)
+        std::vector<int> pass;
+        for (int i = 0; i < nc; ++i) if (list[i].kept) pass.push_back(i);
+        std::stable_sort(pass.begin(), pass.end(), [&](int a, int b) { return list[a].n_faces > list[b].n_faces; });
+        for (size_t q = (size_t)flt.keep_largest; q < pass.size(); ++q) list[pass[q]].kept = 0;
+    }
+    int n_kept = 0;
+    for (int i = 0; i < nc; ++i) n_kept += list[i].kept;
+    int ov = nv, of = nf;
+    const float *r_xyz = m.xyz, *r_nrm = m.nrm; const unsigned char* r_rgb = m.rgb; const int *r_faces = m.faces, *r_vcomp = vcomp;
+    if (n_kept < nc) {      // compaction (everything kept: the arrays as they are)
+        std::vector<int> hk((size_t)nc);
+        for (int i = 0; i < nc; ++i) hk[(size_t)i] = list[i].kept;
+        if (hipMalloc(&d_kept, sizeof(int) * (size_t)nc) != hipSuccess || hipMalloc(&vflag, sizeof(int) * (size_t)nv) != hipSuccess || hipMalloc(&fflag, sizeof(int) * (size_t)nf) != hipSuccess) return oom();
+        if (hipMemcpyAsync(d_kept, hk.data(), sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, c->stream) != hipSuccess) { hipStreamSynchronize(c->stream); release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: upload", me); }
+        timed(c, "mcomp_keep", [&] { psg::launch_mcomp_keep(d_kept, vcomp, nv, m.faces, nf, vflag, fflag, c->stream); });
+        rc = scan_counts(c, vflag, nv, sums, &ov);      // (waits for the stream: hk stays alive until here)
+        if (!rc) rc = scan_counts(c, fflag, nf, sums, &of);
+        if (rc) { hipStreamSynchronize(c->stream); release(); return rc; }
+        if (ov > 0 && of > 0) {
+            if (hipMalloc(&o_xyz, sizeof(float) * 3 * (size_t)ov) != hipSuccess || hipMalloc(&o_nrm, sizeof(float) * 3 * (size_t)ov) != hipSuccess || hipMalloc(&o_rgb, 3 * (size_t)ov) != hipSuccess
+                || hipMalloc(&o_vcomp, sizeof(int) * (size_t)ov) != hipSuccess || hipMalloc(&o_faces, sizeof(int) * 3 * (size_t)of) != hipSuccess) return oom();
+            timed(c, "mcomp_compact", [&] { psg::launch_mcomp_compact(d_kept, vcomp, nv, m.faces, nf, vflag, fflag, m.xyz, m.nrm, m.rgb, o_xyz, o_nrm, o_rgb, o_vcomp, o_faces, c->stream); });
+        }
+        r_xyz = o_xyz; r_nrm = o_nrm; r_rgb = o_rgb; r_faces = o_faces; r_vcomp = o_vcomp;
+    }
+    if (ov > 0 && of > 0) {
+        rc = host_out(c, 5, sizeof(float) * 3 * (size_t)ov, &hx);
+        if (!rc) rc = host_out(c, 6, sizeof(float) * 3 * (size_t)ov, &hn);
+        if (!rc) rc = host_out(c, 7, 3 * (size_t)ov, &hc);
+        if (!rc) rc = host_out(c, 8, sizeof(int) * 3 * (size_t)of, &hf);
+        if (!rc) rc = host_out(c, 9, sizeof(int) * (size_t)ov, &hv);
+        if (!rc) {
+            const bool cp = hipMemcpyAsync(hx, r_xyz, sizeof(float) * 3 * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipMemcpyAsync(hn, r_nrm, sizeof(float) * 3 * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess
+                            && hipMemcpyAsync(hc, r_rgb, 3 * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipMemcpyAsync(hf, r_faces, sizeof(int) * 3 * (size_t)of, hipMemcpyDeviceToHost, c->stream) == hipSuccess
+                            && hipMemcpyAsync(hv, r_vcomp, sizeof(int) * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+            if (!cp || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: download", me);
+        }
+        if (!rc) { *xyz = (const float*)hx; *normals = (const float*)hn; *rgb = (const uint8_t*)hc; *faces = (const int32_t*)hf; *vertex_component = (const int32_t*)hv; *n_vertices = ov; *n_faces = of; }
+    }
+    if (!rc) { *components = list; *n_components = nc; }
+    hipStreamSynchronize(c->stream);
+    release();
     return rc;
 }

@@ -93,6 +93,10 @@ struct OptimizerSettings {                           // OptimizerSettings.h:24-5
 // chunks and written in order), on a background thread, so that the optimisation goes on while a dump is being formatted.
 inline bool& host_writers() { static bool v = false; return v; }
 inline bool& indexed_mesh() { static bool v = false; return v; }      // voxelPS --indexed-mesh: a <name>_mesh_indexed.ply (psgsdf_extract_mesh_indexed) next to every <name>_mesh.ply
+// voxelPS --mesh-min-faces N / --mesh-keep-largest K: next to every <name>_mesh.ply a <name>_mesh_clean.ply (the welded mesh without the connected components
+// the filter drops, psgsdf_extract_mesh_components) and a <name>_mesh_components.txt (every component, one per line); single process only
+inline bool& clean_mesh() { static bool v = false; return v; }
+inline psgsdf_mesh_filter& mesh_filter() { static psgsdf_mesh_filter f{0, 0.0, 0}; return f; }
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
 inline bool& skip_sync_back() { static bool v = false; return v; }      // voxelPS --host-writers: round 4's path (dense download, host marching cubes, iostream): the cross-check
@@ -199,10 +203,10 @@ inline bool write_mesh_ply(const std::string& file, const float* xyz, const uint
 // face records a uchar 3 and three int vertex indices, 13 B.  Coordinates are grid-local like every other writer's: the comment line holds the
 // grid origin and the voxel size (world = origin + the position).  No reference counterpart: `voxelPS --indexed-mesh`.
 constexpr size_t kPlyVertexBytes = 27, kPlyFaceBytes = 13;
-inline std::string mesh_indexed_header(size_t nv, size_t nf, const float origin[3], float vs) {
+inline std::string mesh_indexed_header(size_t nv, size_t nf, const float origin[3], float vs, const std::string& extra = std::string()) {      // extra: further header lines (each ends in \n)
     char c[160];
     snprintf(c, sizeof c, "comment grid origin %.9g %.9g %.9g voxel size %.9g\n", (double)origin[0], (double)origin[1], (double)origin[2], (double)vs);
-    return std::string("ply\nformat binary_little_endian 1.0\n") + c + "element vertex " + std::to_string(nv) + "\n"
+    return std::string("ply\nformat binary_little_endian 1.0\n") + c + extra + "element vertex " + std::to_string(nv) + "\n"
            "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
            "element face " + std::to_string(nf) + "\nproperty list uchar int vertex_indices\nend_header\n";
@@ -218,9 +222,9 @@ inline std::string mesh_indexed_faces(const int32_t* faces, size_t nf) {
     return b;
 }
 inline bool write_mesh_indexed_ply(const std::string& file, const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv, const int32_t* faces, size_t nf,
-                                   const float origin[3], float vs) {
+                                   const float origin[3], float vs, const std::string& extra = std::string()) {
     FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
-    const std::string h = mesh_indexed_header(nv, nf, origin, vs), v = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    const std::string h = mesh_indexed_header(nv, nf, origin, vs, extra), v = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
     bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
     return fclose(f) == 0 && ok;
 }
@@ -400,6 +404,7 @@ struct VolumetricGradSdf {
     bool extract_mesh(const std::string& filename) {
         PSG_STAGE("dump: mesh (marching cubes + PLY)");
         if (ctx && indexed_mesh() && !device_mesh_indexed(ctx, filename)) std::cout << "couldn't save the indexed mesh of " << filename << std::endl;
+        if (ctx && clean_mesh() && !device_mesh_clean(ctx, filename)) std::cout << "couldn't save the cleaned mesh of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
     }
@@ -437,6 +442,39 @@ struct VolumetricGradSdf {
         const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
         DumpQueue::get().push([=] {
             if (!write_mesh_indexed_ply(file, vx->data(), vn->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs)) { std::cout << "couldn't save mesh " << file << std::endl; DumpQueue::get().report_failure(); }
+        });
+        return true;
+    }
+    // <name>_mesh.ply -> <name>_mesh_clean.ply (the binary format of _mesh_indexed.ply and one more comment line) + <name>_mesh_components.txt:
+    // first_vertex n_vertices n_faces n_edges n_boundary_edges n_nonmanifold_edges area lo[3] hi[3] kept, one component per line
+    static bool device_mesh_clean(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: mesh components (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string base = mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                 ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file;
+        const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr; const int32_t* vcomp = nullptr;
+        const psgsdf_mesh_component* comps = nullptr; int64_t nv = 0, nf = 0, nc = 0;
+        if (psgsdf_extract_mesh_components(ctx, &mesh_filter(), &xyz, &nrm, &rgb, &nv, &faces, &nf, &vcomp, &comps, &nc) != 0 || nc == 0) return false;
+        std::string table; int64_t kept = 0;
+        for (int64_t i = 0; i < nc; ++i) {
+            const psgsdf_mesh_component& k = comps[i];
+            char line[400];
+            snprintf(line, sizeof line, "%lld %lld %lld %lld %lld %lld %.17g %.9g %.9g %.9g %.9g %.9g %.9g %d\n", (long long)k.first_vertex, (long long)k.n_vertices, (long long)k.n_faces,
+                     (long long)k.n_edges, (long long)k.n_boundary_edges, (long long)k.n_nonmanifold_edges, k.area, (double)k.lo[0], (double)k.lo[1], (double)k.lo[2],
+                     (double)k.hi[0], (double)k.hi[1], (double)k.hi[2], (int)k.kept);
+            table += line; kept += k.kept;
+        }
+        const std::string extra = "comment components kept " + std::to_string(kept) + " of " + std::to_string(nc) + "\n";
+        auto vx = std::make_shared<std::vector<float>>(xyz, xyz + 3 * nv), vn = std::make_shared<std::vector<float>>(nrm, nrm + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(rgb, rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(faces, faces + 3 * nf);
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            bool ok = write_mesh_indexed_ply(base + "_mesh_clean.ply", vx->data(), vn->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, extra);
+            FILE* f = fopen((base + "_mesh_components.txt").c_str(), "wb");
+            ok = f && fwrite(table.data(), 1, table.size(), f) == table.size() && ok;
+            if (f && fclose(f) != 0) ok = false;
+            if (!ok) { std::cout << "couldn't save the cleaned mesh " << base << std::endl; DumpQueue::get().report_failure(); }
         });
         return true;
     }
@@ -835,6 +873,7 @@ public:
     bool extract_mesh(std::string filename) {
         PSG_STAGE("dump: mesh (marching cubes + PLY)");
         if (indexed_mesh() && !VolumetricGradSdf::device_mesh_indexed(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the indexed mesh " << save_path_ << filename << std::endl;
+        if (clean_mesh() && !VolumetricGradSdf::device_mesh_clean(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the cleaned mesh " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");
             if (!ok) std::cout << "couldn't save mesh " << save_path_ << filename << std::endl;

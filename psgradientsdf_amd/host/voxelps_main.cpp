@@ -223,12 +223,15 @@ int main(int argc, char* argv[]) {
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
+    std::string filter_flag;                  // the last of --mesh-min-faces / --mesh-keep-largest given
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
         else if (a == "--host-writers") host_writers() = true;
         else if (a == "--render-keyframes") render_keyframes = true;
         else if (a == "--indexed-mesh") indexed_mesh() = true;      // a <name>_mesh_indexed.ply (welded, normals, binary; include/psgsdf_mesh.h) next to every <name>_mesh.ply
+        else if (a == "--mesh-min-faces" && i + 1 < argc) { mesh_filter().min_faces = atoll(argv[++i]); clean_mesh() = true; filter_flag = a; }      // <name>_mesh_clean.ply + <name>_mesh_components.txt next to every <name>_mesh.ply:
+        else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
@@ -238,6 +241,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--comm-id" && i + 1 < argc) { std::string h = argv[++i]; for (size_t q = 0; q + 1 < h.size(); q += 2) rank_info().id.push_back((uint8_t)strtol(h.substr(q, 2).c_str(), nullptr, 16)); } }      // round 4's dump path (dense download, host marching cubes, iostream) and frame path (serial decode, normals through the host): the cross-check of the device / threaded one
     if (transport != "rccl" && transport != "sockets") { std::cerr << "--transport: rccl or sockets" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && host_writers()) { std::cerr << "--host-writers is the single-process cross-check" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && clean_mesh()) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
+    if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
     if (want_ranks > 1 && !multi_rank()) return launch_ranks(want_ranks, transport == "sockets", argc, argv);
     static std::ofstream null_out;
     if (multi_rank()) {
