@@ -63,6 +63,35 @@ int psgsdf_extract_mesh_components(psgsdf_ctx* ctx, const psgsdf_mesh_filter* fi
     const int32_t** faces, int64_t* n_faces, const int32_t** vertex_component,
     const psgsdf_mesh_component** components, int64_t* n_components);
 
+/* ---- a level-of-detail mesh by vertex clustering (DESIGN.md "Level of detail"; kernels: csrc/mesh_lod.hip)
+ *
+ * Input mesh (V_in vertices, F_in faces): with filter == NULL the welded mesh exactly as psgsdf_extract_mesh_indexed defines it (no component pass);
+ * otherwise exactly what psgsdf_extract_mesh_components(ctx, filter) returns, the kept components renumbered.  vs: the context's float32 voxel size at
+ * the time of the call, widened to double (it halves with the 2x refinement).  cell: the cluster size, a double in the mesh's units.
+ *   - Cluster of a vertex: per axis c[a] = (int64) floor((double) xyz[a] / cell), a true IEEE double division (vertices sit exactly on cell walls
+ *     when cell is a whole number of voxels: the quotient's bits decide).  Same cluster iff all three are equal.  |c[a]| >= 2^20 for any vertex:
+ *     PSGSDF_ERR_UNSUPPORTED and no output.
+ *   - Faces: a face is dropped if two of its three vertices' clusters are equal; of the remaining faces with the same unordered triple of clusters
+ *     only the one with the smallest input index is kept, in its own orientation; kept faces stay in input order.
+ *   - Vertices: one per cluster that a kept face uses, numbered in ascending order of the cluster's smallest member (an input vertex number), so the
+ *     numbering does not depend on thread scheduling.  Members of the other clusters get vertex_map = -1.
+ *   - Attributes of a cluster of n members, all order-independent integer sums:
+ *       position  S[a] = sum llrint((double) xyz[a] * 2^20 / vs);   pos[a] = (float)((double) S[a] / (double) n * (vs / 2^20))
+ *       normal    T[a] = sum llrint((double) normal[a] * 2^20);     T / sqrt((Tx^2 + Ty^2) + Tz^2) in double, rounded to float; (0, 0, 0) if T = 0
+ *       colour    per channel (2 * sum of the bytes + n) / (2 n) in integer arithmetic
+ *     a single-member cluster keeps its member's position, normal and colour bit for bit.
+ * Output: xyz, normals [n_vertices][3] float32, rgb [n_vertices][3] uint8, faces [n_faces][3] int32 in output numbers, vertex_map [n_vertices_in] int32
+ * (the output vertex of every input vertex, or -1), n_vertices_in = V_in, n_faces_in = F_in.  An empty input mesh: all sizes 0, return 0.  The arrays
+ * are engine-owned pinned host memory, valid until the next extraction call on the context; a later psgsdf_extract_mesh_indexed or
+ * psgsdf_extract_mesh_components returns what it returned before.
+ * PSGSDF_ERR_STATE before a volume exists; PSGSDF_ERR_ARG for a cell that is NaN, infinite or <= 0, or a filter psgsdf_extract_mesh_components
+ * refuses; PSGSDF_ERR_UNSUPPORTED for the coordinate bound; PSGSDF_ERR_DEVICE if a temporary cannot be allocated (everything is freed).  On a context
+ * attached to a rank: PSGSDF_ERR_UNSUPPORTED on every rank, at once, before any exchange and before any device work. */
+int psgsdf_extract_mesh_lod(psgsdf_ctx* ctx, const psgsdf_mesh_filter* filter, double cell,
+    const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+    const int32_t** faces, int64_t* n_faces, const int32_t** vertex_map,
+    int64_t* n_vertices_in, int64_t* n_faces_in);
+
 #ifdef __cplusplus
 }
 #endif

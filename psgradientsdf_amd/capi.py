@@ -430,6 +430,21 @@ class Api:
         return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
                     vertex_component=np.ctypeslib.as_array(vc, shape=(V,)).copy() if V else np.zeros(0, np.int32), components=table)
 
+    def extract_mesh_lod(self, cell, min_faces=0, min_area=0.0, keep_largest=0):
+        """A coarser mesh by vertex clustering (include/psgsdf_mesh.h psgsdf_extract_mesh_lod): the vertices of the welded mesh -- of the mesh
+        extract_mesh_components(min_faces, min_area, keep_largest) returns, if one of the three is non-zero -- that fall into the same cube of
+        edge `cell` (the mesh's units) become one vertex.  dict of xyz [V, 3] float32, normals [V, 3] float32, rgb [V, 3] uint8, faces [F, 3] int32,
+        vertex_map [n_vertices_in] int32 (the output vertex of every input vertex, or -1), n_vertices_in, n_faces_in.  Single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)(); vm = C.POINTER(C.c_int32)()
+        nv, nf, nvi, nfi = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_lod")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv),
+                                                 C.byref(fc), C.byref(nf), C.byref(vm), C.byref(nvi), C.byref(nfi)), "extract_mesh_lod")
+        V, F, Vi = nv.value, nf.value, nvi.value
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
+                    vertex_map=np.ctypeslib.as_array(vm, shape=(Vi,)).copy() if Vi else np.zeros(0, np.int32), n_vertices_in=Vi, n_faces_in=nfi.value)
+
     def extract_pointcloud(self, which=0):
         """(xyz_nxyz [n, 6] float32, rgb [n, 3] int32); which = 0: the band voxels, 1: every fused voxel (psgsdf_extract_pointcloud)"""
         pn = C.POINTER(C.c_float)(); col = C.POINTER(C.c_int32)(); n = C.c_int64()

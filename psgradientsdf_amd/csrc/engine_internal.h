@@ -128,7 +128,7 @@ struct psgsdf_ctx {
     std::shared_ptr<void> comm_keep;     // what a built-in caller-side transport (psgsdf_comm_init_sockets) needs for the life of the context
     unsigned long long xr_openers = 0;   // bit r: rank r opened this rank's region at the last set-up (agreed there); xr_quiesce waits for exactly those
     long long xr_serial = 0, xr_closed_off = 0;   // number of the last set-up (the same on every rank) and where the R "closed" slots of a region sit
-    void* xo_host[11] = {}; size_t xo_bytes[11] = {};   // pinned host results of the extraction calls (extract.hip): mesh xyz / rgb, point cloud xyz+n / rgb, sdf block, indexed mesh xyz / normals / rgb / faces, mesh components: component of each vertex / component list; valid until the next extraction
+    void* xo_host[12] = {}; size_t xo_bytes[12] = {};   // pinned host results of the extraction calls (extract.hip): mesh xyz / rgb, point cloud xyz+n / rgb, sdf block, indexed mesh xyz / normals / rgb / faces, mesh components: component of each vertex / component list, level of detail: output vertex of each input vertex; valid until the next extraction
     long long xr_stale_maps = 0;         // mappings that did not show their owner's nonce (xr_setup)
     bool leak_exported = false;          // a peer never reported its mappings closed: xr / rec_mem / hx_mem are never freed by this context
     std::vector<double*> xr_peer;        // [n_ranks] (own entry = xr)

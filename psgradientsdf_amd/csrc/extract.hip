@@ -16,6 +16,7 @@
 #include "engine_internal.h"
 #include "mc_common.h"
 #include "../../include/psgsdf_mesh.h"
+#include "mesh_lod.h"
 
 namespace psg {
 namespace {
@@ -560,18 +561,26 @@ extern "C" int psgsdf_extract_mesh_indexed(psgsdf_ctx* c, const float** xyz, con
 }
 
 // ---- connected components of the welded mesh, and the mesh without its small pieces (include/psgsdf_mesh.h; kernels: mesh_cc.hip; DESIGN.md "Mesh components")
-extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
-                                              const int32_t** faces, int64_t* n_faces, const int32_t** vertex_component, const psgsdf_mesh_component** components, int64_t* n_components) {
-    const char* me = "extract_mesh_components";
-    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_component || !components || !n_components) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
-    // (before anything collective: no rank waits for another)
-    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): components are not merged across z-slabs yet", me, c->rank, c->n_ranks);
-    psgsdf_mesh_filter flt{0, 0.0, 0};
-    if (filter) flt = *filter;
-    if (flt.min_area != flt.min_area || flt.keep_largest < 0) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
-    { int rc = extract_ready(c, me); if (rc) return rc; }
-    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_component = nullptr; *components = nullptr; *n_vertices = 0; *n_faces = 0; *n_components = 0;
+namespace {
+// the filtered mesh of the context's state as device arrays and its component list (pinned host slot 10), the last kernels launched on the stream and
+// not waited for: what psgsdf_extract_mesh_components downloads and psgsdf_extract_mesh_lod goes on from.  After a failure, or with an empty mesh
+// (nv == 0 && nf == 0 && nc == 0), everything has been waited for and freed.
+struct MCompDev {
     WMeshDev m;
+    int *parent = nullptr, *num = nullptr, *vcomp = nullptr, *uses = nullptr, *sums = nullptr, *d_kept = nullptr, *vflag = nullptr, *fflag = nullptr, *o_vcomp = nullptr, *o_faces = nullptr;
+    unsigned long long* keys = nullptr; long long* stat = nullptr; unsigned* box = nullptr;
+    float *o_xyz = nullptr, *o_nrm = nullptr; unsigned char* o_rgb = nullptr;
+    const float *xyz = nullptr, *nrm = nullptr; const unsigned char* rgb = nullptr; const int *faces = nullptr, *vertex_component = nullptr;      // the kept components (the welded arrays themselves if all are kept)
+    int nv = 0, nf = 0, nc = 0; psgsdf_mesh_component* list = nullptr;
+    void release() {
+        hipFree(parent); hipFree(num); hipFree(vcomp); hipFree(uses); hipFree(sums); hipFree(d_kept); hipFree(vflag); hipFree(fflag); hipFree(o_vcomp); hipFree(o_faces);
+        hipFree(keys); hipFree(stat); hipFree(box); hipFree(o_xyz); hipFree(o_nrm); hipFree(o_rgb); m.release();
+        parent = num = vcomp = uses = sums = d_kept = vflag = fflag = o_vcomp = o_faces = nullptr; keys = nullptr; stat = nullptr; box = nullptr; o_xyz = o_nrm = nullptr; o_rgb = nullptr;
+    }
+};
+bool bad_filter(const psgsdf_mesh_filter& flt) { return flt.min_area != flt.min_area || flt.keep_largest < 0; }
+int mcomp_device(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter& flt, MCompDev* d) {
+    WMeshDev& m = d->m;
     int rc = wmesh_device(c, &m);
     if (rc) return rc;
     const int nv = m.nv, nf = m.nf;
@@ -580,13 +589,10 @@ extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_f
     // per component 8 x 8 B of counters and 6 x 4 B of box, the scan's sums; with a filter 1 int per vertex and face and the compacted arrays
     const unsigned long long cap = std::max<unsigned long long>(64, 6ull * (unsigned long long)nf);
     const long long nscan = std::max(nv, nf);
-    int *parent = nullptr, *num = nullptr, *vcomp = nullptr, *uses = nullptr, *sums = nullptr, *d_kept = nullptr, *vflag = nullptr, *fflag = nullptr, *o_vcomp = nullptr, *o_faces = nullptr;
-    unsigned long long* keys = nullptr; long long* stat = nullptr; unsigned* box = nullptr;
-    float *o_xyz = nullptr, *o_nrm = nullptr; unsigned char* o_rgb = nullptr;
-    auto release = [&] {
-        hipFree(parent); hipFree(num); hipFree(vcomp); hipFree(uses); hipFree(sums); hipFree(d_kept); hipFree(vflag); hipFree(fflag); hipFree(o_vcomp); hipFree(o_faces);
-        hipFree(keys); hipFree(stat); hipFree(box); hipFree(o_xyz); hipFree(o_nrm); hipFree(o_rgb); m.release();
-    };
+    int *&parent = d->parent, *&num = d->num, *&vcomp = d->vcomp, *&uses = d->uses, *&sums = d->sums, *&d_kept = d->d_kept, *&vflag = d->vflag, *&fflag = d->fflag, *&o_vcomp = d->o_vcomp, *&o_faces = d->o_faces;
+    unsigned long long*& keys = d->keys; long long*& stat = d->stat; unsigned*& box = d->box;
+    float *&o_xyz = d->o_xyz, *&o_nrm = d->o_nrm; unsigned char*& o_rgb = d->o_rgb;
+    auto release = [&] { d->release(); };
     auto oom = [&] { hipStreamSynchronize(c->stream); release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d vertices, %d faces)", me, nv, nf); };
     if (hipMalloc(&parent, sizeof(int) * (size_t)nv) != hipSuccess || hipMalloc(&num, sizeof(int) * (size_t)nv) != hipSuccess || hipMalloc(&vcomp, sizeof(int) * (size_t)nv) != hipSuccess
         || hipMalloc(&keys, sizeof(unsigned long long) * (size_t)cap) != hipSuccess || hipMalloc(&uses, sizeof(int) * (size_t)cap) != hipSuccess
@@ -614,7 +620,7 @@ extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_f
         || hipMemcpyAsync(hbox.data(), box, sizeof(unsigned) * hbox.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         release(); return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the component table", me);
     }
-    void *hx = nullptr, *hn = nullptr, *hc = nullptr, *hf = nullptr, *hv = nullptr, *hl = nullptr;
+    void* hl = nullptr;
     rc = host_out(c, 10, sizeof(psgsdf_mesh_component) * (size_t)nc, &hl);
     if (rc) { release(); return rc; }
     psgsdf_mesh_component* list = (psgsdf_mesh_component*)hl;
@@ -654,6 +660,28 @@ extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_f
         }
         r_xyz = o_xyz; r_nrm = o_nrm; r_rgb = o_rgb; r_faces = o_faces; r_vcomp = o_vcomp;
     }
+    d->xyz = r_xyz; d->nrm = r_nrm; d->rgb = r_rgb; d->faces = r_faces; d->vertex_component = r_vcomp; d->nv = ov; d->nf = of; d->nc = nc; d->list = list;
+    return PSGSDF_OK;
+}
+}  // namespace
+
+extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+                                              const int32_t** faces, int64_t* n_faces, const int32_t** vertex_component, const psgsdf_mesh_component** components, int64_t* n_components) {
+    const char* me = "extract_mesh_components";
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_component || !components || !n_components) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    // (before anything collective: no rank waits for another)
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): components are not merged across z-slabs yet", me, c->rank, c->n_ranks);
+    psgsdf_mesh_filter flt{0, 0.0, 0};
+    if (filter) flt = *filter;
+    if (bad_filter(flt)) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_component = nullptr; *components = nullptr; *n_vertices = 0; *n_faces = 0; *n_components = 0;
+    MCompDev d;
+    int rc = mcomp_device(c, me, flt, &d);
+    if (rc || d.nc == 0) return rc;      // (failed, or an empty mesh: waited for and freed)
+    const int ov = d.nv, of = d.nf;
+    const float *r_xyz = d.xyz, *r_nrm = d.nrm; const unsigned char* r_rgb = d.rgb; const int *r_faces = d.faces, *r_vcomp = d.vertex_component;
+    void *hx = nullptr, *hn = nullptr, *hc = nullptr, *hf = nullptr, *hv = nullptr;
     if (ov > 0 && of > 0) {
         rc = host_out(c, 5, sizeof(float) * 3 * (size_t)ov, &hx);
         if (!rc) rc = host_out(c, 6, sizeof(float) * 3 * (size_t)ov, &hn);
@@ -668,8 +696,108 @@ extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_f
         }
         if (!rc) { *xyz = (const float*)hx; *normals = (const float*)hn; *rgb = (const uint8_t*)hc; *faces = (const int32_t*)hf; *vertex_component = (const int32_t*)hv; *n_vertices = ov; *n_faces = of; }
     }
-    if (!rc) { *components = list; *n_components = nc; }
+    if (!rc) { *components = d.list; *n_components = d.nc; }
+    hipStreamSynchronize(c->stream);
+    d.release();
+    return rc;
+}
+
+// ---- a level-of-detail mesh by vertex clustering (include/psgsdf_mesh.h; kernels: mesh_lod.hip; DESIGN.md "Level of detail")
+namespace {
+struct LodOut {
+    const float** xyz; const float** normals; const uint8_t** rgb; int64_t* n_vertices; const int32_t** faces; int64_t* n_faces; const int32_t** vertex_map;
+    int64_t* n_vertices_in; int64_t* n_faces_in;
+};
+// from an input mesh on the device (nv > 0, nf > 0; its kernels may still be in flight on the stream) to the pinned host slots 5-8 and 11.  The
+// stream has been waited for and every temporary freed when this returns, whatever it returns.
+int lod_from_device(psgsdf_ctx* c, const float* xyz, const float* nrm, const unsigned char* rgb, const int* faces, int nv, int nf, double cell, const LodOut& o) {
+    const char* me = "extract_mesh_lod";
+    if (nv >= (1 << 30) || nf >= (1 << 30)) { hipStreamSynchronize(c->stream); return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: %d vertices, %d faces", me, nv, nf); }      // (slots are ints)
+    // temporaries: the cluster table of 2 nv slots (8 B key, 10 x 8 B of sums, 4 B smallest member, 4 B used flag), the face table of 2 nf slots (4 B),
+    // per vertex its slot, its flag / output number and its map entry, per face its slot and its flag / output number, the scan's sums
+    psg::MlodTables t{};
+    t.vcap = std::max<unsigned long long>(64, 2ull * (unsigned long long)nv); t.fcap = std::max<unsigned long long>(64, 2ull * (unsigned long long)nf);
+    const long long nscan = std::max(nv, nf);
+    int *vflag = nullptr, *fflag = nullptr, *sums = nullptr, *vmap = nullptr, *o_faces = nullptr;
+    float *o_xyz = nullptr, *o_nrm = nullptr; unsigned char* o_rgb = nullptr;
+    auto release = [&] {
+        hipFree(t.keys); hipFree(t.acc); hipFree(t.first); hipFree(t.used); hipFree(t.vslot); hipFree(t.ftab); hipFree(t.fslot); hipFree(t.bad);
+        hipFree(vflag); hipFree(fflag); hipFree(sums); hipFree(vmap); hipFree(o_faces); hipFree(o_xyz); hipFree(o_nrm); hipFree(o_rgb);
+    };
+    auto give_up = [&](int code, const char* what) { hipStreamSynchronize(c->stream); release(); return fail(c, code, "%s: %s (%d vertices, %d faces)", me, what, nv, nf); };
+    if (hipMalloc(&t.keys, sizeof(unsigned long long) * (size_t)t.vcap) != hipSuccess || hipMalloc(&t.acc, sizeof(long long) * psg::kMlodAcc * (size_t)t.vcap) != hipSuccess
+        || hipMalloc(&t.first, sizeof(int) * (size_t)t.vcap) != hipSuccess || hipMalloc(&t.used, sizeof(int) * (size_t)t.vcap) != hipSuccess || hipMalloc(&t.vslot, sizeof(int) * (size_t)nv) != hipSuccess
+        || hipMalloc(&t.ftab, sizeof(int) * (size_t)t.fcap) != hipSuccess || hipMalloc(&t.fslot, sizeof(int) * (size_t)nf) != hipSuccess || hipMalloc(&t.bad, sizeof(int)) != hipSuccess
+        || hipMalloc(&vflag, sizeof(int) * (size_t)nv) != hipSuccess || hipMalloc(&fflag, sizeof(int) * (size_t)nf) != hipSuccess || hipMalloc(&vmap, sizeof(int) * (size_t)nv) != hipSuccess
+        || hipMalloc(&sums, sizeof(int) * (size_t)((nscan + psg::kTile - 1) / psg::kTile + 1)) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "out of memory");
+    if (hipMemsetAsync(t.keys, 0xff, sizeof(unsigned long long) * (size_t)t.vcap, c->stream) != hipSuccess || hipMemsetAsync(t.acc, 0, sizeof(long long) * psg::kMlodAcc * (size_t)t.vcap, c->stream) != hipSuccess
+        || hipMemsetAsync(t.first, 0x7f, sizeof(int) * (size_t)t.vcap, c->stream) != hipSuccess || hipMemsetAsync(t.used, 0, sizeof(int) * (size_t)t.vcap, c->stream) != hipSuccess
+        || hipMemsetAsync(t.ftab, 0xff, sizeof(int) * (size_t)t.fcap, c->stream) != hipSuccess || hipMemsetAsync(t.bad, 0, sizeof(int), c->stream) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "memset");
+    const double vs = (double)c->grid.vs;
+    timed(c, "mlod_cluster", [&] { psg::launch_mlod_cluster(xyz, nrm, rgb, nv, cell, vs, t, c->stream); });
+    int bad = 0;
+    if (hipMemcpyAsync(&bad, t.bad, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "kernels");
+    if (bad) return give_up(PSGSDF_ERR_UNSUPPORTED, "a cluster coordinate is beyond 2^20: the cell is too small for this mesh");
+    timed(c, "mlod_ftable", [&] { psg::launch_mlod_ftable(faces, nf, t, c->stream); });
+    timed(c, "mlod_fkeep", [&] { psg::launch_mlod_fkeep(faces, nf, t, fflag, c->stream); });
+    timed(c, "mlod_vflag", [&] { psg::launch_mlod_vflag(nv, t, vflag, c->stream); });
+    int ov = 0, of = 0;
+    int rc = scan_counts(c, vflag, nv, sums, &ov);      // smallest-member flags -> output vertex numbers
+    if (!rc) rc = scan_counts(c, fflag, nf, sums, &of);     // kept-face flags -> output face numbers
+    if (rc) { hipStreamSynchronize(c->stream); release(); return rc; }
+    if (ov > 0 && (hipMalloc(&o_xyz, sizeof(float) * 3 * (size_t)ov) != hipSuccess || hipMalloc(&o_nrm, sizeof(float) * 3 * (size_t)ov) != hipSuccess || hipMalloc(&o_rgb, 3 * (size_t)ov) != hipSuccess
+                   || hipMalloc(&o_faces, sizeof(int) * 3 * (size_t)of) != hipSuccess)) return give_up(PSGSDF_ERR_DEVICE, "out of memory");      // (a vertex exists only with a face: of > 0)
+    timed(c, "mlod_emit", [&] { psg::launch_mlod_emit(xyz, nrm, rgb, nv, faces, nf, vs, t, vflag, fflag, o_xyz, o_nrm, o_rgb, o_faces, vmap, c->stream); });
+    void *hx = nullptr, *hn = nullptr, *hc = nullptr, *hf = nullptr, *hm = nullptr;
+    rc = host_out(c, 11, sizeof(int) * (size_t)nv, &hm);
+    if (!rc && ov > 0) {
+        rc = host_out(c, 5, sizeof(float) * 3 * (size_t)ov, &hx);
+        if (!rc) rc = host_out(c, 6, sizeof(float) * 3 * (size_t)ov, &hn);
+        if (!rc) rc = host_out(c, 7, 3 * (size_t)ov, &hc);
+        if (!rc) rc = host_out(c, 8, sizeof(int) * 3 * (size_t)of, &hf);
+    }
+    if (!rc) {
+        bool cp = hipMemcpyAsync(hm, vmap, sizeof(int) * (size_t)nv, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (cp && ov > 0) cp = hipMemcpyAsync(hx, o_xyz, sizeof(float) * 3 * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipMemcpyAsync(hn, o_nrm, sizeof(float) * 3 * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess
+                                && hipMemcpyAsync(hc, o_rgb, 3 * (size_t)ov, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipMemcpyAsync(hf, o_faces, sizeof(int) * 3 * (size_t)of, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+        if (!cp || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: download", me);
+    }
+    if (!rc) {
+        *o.vertex_map = (const int32_t*)hm; *o.n_vertices_in = nv; *o.n_faces_in = nf;
+        if (ov > 0) { *o.xyz = (const float*)hx; *o.normals = (const float*)hn; *o.rgb = (const uint8_t*)hc; *o.faces = (const int32_t*)hf; *o.n_vertices = ov; *o.n_faces = of; }
+    }
     hipStreamSynchronize(c->stream);
     release();
+    return rc;
+}
+}  // namespace
+
+extern "C" int psgsdf_extract_mesh_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+                                       const int32_t** faces, int64_t* n_faces, const int32_t** vertex_map, int64_t* n_vertices_in, int64_t* n_faces_in) {
+    const char* me = "extract_mesh_lod";
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_map || !n_vertices_in || !n_faces_in) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    // (before anything collective and before any device work: no rank waits for another)
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): clusters are not merged across z-slabs", me, c->rank, c->n_ranks);
+    if (!(cell > 0.0) || std::isinf(cell)) return fail(c, PSGSDF_ERR_ARG, "%s: the cell must be a finite size > 0", me);
+    if (filter && bad_filter(*filter)) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_map = nullptr; *n_vertices = 0; *n_faces = 0; *n_vertices_in = 0; *n_faces_in = 0;
+    const LodOut out{xyz, normals, rgb, n_vertices, faces, n_faces, vertex_map, n_vertices_in, n_faces_in};
+    int rc = 0;
+    if (!filter) {      // the welded mesh as it is: no component pass
+        WMeshDev m;
+        rc = wmesh_device(c, &m);
+        if (rc) return rc;
+        if (m.nv > 0 && m.nf > 0) rc = lod_from_device(c, m.xyz, m.nrm, m.rgb, m.faces, m.nv, m.nf, cell, out);
+        else if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: kernels", me);
+        m.release();
+        return rc;
+    }
+    MCompDev d;
+    rc = mcomp_device(c, me, *filter, &d);
+    if (rc || d.nc == 0) return rc;      // (failed, or an empty mesh: waited for and freed)
+    if (d.nv > 0 && d.nf > 0) rc = lod_from_device(c, d.xyz, d.nrm, d.rgb, d.faces, d.nv, d.nf, cell, out);
+    else if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: kernels", me);
+    d.release();
     return rc;
 }

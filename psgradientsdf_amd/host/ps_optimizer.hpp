@@ -97,6 +97,9 @@ inline bool& indexed_mesh() { static bool v = false; return v; }      // voxelPS
 // the filter drops, psgsdf_extract_mesh_components) and a <name>_mesh_components.txt (every component, one per line); single process only
 inline bool& clean_mesh() { static bool v = false; return v; }
 inline psgsdf_mesh_filter& mesh_filter() { static psgsdf_mesh_filter f{0, 0.0, 0}; return f; }
+// voxelPS --mesh-lod S: next to every <name>_mesh.ply a <name>_mesh_lod.ply, the welded mesh (the filtered one, if a filter flag is given) with the vertices
+// of every cube of S voxels merged into one (psgsdf_extract_mesh_lod); 0: off; single process only
+inline double& mesh_lod_voxels() { static double v = 0.0; return v; }
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
 inline bool& skip_sync_back() { static bool v = false; return v; }      // voxelPS --host-writers: round 4's path (dense download, host marching cubes, iostream): the cross-check
@@ -405,6 +408,7 @@ struct VolumetricGradSdf {
         PSG_STAGE("dump: mesh (marching cubes + PLY)");
         if (ctx && indexed_mesh() && !device_mesh_indexed(ctx, filename)) std::cout << "couldn't save the indexed mesh of " << filename << std::endl;
         if (ctx && clean_mesh() && !device_mesh_clean(ctx, filename)) std::cout << "couldn't save the cleaned mesh of " << filename << std::endl;
+        if (ctx && mesh_lod_voxels() > 0 && !device_mesh_lod(ctx, filename)) std::cout << "couldn't save the level-of-detail mesh of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
     }
@@ -475,6 +479,30 @@ struct VolumetricGradSdf {
             ok = f && fwrite(table.data(), 1, table.size(), f) == table.size() && ok;
             if (f && fclose(f) != 0) ok = false;
             if (!ok) { std::cout << "couldn't save the cleaned mesh " << base << std::endl; DumpQueue::get().report_failure(); }
+        });
+        return true;
+    }
+    // <name>_mesh.ply -> <name>_mesh_lod.ply (the binary format of _mesh_indexed.ply and one more comment line): cell = S voxels of the state's voxel size
+    static bool device_mesh_lod(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: level-of-detail mesh (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string base = mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                 ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file;
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr; const int32_t* vmap = nullptr;
+        int64_t nv = 0, nf = 0, nv_in = 0, nf_in = 0;
+        if (psgsdf_extract_mesh_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, mesh_lod_voxels() * (double)info.voxel_size, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vmap, &nv_in, &nf_in) != 0
+            || nf_in == 0) return false;
+        char line[200];
+        snprintf(line, sizeof line, "comment lod cell %.9g voxels from %lld vertices %lld faces\n", mesh_lod_voxels(), (long long)nv_in, (long long)nf_in);
+        const std::string extra = line;
+        auto vx = std::make_shared<std::vector<float>>(xyz, xyz + 3 * nv), vn = std::make_shared<std::vector<float>>(nrm, nrm + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(rgb, rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(faces, faces + 3 * nf);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            if (!write_mesh_indexed_ply(base + "_mesh_lod.ply", vx->data(), vn->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, extra)) {
+                std::cout << "couldn't save the level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure();
+            }
         });
         return true;
     }
@@ -874,6 +902,7 @@ public:
         PSG_STAGE("dump: mesh (marching cubes + PLY)");
         if (indexed_mesh() && !VolumetricGradSdf::device_mesh_indexed(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the indexed mesh " << save_path_ << filename << std::endl;
         if (clean_mesh() && !VolumetricGradSdf::device_mesh_clean(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the cleaned mesh " << save_path_ << filename << std::endl;
+        if (mesh_lod_voxels() > 0 && !VolumetricGradSdf::device_mesh_lod(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the level-of-detail mesh " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");
             if (!ok) std::cout << "couldn't save mesh " << save_path_ << filename << std::endl;

@@ -224,6 +224,7 @@ int main(int argc, char* argv[]) {
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
     std::string filter_flag;                  // the last of --mesh-min-faces / --mesh-keep-largest given
+    bool lod_flag = false, lod_ok = true;     // --mesh-lod S given / S is a number > 0
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
@@ -232,6 +233,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--indexed-mesh") indexed_mesh() = true;      // a <name>_mesh_indexed.ply (welded, normals, binary; include/psgsdf_mesh.h) next to every <name>_mesh.ply
         else if (a == "--mesh-min-faces" && i + 1 < argc) { mesh_filter().min_faces = atoll(argv[++i]); clean_mesh() = true; filter_flag = a; }      // <name>_mesh_clean.ply + <name>_mesh_components.txt next to every <name>_mesh.ply:
         else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
+        else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_lod_voxels() = lod_ok ? v : 0.0; lod_flag = true; }      // <name>_mesh_lod.ply next to every <name>_mesh.ply: the vertices of every cube of S voxels merged (include/psgsdf_mesh.h psgsdf_extract_mesh_lod)
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
@@ -242,6 +244,8 @@ int main(int argc, char* argv[]) {
     if (transport != "rccl" && transport != "sockets") { std::cerr << "--transport: rccl or sockets" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && host_writers()) { std::cerr << "--host-writers is the single-process cross-check" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && clean_mesh()) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
+    if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && lod_flag) { std::cerr << "--mesh-lod needs a single process: clusters are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
     if (want_ranks > 1 && !multi_rank()) return launch_ranks(want_ranks, transport == "sockets", argc, argv);
     static std::ofstream null_out;
