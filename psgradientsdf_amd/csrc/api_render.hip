@@ -9,19 +9,7 @@ using namespace psge;
 
 namespace {
 
-// per-call device memory: brick map, bbox, planes, partials, folded sums (freed on every exit path)
-struct RenderMem {
-    std::vector<void*> p;
-    ~RenderMem() { for (void* q : p) hipFree(q); }
-    template <class T> hipError_t get(T** out, size_t bytes) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes < 8 ? 8 : bytes);
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T*)q;
-        return e;
-    }
-};
-
+int oom(psgsdf_ctx* c) { return fail(c, PSGSDF_ERR_DEVICE, "render: out of device memory"); }
 constexpr size_t kRenderChunkBytes = (size_t)256 << 20;     // multi-rank report: per-pixel exchange buffers of one chunk of keyframes
 
 int render_ready(psgsdf_ctx* c, const char* what) {
@@ -55,7 +43,7 @@ int allreduce_big(psgsdf_ctx* c, double* buf, size_t n) {
 // Multi-rank: each rank marks the bricks of the planes it owns (global brick coordinates); the first exchange sums the marks together with every
 // rank's z0 (-> this rank's place in the z order, a.slab) and checksum `tag` of the call; the map and box then come from the merged marks.
 // err_local: this rank's own argument error (reported once the exchange shows every rank that the call failed).
-int render_args(psgsdf_ctx* c, RenderMem& m, RenderArgs& a, double tag, const char* what, const char* err_local) {
+int render_args(psgsdf_ctx* c, DevMem& m, RenderArgs& a, double tag, const char* what, const char* err_local) {
     a = RenderArgs{};
     a.d = c->dense;
     for (int k = 0; k < 3; ++k) a.vp[k] = c->band.vp[k];
@@ -68,8 +56,8 @@ int render_args(psgsdf_ctx* c, RenderMem& m, RenderArgs& a, double tag, const ch
     for (int k = 0; k < 3; ++k) a.nb[k] = (a.grid.dim[k] + kRenderBrick - 1) / kRenderBrick;
     const size_t nbr = (size_t)a.nb[0] * a.nb[1] * a.nb[2];
     unsigned char* bricks = nullptr; int* bbox = nullptr;
-    HIPCHK(c, m.get(&bricks, nbr));
-    HIPCHK(c, m.get(&bbox, 6 * sizeof(int)));
+    if (!m.get(&bricks, nbr)) return oom(c);
+    if (!m.get(&bbox, 6)) return oom(c);
     HIPCHK(c, hipMemsetAsync(bbox, 0x7f, 6 * sizeof(int), c->stream));
     const float thr = (float)(0.5 * sqrt(3.0) * (double)c->grid.vs * (1.0 + 1e-3));
     a.bricks = bricks; a.bbox = bbox;
@@ -81,7 +69,7 @@ int render_args(psgsdf_ctx* c, RenderMem& m, RenderArgs& a, double tag, const ch
     }
     const int R = c->n_ranks;
     double* marks = nullptr;
-    HIPCHK(c, m.get(&marks, sizeof(double) * (nbr + 2 * R)));
+    if (!m.get(&marks, nbr + 2 * R)) return oom(c);
     timed(c, "k_render_bricks", [&] { launch_render_bricks(c->dense, a.grid, thr, c->z0, c->z1, nullptr, nullptr, marks, c->stream); });
     std::vector<double> tail(2 * R, 0.0);
     tail[c->rank] = (double)c->z0; tail[R + c->rank] = err_local ? -1.0 : tag;
@@ -167,7 +155,7 @@ int psgsdf_render(psgsdf_ctx* c, const psgsdf_view* v, uint32_t channels, float*
         if (channels & PSGSDF_R_RESIDUAL) bad("render: a residual needs a keyframe view");
     }
     if (err[0] && !mr) return fail(c, PSGSDF_ERR_ARG, "%s", err);
-    RenderMem m;
+    DevMem m;      // per-call device memory: brick map, bbox, planes, partials, folded sums
     RenderArgs a;
     { int rc = render_args(c, m, a, view_hash(v, channels), "render", err[0] ? err : nullptr); if (rc) return rc; }
     if (key) { a.cam = c->cam; a.frame = v->frame; a.light_frame = v->frame; }
@@ -183,18 +171,18 @@ int psgsdf_render(psgsdf_ctx* c, const psgsdf_view* v, uint32_t channels, float*
     for (int q = 0; q < RP_COUNT; ++q) if (channels & (1u << q)) nplanes += kPlaneCh[q];
     float* planes = nullptr; double* sums = nullptr;
     if (nplanes) {
-        HIPCHK(c, m.get(&planes, sizeof(float) * nplanes * HW));
+        if (!m.get(&planes, nplanes * HW)) return oom(c);
         size_t off = 0;
         for (int q = 0; q < RP_COUNT; ++q) if (channels & (1u << q)) { a.planes[q] = planes + off * HW; off += kPlaneCh[q]; }
     }
-    HIPCHK(c, m.get(&a.part, sizeof(double) * kRenderStats * (size_t)tiles));
-    HIPCHK(c, m.get(&sums, sizeof(double) * kRenderStats));
+    if (!m.get(&a.part, kRenderStats * (size_t)tiles)) return oom(c);
+    if (!m.get(&sums, kRenderStats)) return oom(c);
     if (mr) {
         carry_fields(a, channels, key);
         a.rec_px = (long long)HW;
-        HIPCHK(c, m.get(&a.mask, sizeof(double) * HW));
-        HIPCHK(c, m.get(&a.mine, HW));
-        HIPCHK(c, m.get(&a.rec, sizeof(double) * HW * a.n_rf));
+        if (!m.get(&a.mask, HW)) return oom(c);
+        if (!m.get(&a.mine, HW)) return oom(c);
+        if (!m.get(&a.rec, HW * a.n_rf)) return oom(c);
         { int rc = render_ranks_pass(c, a, false, 1); if (rc) return rc; }
     } else timed(c, "k_render", [&] { launch_render(a, c->set.model, c->stream); });
     timed(c, "k_render_fold", [&] { launch_render_fold(a.part, tiles, 1, sums, c->stream); });
@@ -210,7 +198,7 @@ int psgsdf_render(psgsdf_ctx* c, const psgsdf_view* v, uint32_t channels, float*
 int psgsdf_render_report(psgsdf_ctx* c, psgsdf_render_stats* per_keyframe) {
     if (!c || (!per_keyframe && c->n_ranks <= 1)) return fail(c, PSGSDF_ERR_ARG, "render_report: null argument");
     { int rc = render_ready(c, "render_report"); if (rc) return rc; }
-    RenderMem m;
+    DevMem m;      // per-call device memory: brick map, bbox, planes, partials, folded sums
     RenderArgs a;
     const double tag = (double)CallHash{}.add(2).h;
     { int rc = render_args(c, m, a, tag, "render_report", per_keyframe ? nullptr : "render_report: null argument"); if (rc) return rc; }
@@ -218,16 +206,16 @@ int psgsdf_render_report(psgsdf_ctx* c, psgsdf_render_stats* per_keyframe) {
     a.tiles_x = (a.cam.W + kRenderTile - 1) / kRenderTile; a.tiles_y = (a.cam.H + kRenderTile - 1) / kRenderTile;
     const int tiles = a.tiles_x * a.tiles_y;
     double* sums = nullptr;
-    HIPCHK(c, m.get(&a.part, sizeof(double) * kRenderStats * (size_t)tiles * c->F));
-    HIPCHK(c, m.get(&sums, sizeof(double) * kRenderStats * c->F));
+    if (!m.get(&a.part, kRenderStats * (size_t)tiles * c->F)) return oom(c);
+    if (!m.get(&sums, kRenderStats * c->F)) return oom(c);
     if (c->n_ranks > 1) {
         // keyframes in chunks: mask, hit byte and records (rendered colour, off-band flag) of every pixel of a chunk within kRenderChunkBytes
         carry_fields(a, 0, true);
         const size_t HW = (size_t)a.cam.W * a.cam.H, per_frame = HW * (sizeof(double) * (1 + a.n_rf) + 1);
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->F, kRenderChunkBytes / per_frame));
-        HIPCHK(c, m.get(&a.mask, sizeof(double) * HW * chunk));
-        HIPCHK(c, m.get(&a.mine, HW * chunk));
-        HIPCHK(c, m.get(&a.rec, sizeof(double) * HW * chunk * a.n_rf));
+        if (!m.get(&a.mask, HW * chunk)) return oom(c);
+        if (!m.get(&a.mine, HW * chunk)) return oom(c);
+        if (!m.get(&a.rec, HW * chunk * a.n_rf)) return oom(c);
         for (int f0 = 0; f0 < c->F; f0 += chunk) {
             const int n = std::min(chunk, c->F - f0);
             a.f0 = f0; a.rec_px = (long long)(HW * n);

@@ -3,7 +3,9 @@
 //   loop.hip          the solves and the alternation loop (fused PCG driver, sub-steps, psgsdf_iterate / psgsdf_optimize control flow)
 //   api.hip           the C ABI of include/psgsdf.h (volume, keyframes, init, steps, downloads)
 //   api_frontend.hip  frame fusion, FALS normals, depth tracker        api_multi_gpu.hip  the z-slab phase API
-//   api_debug.hip     measurement and test hooks
+//   api_debug.hip     measurement and test hooks               api_render.hip     the C ABI of include/psgsdf_render.h
+//   extract.hip       mesh, point clouds, SDF block on the device (kernels and calls); extract_mesh.hip: the welded mesh, its components and
+//                     its level of detail (include/psgsdf_mesh.h); what the two share: extract_internal.h
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"
@@ -29,6 +31,16 @@ struct Comm;                  // comm.hip: RCCL communicator or caller-supplied 
 struct MgSeg { unsigned off, n; unsigned long long key; };
 // a scalar read-back waiting in the host-mapped mailbox: n values at src, their check words behind them (engine.h FoldReq; key 0: unchecked)
 struct Deferred { const double* src; int n; unsigned long long key; std::function<void(const double*)> consume; };
+// pinned host slots of the extraction calls' results (psgsdf_ctx::xo_host)
+enum XoSlot {
+    XO_MESH_XYZ, XO_MESH_RGB,                                        // psgsdf_extract_mesh
+    XO_PC_XYZN, XO_PC_RGB,                                           // psgsdf_extract_pointcloud
+    XO_SDF,                                                          // psgsdf_extract_sdf
+    XO_IMESH_XYZ, XO_IMESH_NORMALS, XO_IMESH_RGB, XO_IMESH_FACES,    // psgsdf_extract_mesh_indexed, _components and _lod: each call's own mesh
+    XO_VERTEX_COMPONENT, XO_COMPONENTS,                              // psgsdf_extract_mesh_components (the list also when _lod filters)
+    XO_LOD_VERTEX_MAP,                                               // psgsdf_extract_mesh_lod
+    XO_COUNT
+};
 }  // namespace psge
 using psge::KTime;
 using namespace psg;   // the layout structs of engine.h
@@ -128,7 +140,7 @@ struct psgsdf_ctx {
     std::shared_ptr<void> comm_keep;     // what a built-in caller-side transport (psgsdf_comm_init_sockets) needs for the life of the context
     unsigned long long xr_openers = 0;   // bit r: rank r opened this rank's region at the last set-up (agreed there); xr_quiesce waits for exactly those
     long long xr_serial = 0, xr_closed_off = 0;   // number of the last set-up (the same on every rank) and where the R "closed" slots of a region sit
-    void* xo_host[12] = {}; size_t xo_bytes[12] = {};   // pinned host results of the extraction calls (extract.hip): mesh xyz / rgb, point cloud xyz+n / rgb, sdf block, indexed mesh xyz / normals / rgb / faces, mesh components: component of each vertex / component list, level of detail: output vertex of each input vertex; valid until the next extraction
+    void* xo_host[psge::XO_COUNT] = {}; size_t xo_bytes[psge::XO_COUNT] = {};   // pinned host results of the extraction calls, one slot per array (psge::XoSlot); the three indexed-mesh calls share XO_IMESH_*: a result is valid until the next extraction
     long long xr_stale_maps = 0;         // mappings that did not show their owner's nonce (xr_setup)
     bool leak_exported = false;          // a peer never reported its mappings closed: xr / rec_mem / hx_mem are never freed by this context
     std::vector<double*> xr_peer;        // [n_ranks] (own entry = xr)
@@ -205,6 +217,24 @@ using namespace psg;
 int fail(psgsdf_ctx* c, int code, const char* fmt, ...);
 inline unsigned long long dbits(double v) { unsigned long long u; memcpy(&u, &v, 8); return u; }
 #define HIPCHK(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
+
+// per-call device memory: whatever get() handed out is freed at scope exit -- after the context's stream has been waited for, if the owner was
+// given a context (kernels in flight may still read or write it)
+struct DevMem {
+    explicit DevMem(psgsdf_ctx* wait_for = nullptr) : c(wait_for) {}
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { if (c) hipStreamSynchronize(c->stream); for (void* q : p) hipFree(q); }
+    template <class T> bool get(T** out, size_t count) {
+        void* q = nullptr;
+        const bool ok = hipMalloc(&q, std::max<size_t>(8, sizeof(T) * count)) == hipSuccess;
+        if (ok) p.push_back(q);
+        *out = (T*)q;
+        return ok;
+    }
+private:
+    psgsdf_ctx* c; std::vector<void*> p;
+};
 
 template <class Fn> void timed(psgsdf_ctx* c, const char* name, Fn&& fn) {
     if (!c->profiling) {

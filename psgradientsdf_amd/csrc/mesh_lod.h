@@ -1,4 +1,4 @@
-// mesh_lod.h -- the launchers of mesh_lod.hip (psgsdf_extract_mesh_lod, include/psgsdf_mesh.h; DESIGN.md "Level of detail"), called from extract.hip.
+// mesh_lod.h -- the launchers of mesh_lod.hip (psgsdf_extract_mesh_lod, include/psgsdf_mesh.h; DESIGN.md "Level of detail"), called from extract_mesh.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
