@@ -445,6 +445,31 @@ class Api:
         return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
                     vertex_map=np.ctypeslib.as_array(vm, shape=(Vi,)).copy() if Vi else np.zeros(0, np.int32), n_vertices_in=Vi, n_faces_in=nfi.value)
 
+    # -- the photometric fit resolved over the surface (include/psgsdf_fit.h)
+    def band_fit(self):
+        """Per band row, in download_band's order (psgsdf_band_fit): dict of n_obs [n_band] int32 (the observations the energy counts), loss [n_band]
+        float64 (the row's share of the sum behind energy()[0]: sum(loss) / n_band is E_ps), sum_r2 [n_band, 3] float32 (squared residuals per channel).
+        Single contexts only."""
+        no = C.POINTER(C.c_int32)(); ls = C.POINTER(C.c_double)(); r2 = C.POINTER(C.c_float)(); n = C.c_int64()
+        self._check(self._fn("band_fit")(self.ctx, C.byref(no), C.byref(ls), C.byref(r2), C.byref(n)), "band_fit")
+        S = n.value
+        if S == 0:
+            return dict(n_obs=np.zeros(0, np.int32), loss=np.zeros(0, np.float64), sum_r2=np.zeros((0, 3), np.float32))
+        return dict(n_obs=np.ctypeslib.as_array(no, shape=(S,)).copy(), loss=np.ctypeslib.as_array(ls, shape=(S,)).copy(), sum_r2=np.ctypeslib.as_array(r2, shape=(S, 3)).copy())
+
+    def extract_mesh_fit(self):
+        """The welded mesh with the fit of its vertices (psgsdf_extract_mesh_fit): dict of xyz, normals, rgb, faces (extract_mesh_indexed's arrays) and
+        n_obs [V] int32, rms [V] float32, loss [V] float32 -- the observations of the vertex's end voxels, their rms residual and mean robust loss; zeros
+        where nothing was observed.  Single contexts only."""
+        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)()
+        no = C.POINTER(C.c_int32)(); rms = C.POINTER(C.c_float)(); ls = C.POINTER(C.c_float)(); nv, nf = C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_fit")(self.ctx, C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(no), C.byref(rms), C.byref(ls)), "extract_mesh_fit")
+        V, F = nv.value, nf.value
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        col = lambda p, dt: np.ctypeslib.as_array(p, shape=(V,)).copy() if V else np.zeros(0, dt)
+        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
+                    n_obs=col(no, np.int32), rms=col(rms, np.float32), loss=col(ls, np.float32))
+
     def extract_pointcloud(self, which=0):
         """(xyz_nxyz [n, 6] float32, rgb [n, 3] int32); which = 0: the band voxels, 1: every fused voxel (psgsdf_extract_pointcloud)"""
         pn = C.POINTER(C.c_float)(); col = C.POINTER(C.c_int32)(); n = C.c_int64()

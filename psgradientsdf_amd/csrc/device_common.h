@@ -10,6 +10,7 @@
 //   band.hip       : k_select_vis, k_band_flags, k_scan_*, k_band_fill, k_band_nb, k_band_scatter, k_upsample, k_derive, k_obs_*, k_sum_parts
 //   sweeps.hip     : k_init_albedo, k_energy, k_sweep_albedo (voxel-major, set-bit iteration); k_sweep_light, k_sweep_pose
 //                    (frame-major, wave + LDS reduction); k_solve_light, k_solve_pose (LDL^T per frame)
+//   fit.hip        : k_band_fit (k_energy's loop with the row's sums stored, not reduced), k_wmesh_fit (those sums on the welded mesh's vertices)
 //   dist.hip       : k_sweep_dist, k_assemble (per-pass path only)
 //   pcg.hip        : k_cgp_solve (the whole distance step as ONE persistent kernel: assembly into LDS, pipelined Jacobi-PCG in double, update; the
 //                    default), k_cgf_solve (the same with the classic recurrences), k_cgf_init / k_cgf_pass / k_cgf_sum (one kernel per pass:

@@ -1,5 +1,5 @@
 // engine.h — data layout shared by the host orchestration (engine.hip, loop.hip, api*.hip; engine_internal.h) and the gfx950 kernels
-// (band.hip, sweeps.hip, dist.hip, pcg.hip, albedo_reg.hip, frontend.hip).  Internal: the public boundary is include/psgsdf.h.
+// (band.hip, sweeps.hip, fit.hip, dist.hip, pcg.hip, albedo_reg.hip, frontend.hip).  Internal: the public boundary is include/psgsdf.h.
 //
 // Layout in HBM:
 //   dense grid  : SoA planes dist | gx | gy | gz | weight | r | g | b (float, x-fastest) + packed
@@ -344,6 +344,13 @@ void launch_wmesh_or(int* dst, const int* src, long long n, hipStream_t s);     
 // faces: vertex number of slot q = q < nown ? num[q] + first : num_up[q - nown] + first_up (num: exclusive scan of the flags)
 void launch_wmesh_faces(const WMeshGrid& g, long long ncell, const int* offs, int n_faces, const int* num, int first, const int* num_up, int first_up, int* faces, hipStream_t s);
 void launch_wmesh_verts(const WMeshGrid& g, const int* num, int n_verts, float* xyz, float* nrm, unsigned char* rgb, hipStream_t s);
+
+// ---- photometric fit per band row and per welded-mesh vertex (fit.hip; include/psgsdf_fit.h, DESIGN.md "Photometric fit per voxel and vertex")
+// per owned band row [row0, row1): the counted observations, k_energy's robust loss of the row, the sum of squared residuals per channel ([rows][3])
+void launch_band_fit(const SweepArgs& a, int* n_obs, double* loss, float* sum_r2, hipStream_t s);
+// per vertex (num: the scan of the used-key flags, as launch_wmesh_verts takes it; row_of: the dense voxel-to-row map): observations, rms residual, mean loss
+void launch_wmesh_fit(const WMeshGrid& g, const int* num, int n_verts, const int* row_of, int row0, int row1, const int* n_obs, const double* loss, const float* sum_r2,
+                      int* v_n, float* v_rms, float* v_loss, hipStream_t s);
 
 // ---- connected components of the welded mesh (mesh_cc.hip, psgsdf_extract_mesh_components; DESIGN.md "Mesh components").  Per component kMcompStats
 // 64-bit integers (stat[comp][MC_*], zeroed first; MC_AREA: the sum of llrint(2^24 A_f / vs^2)) and the bounding box as order-preserving unsigned

@@ -5,7 +5,7 @@
 //   api_frontend.hip  frame fusion, FALS normals, depth tracker        api_multi_gpu.hip  the z-slab phase API
 //   api_debug.hip     measurement and test hooks               api_render.hip     the C ABI of include/psgsdf_render.h
 //   extract.hip       mesh, point clouds, SDF block on the device (kernels and calls); extract_mesh.hip: the welded mesh, its components and
-//                     its level of detail (include/psgsdf_mesh.h); what the two share: extract_internal.h
+//                     its level of detail (include/psgsdf_mesh.h) and the photometric fit per band row and vertex (include/psgsdf_fit.h); what the two share: extract_internal.h
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"
@@ -36,9 +36,11 @@ enum XoSlot {
     XO_MESH_XYZ, XO_MESH_RGB,                                        // psgsdf_extract_mesh
     XO_PC_XYZN, XO_PC_RGB,                                           // psgsdf_extract_pointcloud
     XO_SDF,                                                          // psgsdf_extract_sdf
-    XO_IMESH_XYZ, XO_IMESH_NORMALS, XO_IMESH_RGB, XO_IMESH_FACES,    // psgsdf_extract_mesh_indexed, _components and _lod: each call's own mesh
+    XO_IMESH_XYZ, XO_IMESH_NORMALS, XO_IMESH_RGB, XO_IMESH_FACES,    // psgsdf_extract_mesh_indexed, _components, _lod and _fit: each call's own mesh
     XO_VERTEX_COMPONENT, XO_COMPONENTS,                              // psgsdf_extract_mesh_components (the list also when _lod filters)
     XO_LOD_VERTEX_MAP,                                               // psgsdf_extract_mesh_lod
+    XO_FIT_NOBS, XO_FIT_LOSS, XO_FIT_R2,                             // psgsdf_band_fit
+    XO_VFIT_NOBS, XO_VFIT_RMS, XO_VFIT_LOSS,                         // psgsdf_extract_mesh_fit (its mesh: XO_IMESH_*)
     XO_COUNT
 };
 }  // namespace psge

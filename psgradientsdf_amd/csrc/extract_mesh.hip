@@ -1,12 +1,14 @@
 // extract_mesh.hip -- the C ABI of include/psgsdf_mesh.h: the welded, indexed mesh of the context's state (kernels: mesh.hip; DESIGN.md "Welded
 // meshes"), its connected components and the mesh without its small pieces (mesh_cc.hip; "Mesh components") and a level-of-detail mesh by vertex
-// clustering (mesh_lod.hip; "Level of detail").  Each call is a chain of stages -- welded mesh -> components -> clusters -- that hand each other
-// device arrays whose kernels may still be in flight.  The CALL owns all device memory of its stages in one DevMem, which waits for the stream and
-// frees when the call returns, whichever way it returns: a stage allocates from it and never frees.
+// clustering (mesh_lod.hip; "Level of detail"); and the C ABI of include/psgsdf_fit.h: the photometric fit per band row and per vertex of the welded
+// mesh (fit.hip; "Photometric fit per voxel and vertex").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
+// welded mesh -> vertex fit -- that hand each other device arrays whose kernels may still be in flight.  The CALL owns all device memory of its
+// stages in one DevMem, which waits for the stream and frees when the call returns, whichever way it returns: a stage allocates from it and never frees.
 // The frame arithmetic (extract_internal.h crop_frame) runs on the host and its results are compared bit for bit: no FMA contraction here either.
 #pragma clang fp contract(off)
 #include "extract_internal.h"
 #include "../../include/psgsdf_mesh.h"
+#include "../../include/psgsdf_fit.h"
 #include "mesh_lod.h"
 
 using namespace psge;
@@ -16,7 +18,7 @@ namespace {
 struct MeshView { const float *xyz = nullptr, *nrm = nullptr; const unsigned char* rgb = nullptr; const int* faces = nullptr; int nv = 0, nf = 0; };
 
 // ---- stage 1: the welded mesh of the context's state (this rank's share).  nv == 0 && nf == 0: nothing was launched for it
-struct WMeshDev : MeshView { long long first = 0; };
+struct WMeshDev : MeshView { long long first = 0; psg::WMeshGrid grid{}; const int* num = nullptr; };      // grid, num: the key slots and their vertex numbers (the scan of the used-key flags)
 int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m) {
     const char* me = "extract_mesh_indexed";
     int lo[3], hi[3]; bool any = false;
@@ -97,7 +99,7 @@ int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m) {
         return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d vertices, %d faces)", me, nv, nf);
     if (nf > 0) timed(c, "wmesh_faces", [&] { psg::launch_wmesh_faces(g, ncell, cnt, nf, flag, (int)first, xin ? xin + P : nullptr, (int)first_up, faces, c->stream); });
     if (nv > 0) timed(c, "wmesh_verts", [&] { psg::launch_wmesh_verts(g, flag, nv, xyz, nrm, rgb, c->stream); });
-    m->xyz = xyz; m->nrm = nrm; m->rgb = rgb; m->faces = faces;
+    m->xyz = xyz; m->nrm = nrm; m->rgb = rgb; m->faces = faces; m->grid = g; m->num = flag;
     return PSGSDF_OK;
 }
 }  // namespace
@@ -292,4 +294,63 @@ extern "C" int psgsdf_extract_mesh_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* 
     }
     if (in.nv > 0 && in.nf > 0) return lod_from_device(c, mem, in, cell, LodOut{xyz, normals, rgb, n_vertices, faces, n_faces, vertex_map, n_vertices_in, n_faces_in});
     return hipStreamSynchronize(c->stream) != hipSuccess ? fail(c, PSGSDF_ERR_DEVICE, "%s: kernels", me) : PSGSDF_OK;
+}
+
+namespace {
+// ---- the photometric fit of this context's band rows [row0, row1) (fit.hip k_band_fit); n == 0: nothing was launched
+struct BFitDev { const int* n_obs = nullptr; const double* loss = nullptr; const float* r2 = nullptr; int n = 0; };
+int bfit_device(psgsdf_ctx* c, DevMem& mem, const char* me, BFitDev* d) {
+    const int n = c->row1 - c->row0;
+    if (n <= 0) return PSGSDF_OK;
+    int* n_obs = nullptr; double* loss = nullptr; float* r2 = nullptr;      // temporaries: 24 B per band row
+    if (!mem.get(&n_obs, (size_t)n) || !mem.get(&loss, (size_t)n) || !mem.get(&r2, 3 * (size_t)n)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d band rows)", me, n);
+    const SweepArgs a = make_args(c, 0);      // (fold.n = 0: the kernel takes no pending fold; it writes no partial slot either)
+    timed(c, "band_fit", [&] { psg::launch_band_fit(a, n_obs, loss, r2, c->stream); });
+    d->n_obs = n_obs; d->loss = loss; d->r2 = r2; d->n = n;
+    return PSGSDF_OK;
+}
+// what both calls check first: no rank waits for another, nothing has touched the device
+int fit_ready(psgsdf_ctx* c, const char* me) {
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): the fit is not gathered across z-slabs", me, c->rank, c->n_ranks);
+    if (!c || !c->inited) return fail(c, PSGSDF_ERR_STATE, "%s: psgsdf_init first (no band)", me);
+    return extract_ready(c, me);      // the quiescent point of the extraction calls: pending read-backs delivered
+}
+}  // namespace
+
+extern "C" int psgsdf_band_fit(psgsdf_ctx* c, const int32_t** n_obs, const double** loss, const float** sum_r2, int64_t* n_band) {
+    const char* me = "band_fit";
+    if (!n_obs || !loss || !sum_r2 || !n_band) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    { int rc = fit_ready(c, me); if (rc) return rc; }
+    *n_obs = nullptr; *loss = nullptr; *sum_r2 = nullptr; *n_band = 0;
+    DevMem mem(c);
+    BFitDev d;
+    if (int rc = bfit_device(c, mem, me, &d)) return rc;
+    const size_t n = (size_t)d.n;
+    if (int rc = download(c, me, {{XO_FIT_NOBS, d.n_obs, sizeof(int) * n, n_obs}, {XO_FIT_LOSS, d.loss, sizeof(double) * n, loss}, {XO_FIT_R2, d.r2, sizeof(float) * 3 * n, sum_r2}})) return rc;
+    *n_band = d.n;
+    return PSGSDF_OK;
+}
+
+extern "C" int psgsdf_extract_mesh_fit(psgsdf_ctx* c, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices, const int32_t** faces, int64_t* n_faces,
+                                       const int32_t** vertex_n_obs, const float** vertex_rms, const float** vertex_loss) {
+    const char* me = "extract_mesh_fit";
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_n_obs || !vertex_rms || !vertex_loss) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    { int rc = fit_ready(c, me); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_n_obs = nullptr; *vertex_rms = nullptr; *vertex_loss = nullptr; *n_vertices = 0; *n_faces = 0;
+    DevMem mem(c);
+    BFitDev d;
+    if (int rc = bfit_device(c, mem, me, &d)) return rc;
+    WMeshDev m;
+    if (int rc = wmesh_device(c, mem, &m)) return rc;
+    const size_t nv = (size_t)m.nv, nf = (size_t)m.nf;
+    int* v_n = nullptr; float *v_rms = nullptr, *v_loss = nullptr;      // temporaries: 12 B per vertex
+    if (nv > 0) {
+        if (!mem.get(&v_n, nv) || !mem.get(&v_rms, nv) || !mem.get(&v_loss, nv)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d vertices)", me, m.nv);
+        timed(c, "wmesh_fit", [&] { psg::launch_wmesh_fit(m.grid, m.num, m.nv, c->dense.row_of, c->row0, c->row1, d.n_obs, d.loss, d.r2, v_n, v_rms, v_loss, c->stream); });
+    }
+    if (int rc = download(c, me, {{XO_IMESH_XYZ, m.xyz, sizeof(float) * 3 * nv, xyz}, {XO_IMESH_NORMALS, m.nrm, sizeof(float) * 3 * nv, normals}, {XO_IMESH_RGB, m.rgb, 3 * nv, rgb},
+                                  {XO_IMESH_FACES, m.faces, sizeof(int) * 3 * nf, faces}, {XO_VFIT_NOBS, v_n, sizeof(int) * nv, vertex_n_obs}, {XO_VFIT_RMS, v_rms, sizeof(float) * nv, vertex_rms},
+                                  {XO_VFIT_LOSS, v_loss, sizeof(float) * nv, vertex_loss}})) return rc;
+    *n_vertices = m.nv; *n_faces = m.nf;
+    return PSGSDF_OK;
 }

@@ -36,6 +36,7 @@
 #include "../../include/psgsdf.h"
 #include "../../include/psgsdf_render.h"
 #include "../../include/psgsdf_mesh.h"
+#include "../../include/psgsdf_fit.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 
@@ -100,6 +101,9 @@ inline psgsdf_mesh_filter& mesh_filter() { static psgsdf_mesh_filter f{0, 0.0, 0
 // voxelPS --mesh-lod S: next to every <name>_mesh.ply a <name>_mesh_lod.ply, the welded mesh (the filtered one, if a filter flag is given) with the vertices
 // of every cube of S voxels merged into one (psgsdf_extract_mesh_lod); 0: off; single process only
 inline double& mesh_lod_voxels() { static double v = 0.0; return v; }
+// voxelPS --mesh-fit: next to every <name>_mesh.ply a <name>_mesh_fit.ply, the welded mesh with the photometric fit of every vertex (psgsdf_extract_mesh_fit): how many
+// keyframes saw it, the rms residual and the mean robust loss; single process only
+inline bool& mesh_fit() { static bool v = false; return v; }
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
 inline bool& skip_sync_back() { static bool v = false; return v; }      // voxelPS --host-writers: round 4's path (dense download, host marching cubes, iostream): the cross-check
@@ -206,12 +210,13 @@ inline bool write_mesh_ply(const std::string& file, const float* xyz, const uint
 // face records a uchar 3 and three int vertex indices, 13 B.  Coordinates are grid-local like every other writer's: the comment line holds the
 // grid origin and the voxel size (world = origin + the position).  No reference counterpart: `voxelPS --indexed-mesh`.
 constexpr size_t kPlyVertexBytes = 27, kPlyFaceBytes = 13;
-inline std::string mesh_indexed_header(size_t nv, size_t nf, const float origin[3], float vs, const std::string& extra = std::string()) {      // extra: further header lines (each ends in \n)
+inline std::string mesh_indexed_header(size_t nv, size_t nf, const float origin[3], float vs, const std::string& extra = std::string(),      // extra: further header lines (each ends in \n)
+                                       const std::string& vertex_props = std::string()) {                                                     // vertex_props: further vertex property lines, behind the colours
     char c[160];
     snprintf(c, sizeof c, "comment grid origin %.9g %.9g %.9g voxel size %.9g\n", (double)origin[0], (double)origin[1], (double)origin[2], (double)vs);
     return std::string("ply\nformat binary_little_endian 1.0\n") + c + extra + "element vertex " + std::to_string(nv) + "\n"
            "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
-           "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+           "property uchar red\nproperty uchar green\nproperty uchar blue\n" + vertex_props +
            "element face " + std::to_string(nf) + "\nproperty list uchar int vertex_indices\nend_header\n";
 }
 inline std::string mesh_indexed_vertices(const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv) {
@@ -228,6 +233,27 @@ inline bool write_mesh_indexed_ply(const std::string& file, const float* xyz, co
                                    const float origin[3], float vs, const std::string& extra = std::string()) {
     FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
     const std::string h = mesh_indexed_header(nv, nf, origin, vs, extra), v = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
+    return fclose(f) == 0 && ok;
+}
+// the welded mesh with the fit of its vertices (include/psgsdf_fit.h): the format above with three more vertex properties behind the colours -- float quality
+// (the rms residual), float loss (the mean robust loss), int n_obs -- 39 B per vertex, and one more header line with the overall rms residual (the
+// root of the n_obs-weighted mean of quality^2, in double from the columns as written) and the sum of n_obs.  `voxelPS --mesh-fit`.
+constexpr size_t kPlyFitVertexBytes = kPlyVertexBytes + 12;
+inline std::string mesh_fit_comment(const float* rms, const int32_t* n_obs, size_t nv) {
+    double q = 0.0; long long n = 0;
+    for (size_t i = 0; i < nv; ++i) { q += (double)n_obs[i] * ((double)rms[i] * (double)rms[i]); n += n_obs[i]; }
+    char c[120];
+    snprintf(c, sizeof c, "comment fit rms %.17g observations %lld\n", n ? std::sqrt(q / (double)n) : 0.0, n);
+    return c;
+}
+inline bool write_mesh_fit_ply(const std::string& file, const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv, const int32_t* faces, size_t nf,
+                               const float origin[3], float vs, const float* rms, const float* loss, const int32_t* n_obs) {
+    FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
+    const std::string h = mesh_indexed_header(nv, nf, origin, vs, mesh_fit_comment(rms, n_obs, nv), "property float quality\nproperty float loss\nproperty int n_obs\n");
+    const std::string base = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    std::string v(nv * kPlyFitVertexBytes, '\0'); char* p = &v[0];
+    for (size_t i = 0; i < nv; ++i, p += kPlyFitVertexBytes) { memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes); memcpy(p + 27, rms + i, 4); memcpy(p + 31, loss + i, 4); memcpy(p + 35, n_obs + i, 4); }
     bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
     return fclose(f) == 0 && ok;
 }
@@ -409,6 +435,7 @@ struct VolumetricGradSdf {
         if (ctx && indexed_mesh() && !device_mesh_indexed(ctx, filename)) std::cout << "couldn't save the indexed mesh of " << filename << std::endl;
         if (ctx && clean_mesh() && !device_mesh_clean(ctx, filename)) std::cout << "couldn't save the cleaned mesh of " << filename << std::endl;
         if (ctx && mesh_lod_voxels() > 0 && !device_mesh_lod(ctx, filename)) std::cout << "couldn't save the level-of-detail mesh of " << filename << std::endl;
+        if (ctx && mesh_fit() && !device_mesh_fit(ctx, filename)) std::cout << "couldn't save the mesh with its fit of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
     }
@@ -502,6 +529,31 @@ struct VolumetricGradSdf {
         DumpQueue::get().push([=] {
             if (!write_mesh_indexed_ply(base + "_mesh_lod.ply", vx->data(), vn->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, extra)) {
                 std::cout << "couldn't save the level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure();
+            }
+        });
+        return true;
+    }
+    // <name>_mesh.ply -> <name>_mesh_fit.ply (write_mesh_fit_ply).  Before psgsdf_init there is no band: the mesh of psgsdf_extract_mesh_indexed with zeros
+    static bool device_mesh_fit(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: welded mesh with vertex fit (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string base = mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                 ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file;
+        const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr;
+        const int32_t* vn_obs = nullptr; const float* vrms = nullptr; const float* vloss = nullptr; int64_t nv = 0, nf = 0, first = 0;
+        const int rc = psgsdf_extract_mesh_fit(ctx, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vn_obs, &vrms, &vloss);
+        if (rc == PSGSDF_ERR_STATE) { if (psgsdf_extract_mesh_indexed(ctx, &xyz, &nrm, &rgb, &nv, &faces, &nf, &first) != 0) return false; }
+        else if (rc != 0) return false;
+        if (nf == 0) return false;
+        auto vx = std::make_shared<std::vector<float>>(xyz, xyz + 3 * nv), vnr = std::make_shared<std::vector<float>>(nrm, nrm + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(rgb, rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(faces, faces + 3 * nf);
+        auto fr = std::make_shared<std::vector<float>>((size_t)nv, 0.0f), fl = std::make_shared<std::vector<float>>((size_t)nv, 0.0f); auto fn = std::make_shared<std::vector<int32_t>>((size_t)nv, 0);
+        if (rc == 0) { fr->assign(vrms, vrms + nv); fl->assign(vloss, vloss + nv); fn->assign(vn_obs, vn_obs + nv); }
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            if (!write_mesh_fit_ply(base + "_mesh_fit.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, fr->data(), fl->data(), fn->data())) {
+                std::cout << "couldn't save the mesh with its fit " << base << std::endl; DumpQueue::get().report_failure();
             }
         });
         return true;
@@ -903,6 +955,7 @@ public:
         if (indexed_mesh() && !VolumetricGradSdf::device_mesh_indexed(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the indexed mesh " << save_path_ << filename << std::endl;
         if (clean_mesh() && !VolumetricGradSdf::device_mesh_clean(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the cleaned mesh " << save_path_ << filename << std::endl;
         if (mesh_lod_voxels() > 0 && !VolumetricGradSdf::device_mesh_lod(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the level-of-detail mesh " << save_path_ << filename << std::endl;
+        if (mesh_fit() && !VolumetricGradSdf::device_mesh_fit(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the mesh with its fit " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");
             if (!ok) std::cout << "couldn't save mesh " << save_path_ << filename << std::endl;

@@ -117,6 +117,19 @@ static int selftest_ply_indexed(const char* path) {
     return psgsdf_host::write_mesh_indexed_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f) ? 0 : 1;
 }
 
+// `--selftest-ply-fit out.ply`: the same octahedron through the writer of `--mesh-fit` (three more vertex properties, one more header line;
+// tests/test_fit_cpu.py parses it back)
+static int selftest_ply_fit(const char* path) {
+    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
+    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
+    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
+    const float origin[3] = {-0.25f, 0.5f, 1.0f};
+    const float rms[6] = {0.125f, 0.03125f, 0.0f, 0.25f, 0.0625f, 0.5f}, loss[6] = {0.75f, 0.01f, 0.0f, 1.5f, 0.02f, 2.25f};
+    const int32_t n_obs[6] = {3, 8, 0, 1, 16, 2};
+    return psgsdf_host::write_mesh_fit_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, rms, loss, n_obs) ? 0 : 1;
+}
+
 // the focus measure of one colour PNG as the keyframe selector computes it (SharpDetector.h:22-37), and the keyframe sub-sampling of
 // main_ps.cpp:392-421 on the index list 0..n-1: tests/test_host_tools.py compares both with numpy / scipy restatements (no GPU needed)
 static int selftest_lapm(const char* path) {
@@ -221,6 +234,7 @@ int main(int argc, char* argv[]) {
     if (argc >= 2 && std::string(argv[1]) == "--selftest-mc-generated") return selftest_mc_table(true);
     if (argc >= 4 && std::string(argv[1]) == "--selftest-mc-ply") return selftest_mc_ply(atoi(argv[2]), argv[3]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-fit") return selftest_ply_fit(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
     std::string filter_flag;                  // the last of --mesh-min-faces / --mesh-keep-largest given
@@ -234,6 +248,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-min-faces" && i + 1 < argc) { mesh_filter().min_faces = atoll(argv[++i]); clean_mesh() = true; filter_flag = a; }      // <name>_mesh_clean.ply + <name>_mesh_components.txt next to every <name>_mesh.ply:
         else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
         else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_lod_voxels() = lod_ok ? v : 0.0; lod_flag = true; }      // <name>_mesh_lod.ply next to every <name>_mesh.ply: the vertices of every cube of S voxels merged (include/psgsdf_mesh.h psgsdf_extract_mesh_lod)
+        else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
@@ -246,6 +261,7 @@ int main(int argc, char* argv[]) {
     if ((want_ranks > 1 || multi_rank()) && clean_mesh()) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && lod_flag) { std::cerr << "--mesh-lod needs a single process: clusters are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && mesh_fit()) { std::cerr << "--mesh-fit needs a single process: the fit is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
     if (want_ranks > 1 && !multi_rank()) return launch_ranks(want_ranks, transport == "sockets", argc, argv);
     static std::ofstream null_out;
