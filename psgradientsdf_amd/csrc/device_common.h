@@ -258,17 +258,19 @@ __device__ __forceinline__ void block_part_store(double v, double* part_slot, do
         part_slot[bid >= 0 ? bid : (int)blockIdx.x] = s;
     }
 }
-// sum of n partials, identical in every thread of every block (fixed order)
+// sum of n partials, identical in every thread of every block (fixed order).  NT != 0: only the first NT threads of a LARGER workgroup sum -- the order,
+// and so the bits, of a workgroup of NT threads (all threads must call; red holds NT / 64 doubles)
+template <int NT = 0>
 __device__ __forceinline__ double block_total(const double* part, int n, double* red) {
     double v = 0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) v += part[i];
+    if (!NT || threadIdx.x < NT) for (int i = threadIdx.x; i < n; i += NT ? NT : blockDim.x) v += part[i];
     v = wave_sum(v);
     int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     __syncthreads();
-    if (lane == 0) red[w] = v;
+    if (lane == 0 && (!NT || w < NT / 64)) red[w] = v;
     __syncthreads();
     double s = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
+    for (int i = 0; i < (int)((NT ? NT : blockDim.x) >> 6); ++i) s += red[i];
     return s;
 }
 // Workgroups are dealt to the 8 XCDs round-robin in dispatch order (physical id mod 8).  xcd_remap turns the physical id into a LOGICAL one such that
@@ -349,10 +351,12 @@ __device__ __forceinline__ void fold_exchange(const XfTable* xf, long long epoch
 }
 // a.fold: sum the partial slots the PREVIOUS kernel left behind (first workgroup only; all its threads must call).
 // The calling kernel must not write the folded slots itself (engine.hip: take_fold checks).
+// NT = kBlock from a workgroup of more than kBlock threads (the persistent solves, pcg.hip): the sums of the kBlock-thread kernels, to the bit.
+template <int NT = 0>
 __device__ __forceinline__ void fold_pending(const SweepArgs& a, double* red /*[kBlock/64]*/) {
     if (a.fold.n == 0 || blockIdx.x != 0 || blockIdx.y != 0) return;
     double t[4];
-    for (int s = 0; s < a.fold.n; ++s) t[s] = block_total(PART(a, a.fold.id[s]), a.fold.nblk, red);
+    for (int s = 0; s < a.fold.n; ++s) t[s] = block_total<NT>(PART(a, a.fold.id[s]), a.fold.nblk, red);
     if (threadIdx.x < 64) {      // (the exchange between the ranks takes the whole first wavefront)
         if (a.fold.xf) fold_exchange(a.fold.xf, a.fold.xf_epoch, a.fold.n, t);
         if (threadIdx.x == 0) {

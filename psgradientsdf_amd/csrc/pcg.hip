@@ -417,6 +417,211 @@ __device__ __forceinline__ void assemble_row_regs(const SweepArgs& a, int i, dou
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// What the two persistent kernels share (k_cgf_solve: the classic recurrences; k_cgp_solve: the pipelined ones, production): the workgroup's place in
+// the band and in the slab, every bounded wait of the hand-off protocol with its abort path, the assembly of a thread's rows, the
+// distance update of the epilogue and the outcome the host reads.  The kernels differ in the recurrences, in what travels and in the barrier scheme --
+// and, as far as this code is concerned, in four parameters: the pass index of the prologue round, the LDS word that carries 'a wait gave up', the
+// buffer a stage sums in, and the number of sums.
+// ------------------------------------------------------------------------------------------
+constexpr int kXrSpins = 1 << 24;            // bound of every wait for another RANK (~1 s)
+// stage timestamps of pass 8 (timing hook only: force_passes > 0), wall clock at 100 MHz, written by thread 0 of two workgroups
+#define SOLVE_STAMP(j) do { if (force_passes > 0 && k == 8 && tid == 0 && (lb == 0 || lb == (G * 9) / 16)) mb[8 + (lb ? 8 : 0) + (j)] = (double)wall_clock64(); } while (0)
+
+template <bool MR> struct SolveWg {
+    static constexpr int kLocalSpins = MR ? kXrSpins : (1 << 22);      // MR: a local neighbour may itself be waiting for a late RANK -- the local waits must not expire first
+    const SweepArgs& a; const XrArgs& xr; double* const fs; double* const gran; const int rows_per_wg;
+    const int G = gridDim.x, tid = threadIdx.x;
+    // The XCD this workgroup REALLY runs on (HW_REG_XCC_ID): if every workgroup that gathers from its rows sits on the same XCD, its records can stay
+    // in that XCD's L2 (plain stores) instead of going through memory with write-through stores, which drop the line and make every reader fetch it at the
+    // cross-XCD rate (MI355X_MICROARCH.md: same-XCD hand-offs 1.7x; r02 notes section 8 measured 9.5-9.6 vs 9.9-10.5 us per pass but would not rely on an
+    // ASSUMED placement).  Here the neighbours tell each other where they are: the 'records are out' flag of the prologue carries 1 + the XCD id.
+    const int my_xcc = (int)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));
+    // XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs; logical block lb gives XCD x the contiguous blocks [x G/8, (x+1) G/8)
+    const int lb = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+    // MR: which of this workgroup's rows the neighbours hold as halo, and whose tags it has to wait for
+    const int own_n = a.row1 - a.row0;
+    const int wg_first = lb * rows_per_wg, wg_last = min(own_n, wg_first + rows_per_wg) - 1;      // (relative to row0)
+    const bool cut_lo = MR && xr.give_lo > 0 && wg_first < xr.give_lo && wg_first < own_n;          // owns rows of the lower neighbour's upper halo
+    const bool cut_hi = MR && xr.give_hi > 0 && wg_last >= own_n - xr.give_hi && wg_first < own_n;
+    const int hi_first_wg = MR ? max(0, own_n - xr.give_hi) / rows_per_wg : 0;                      // first workgroup that owns such rows
+    double* const xr_me = MR ? xr.region[xr.rank] : nullptr;
+    const unsigned etag0 = MR ? (xr.epoch & kXrEpochMask) << 2 : 0u;      // cross-rank tags: (epoch << 2 | pass tag)
+    // The workgroups whose records this one gathers from: rows within `reach` of its own range (a handful of neighbours in band order) ...
+    const int nlo = max(0, (wg_first - a.b.reach) / rows_per_wg), nhi = min(G - 1, (wg_first + rows_per_wg - 1 + a.b.reach) / rows_per_wg);
+    // ... and, MR, the neighbour slabs: rows within `reach` of a cut gather from halo rows
+    const bool need_lo = MR && xr.need_lo > 0 && wg_first < a.b.reach, need_hi = MR && xr.need_hi > 0 && wg_last + a.b.reach >= own_n;
+
+    __device__ __forceinline__ SolveWg(const SweepArgs& a_, const XrArgs& xr_, double* fs_, double* gran_, int rows_per_wg_) : a(a_), xr(xr_), fs(fs_), gran(gran_), rows_per_wg(rows_per_wg_) {}
+
+    // row slot u of this thread.  The band is dealt evenly to ALL workgroups (rows_per_wg each, a multiple of 64): the last row slot of a thread is only
+    // partly used; a slot without a row works on the last own row and stores nothing
+    __device__ __forceinline__ int own_row(int u, bool& live) const {
+        const int i = a.row0 + lb * rows_per_wg + u * kSolveThreads + tid;
+        live = u * kSolveThreads + tid < rows_per_wg && i < a.row1;
+        return live ? i : a.row1 - 1;
+    }
+    __device__ __forceinline__ double* gran_plane(int buf, int q) const { return gran + ((size_t)buf * kSolveGranPlanes + q) * kSolveMaxBlocks; }
+    // the neighbour's mailbox slots this workgroup tags: it is the (lb)-th cut-side workgroup towards the lower neighbour, the (lb - hi_first_wg)-th towards the upper one
+    __device__ __forceinline__ void peer_tag(int buf, unsigned pass_tag) const {
+        const double v = xr_tag(1.0, etag0 | pass_tag);
+        if (cut_lo && lb < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank - 1] + kXrPtag + (1 * 3 + buf) * kXrPeerTags + lb, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);              // (side 1 of the lower rank = tags of its UPPER neighbour)
+        if (cut_hi && lb - hi_first_wg < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank + 1] + kXrPtag + (0 * 3 + buf) * kXrPeerTags + (lb - hi_first_wg), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    // 'a wait gave up': here and in every rank's region, so that every workgroup of every rank leaves
+    __device__ __forceinline__ void raise_abort() const {
+        __hip_atomic_store(fs + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (MR) for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrAbort, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __device__ __forceinline__ bool aborted() const { return __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0; }
+    __device__ __forceinline__ bool aborted_by_rank() const { return aborted() || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0; }
+    // Prologue (thread 0, behind the barrier that follows the drain of the workgroup's first stores): the flag the neighbours' first round waits for
+    // (plane 7 of buffer 1) carries 1 + the XCD id; tag_peers: the same news for the neighbour slabs (pass tag 1 in buffer 2)
+    __device__ __forceinline__ void publish_prologue(bool tag_peers) const {
+        __hip_atomic_store(gran_plane(1, 7) + lb, (double)(1 + my_xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (MR && tag_peers) peer_tag(2, 1u);
+    }
+    // Stage A, local: the records this workgroup gathers from are those of its NEIGHBOURS in band order: thread j waits for the tag of neighbour nlo + j
+    // (the tag of a workgroup's first sum of buffer pb is stored after its records have drained; prologue: its flag), not for the whole device.
+    // *foreign = 1 if a neighbour sits on another XCD (the relation is symmetric: whoever gathers from this workgroup is in [nlo, nhi])
+    __device__ __forceinline__ void wait_band_neighbours(bool prologue, int pb, unsigned want, int* abort_word, int* foreign) const {
+        if (tid > nhi - nlo) return;
+        int spins = 0;
+        const double* wp = (prologue ? gran_plane(1, 7) : gran_plane(pb, 0)) + nlo + tid;
+        double seen = 0.0;
+        while (prologue ? (seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0.0 : gran_tag_of(seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != want) {
+            __builtin_amdgcn_s_sleep(1);
+            if (++spins > kLocalSpins || aborted()) { *abort_word = 1; break; }
+        }
+        if (prologue && (int)seen != 1 + my_xcc) *foreign = 1;
+    }
+    // Stage A, MR: wait for the tags the neighbour slab's cut-side workgroups wrote into this rank's region after their records had drained
+    // (kXrPeerTags = 64 slots per side: threads 64..127 / 128..191 -- wavefronts 1 and 2, next to the local pollers in wavefront 0)
+    __device__ __forceinline__ void wait_peer_tags(bool prologue, int pb, unsigned want, int* abort_word) const {
+        const int side = tid >= 128 ? 1 : 0, j = tid - (side ? 128 : 64);
+        if (!MR || tid < 64 || tid >= 192 || j >= (side ? xr.wait_hi : xr.wait_lo) || !(side ? need_hi : need_lo)) return;
+        int spins = 0;
+        const double* wp = xr_me + kXrPtag + (side * 3 + (prologue ? 2 : pb)) * kXrPeerTags + j;
+        const unsigned wantx = etag0 | (prologue ? 1u : want);
+        while (xr_tag_of(__hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != wantx) {
+            __builtin_amdgcn_s_sleep(1);
+            if (++spins > kXrSpins || aborted_by_rank()) { *abort_word = 1; break; }
+        }
+    }
+    // Stage A, end (all threads): false = a wait gave up and the abort flag is raised; else the records are visible to this workgroup
+    // (MR: system scope -- the halo records came from another GPU).  The caller's next barrier publishes the acquire to the other wavefronts.
+    __device__ __forceinline__ bool neighbours_acquired(const int* abort_word) const {
+        __syncthreads();
+        if (*abort_word) { if (tid == 0) raise_abort(); return false; }
+        if (tid == 0) { if (MR) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+        return true;
+    }
+    // Stage C2 (MR): t[0..n) are this RANK's sums (every local workgroup holds the same bits).  Workgroup 0 hands them to every rank as tagged granules of
+    // buffer pb; every workgroup then adds the granules of its own region in rank order (one fixed tree: the same bits on every rank) -- all <= 32 of them
+    // sit in wavefront 0.  false = a wait gave up.  The caller's next barrier protects `red`.
+    template <int N> __device__ __forceinline__ bool exchange_rank_sums(double (&t)[N], int n, int pb, unsigned want, double* red /*[8 * kSolveThreads / 64]*/, int* abort_word) const {
+        static_assert(N <= 8, "eight granule planes per buffer");
+        if (lb == 0 && tid < n) {
+            const double mine = xr_tag(t[tid], etag0 | want);
+            for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrRankGran + (pb * 8 + tid) * kXrMaxRanks + xr.rank, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        double rv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) rv[q] = 0.0;
+        if (tid < xr.n_ranks) {
+            int spins = 0; bool ok = false;
+            while (!ok) {
+                ok = true;
+#pragma unroll
+                for (int q = 0; q < N; ++q) if (q < n) { rv[q] = __hip_atomic_load(xr_me + kXrRankGran + (pb * 8 + q) * kXrMaxRanks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); ok = ok && xr_tag_of(rv[q]) == (etag0 | want); }
+                if (!ok) {
+                    __builtin_amdgcn_s_sleep(1);
+                    if (++spins > kXrSpins || aborted_by_rank()) { *abort_word = 1; break; }
+                }
+            }
+        }
+        double r0, r1; wave_sum8(rv, r0, r1);
+        wave_sum8_store<kSolveThreads / 64>(r0, r1, red, tid >> 6);
+        __syncthreads();
+        if (*abort_word) { if (tid == 0) raise_abort(); return false; }
+#pragma unroll
+        for (int q = 0; q < N; ++q) if (q < n) t[q] = red[q * (kSolveThreads / 64)];
+        return true;
+    }
+};
+
+// One row of a thread, assembled straight from the voxel blocks of the distance sweep (no k_assemble, no H in memory): the 19 coefficients (the diagonal
+// damped) into the thread's LDS column hs_slot[q * kSolveThreads], the Jacobi weight and the right-hand side returned
+__device__ __forceinline__ void solve_assemble_row(const SweepArgs& a, int row, float* hs_slot, float& inv, double& rhs) {
+    double acc[kNQ];
+    assemble_row_regs(a, row, acc, rhs);
+#pragma unroll
+    for (int q = 0; q < kNQ; ++q) {
+        float hv = (float)acc[q];
+        if (q == 0 && a.damping != 0.0f) hv += a.damping * hv;
+        hs_slot[q * kSolveThreads] = hv;
+    }
+    float dg = (float)acc[0];
+    if (a.damping != 0.0f) dg += a.damping * dg;
+    inv = dg != 0.f ? 1.0f / dg : 1.0f;
+}
+// the 9 packed column words of a row (two 16-bit deltas each), kept in registers for the whole solve
+__device__ __forceinline__ void solve_load_columns(const Band& b, int row, unsigned (&cp)[(kNQ - 1) / 2]) {
+    const int plane = b.Spad * 4;
+    const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)b.colp, 0, (kNQ - 1) / 2 * plane, 0x00020000);
+#pragma unroll
+    for (int wd = 0; wd < (kNQ - 1) / 2; ++wd) cp[wd] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rC, row * 4, wd * plane, 0);
+}
+// (the packed column deltas are loop-invariant: given the chance, the compiler precomputes all 18 R gather addresses as 64-bit pairs
+// ahead of the loop and spills them -- an empty asm per word, once per pass, keeps the three-instruction address arithmetic inside the pass)
+template <int R> __device__ __forceinline__ void solve_keep_columns_packed(unsigned (&cp)[R][(kNQ - 1) / 2]) {
+#pragma unroll
+    for (int u = 0; u < R; ++u)
+#pragma unroll
+        for (int wd = 0; wd < (kNQ - 1) / 2; ++wd) asm volatile("" : "+v"(cp[u][wd]));
+}
+// Eigen's info() == Success for a solve that ran to its end, the host's rule (loop.hip: pcg_solve) -- every workgroup holds the same |r|^2 and |b|^2
+__device__ __forceinline__ bool solve_converged(int status, float rr_cur, float rhsNorm2) {
+    return status == 1 && (rhsNorm2 == 0.f || sqrt((double)rr_cur / (double)rhsNorm2) <= (double)FLT_EPSILON);
+}
+// Epilogue: x of the own rows and, if asked for, the distance update (k_apply_dist: updateDist's accept rule, OptimizerAux.cpp:162-188) under the rule
+// the host applies to the solve's outcome.  The accepted count is a sum of integers: the per-workgroup counts go to the first G entries of the slot,
+// the rest of the slot (k_apply_albedo's leftovers) is cleared.
+template <bool MR, int R>
+__device__ __forceinline__ void solve_apply_and_count(const SolveWg<MR>& wg, const float (&x)[R], const int (&row)[R], const bool (&live)[R], int status, float rr_cur, float rhsNorm2, double* red) {
+    const SweepArgs& a = wg.a; const Band& b = a.b;
+#pragma unroll
+    for (int u = 0; u < R; ++u) if (live[u]) b.x[row[u]] = x[u];
+    if (!a.pcg_apply) return;
+    const bool apply = status == 1 && (a.pcg_apply == 1 || solve_converged(status, rr_cur, rhsNorm2));
+    double cnt = 0;
+    if (apply) {
+#pragma unroll
+        for (int u = 0; u < R; ++u) if (live[u] && (double)fabsf(x[u]) < sqrt(3.0) * (double)a.grid.vs) { b.dist[row[u]] -= x[u]; cnt += 1.0; }
+    }
+    cnt = wave_sum(cnt);
+    __syncthreads();
+    if ((wg.tid & 63) == 0) red[wg.tid >> 6] = cnt;
+    __syncthreads();
+    double* slot = PART(a, SC_ACCEPT);
+    if (wg.tid == 0) { double t = 0; for (int i = 0; i < kSolveThreads / 64; ++i) t += red[i]; slot[wg.lb] = t; }
+    for (int i = wg.G + wg.lb * kSolveThreads + wg.tid; i < a.acc.PB; i += wg.G * kSolveThreads) slot[i] = 0.0;
+}
+// The outcome for the host and for the gated kernels behind the solve (ONE thread of the grid).  status 1 = finished, 2 = a wait timed out: a solve
+// that gave up leaves BOTH gates closed -- nothing behind it may act on it (the host re-runs the solve, loop.hip)
+__device__ __forceinline__ void solve_report(double* fs, double* mb, unsigned long long mb_key, int status, int k, float rr_cur, float rhsNorm2, float thr) {
+    int iters = 0;
+    if (rhsNorm2 != 0.f && k > 0) iters = (rr_cur < thr) ? k - 1 : k;      // Eigen leaves the loop before ++i when it detects convergence; k == kmax otherwise
+    fs[1] = status == 1 ? (double)(k + 1) : 0.0; fs[2] = solve_converged(status, rr_cur, rhsNorm2) ? 1.0 : 0.0;
+    const double m0 = (double)iters, m1 = (double)rr_cur, m2 = (double)rhsNorm2, m3 = (double)status;
+    mb[0] = m0; mb[1] = m1; mb[2] = m2;
+    __threadfence_system();
+    mb[3] = m3;                            // the host watches this slot ...
+    // ... and takes the four words only together with their check word (engine.h FoldReq)
+    if (mb_key) reinterpret_cast<unsigned long long*>(mb)[4] = (unsigned long long)(__double_as_longlong(m0) ^ __double_as_longlong(m1) ^ __double_as_longlong(m2) ^ __double_as_longlong(m3)) ^ mb_key;
+    __threadfence_system();
+}
+
 // MR (multi-rank, z-slabs): the same kernel on every rank's slab, meeting the other ranks in two places.  (1) The records of the rows next to a cut
 // are ALSO written into the neighbour's halo rows (system-scope write-through stores through the IPC mapping), followed -- once the wave's stores
 // have drained -- by a tag in the neighbour's mailbox region; the neighbour's workgroups whose gathers reach across the cut wait for those tags
@@ -430,82 +635,28 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgf_solve(SweepArgs a, dou
     __shared__ int s_abort;
     __shared__ int s_foreign;      // a neighbour workgroup (in band order) runs on another XCD
     const Band& b = a.b;
-    const int G = gridDim.x, tid = threadIdx.x;
-    // The XCD this workgroup REALLY runs on (HW_REG_XCC_ID): if every workgroup that gathers from its rows sits on the same XCD, its records can stay
-    // in that XCD's L2 (plain stores) instead of going through memory with write-through stores, which drop the line and make every reader fetch it at the
-    // cross-XCD rate (MI355X_MICROARCH.md: same-XCD hand-offs 1.7x; r02 notes section 8 measured 9.5-9.6 vs 9.9-10.5 us per pass but would not rely on an
-    // ASSUMED placement).  Here the neighbours tell each other where they are: the 'records are out' flag of the prologue carries 1 + the XCD id.
-    const int my_xcc = (int)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));
+    const SolveWg<MR> wg(a, xr, fs, gran, rows_per_wg);
+    const int G = wg.G, tid = wg.tid, lb = wg.lb;
     bool xcd_local = false;
-    // XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs; logical block lb gives XCD x the contiguous blocks [x G/8, (x+1) G/8)
-    const int lb = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
     const int plane = b.Spad * 4;
     const __amdgpu_buffer_rsrc_t rH = __builtin_amdgcn_make_buffer_rsrc((void*)b.H, 0, kNQ * plane, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)b.colp, 0, (kNQ - 1) / 2 * plane, 0x00020000);
-    // MR: which of this workgroup's rows the neighbours hold as halo, and whose tags it has to wait for
-    const int own_n = a.row1 - a.row0;
-    const int wg_first = lb * rows_per_wg, wg_last = min(own_n, wg_first + rows_per_wg) - 1;      // (relative to row0)
-    const bool cut_lo = MR && xr.give_lo > 0 && wg_first < xr.give_lo && wg_first < own_n;          // owns rows of the lower neighbour's upper halo
-    const bool cut_hi = MR && xr.give_hi > 0 && wg_last >= own_n - xr.give_hi && wg_first < own_n;
-    const int hi_first_wg = MR ? max(0, own_n - xr.give_hi) / rows_per_wg : 0;                      // first workgroup that owns such rows
-    double* const xr_me = MR ? xr.region[xr.rank] : nullptr;
-    const unsigned etag0 = MR ? (xr.epoch & kXrEpochMask) << 2 : 0u;      // cross-rank tags: (epoch << 2 | pass tag)
-    constexpr int kLocalSpins = MR ? (1 << 24) : (1 << 22);               // MR: a local neighbour may itself be waiting for a late RANK -- the local waits must not expire first
-    // the neighbour's mailbox slots this workgroup tags: it is the (lb)-th cut-side workgroup towards the lower neighbour, the (lb - hi_first_wg)-th towards the upper one
-    auto peer_tag = [&](int buf, double v) {
-        if (cut_lo && lb < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank - 1] + kXrPtag + (1 * 3 + buf) * kXrPeerTags + lb, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);              // (side 1 of the lower rank = tags of its UPPER neighbour)
-        if (cut_hi && lb - hi_first_wg < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank + 1] + kXrPtag + (0 * 3 + buf) * kXrPeerTags + (lb - hi_first_wg), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    };
     auto push_record = [&](int buf, int rel, const float4& rec) {      // rel = row - row0
         if (MR && rel < xr.give_lo) store16_sys(xr.lo_rec[buf] + rel, rec);
-        if (MR && rel >= own_n - xr.give_hi) store16_sys(xr.hi_rec[buf] + (rel - (own_n - xr.give_hi)), rec);
+        if (MR && rel >= wg.own_n - xr.give_hi) store16_sys(xr.hi_rec[buf] + (rel - (wg.own_n - xr.give_hi)), rec);
     };
     // ---- once: the rows of this thread.  The 19 coefficients of a row live in LDS ([row slot][column][thread]: conflict-free, R x 38 KB of
     // the CU's 160 KB), the 9 index words and the row's own state in registers.
     float* hs = (float*)psg_dyn_smem;
     unsigned cp[R][(kNQ - 1) / 2]; float4 me[R]; float x[R]; int row[R]; bool live[R];
-    if (ASM && a.fold.n != 0 && blockIdx.x == 0) {
-        // no k_assemble in front of this kernel to fold the sums the distance sweep left pending (device_common.h fold_pending): done here,
-        // by the first 256 threads in that function's order (the same bits as in any 256-thread kernel)
-        double ftot[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int sl = 0; sl < a.fold.n; ++sl) {
-            const double* part = PART(a, a.fold.id[sl]);
-            double v = 0;
-            if (tid < kBlock) for (int i = tid; i < a.fold.nblk; i += kBlock) v += part[i];
-            v = wave_sum(v);
-            __syncthreads();
-            if ((tid & 63) == 0) red[tid >> 6] = v;
-            __syncthreads();
-            if (tid == 0) { double t = 0; for (int i = 0; i < kBlock / 64; ++i) t += red[i]; ftot[sl] = t; }
-        }
-        if (tid < 64) {      // (the exchange between the ranks takes the whole first wavefront; lane 0 holds the slab's sums)
-            if (a.fold.xf) fold_exchange(a.fold.xf, a.fold.xf_epoch, a.fold.n, ftot);      // multi-rank: the sums over all slabs
-            if (tid == 0) {
-                for (int sl = 0; sl < a.fold.n; ++sl) mbox_put(a.fold.out, a.fold.n, sl, ftot[sl], a.fold.key);
-                mbox_commit(a.fold.key);
-            }
-        }
-        __syncthreads();
-    }
+    if (ASM) fold_pending<kBlock>(a, red);      // (no k_assemble in front of this kernel to fold the sums the distance sweep left pending)
     double bb_thread = 0.0;                     // ASM: |b|^2 of this thread's rows (summed over the device with the sums of pass 0)
 #pragma unroll
     for (int u = 0; u < R; ++u) {
-        // the band is dealt evenly to ALL workgroups (rows_per_wg each, a multiple of 64): the last row slot of a thread is only partly used
-        const int i = a.row0 + lb * rows_per_wg + u * kSolveThreads + tid;
-        live[u] = u * kSolveThreads + tid < rows_per_wg && i < a.row1; row[u] = live[u] ? i : a.row1 - 1;
+        row[u] = wg.own_row(u, live[u]);
+        float* hs_slot = hs + (size_t)u * kNQ * kSolveThreads + tid;
         if (ASM) {
-            // the row's matrix entries straight from the voxel blocks of the distance sweep (no k_assemble, no H in memory)
-            double acc[kNQ], rhs;
-            assemble_row_regs(a, row[u], acc, rhs);
-#pragma unroll
-            for (int q = 0; q < kNQ; ++q) {
-                float hv = (float)acc[q];
-                if (q == 0 && a.damping != 0.0f) hv += a.damping * hv;
-                hs[(u * kNQ + q) * kSolveThreads + tid] = hv;
-            }
-            float dg = (float)acc[0];
-            if (a.damping != 0.0f) dg += a.damping * dg;
-            const float inv = dg != 0.f ? 1.0f / dg : 1.0f;
+            float inv; double rhs;
+            solve_assemble_row(a, row[u], hs_slot, inv, rhs);
             const float r = (float)rhs;
             me[u] = make_float4(r, 0.f, 0.f, inv);
             if (live[u]) { store16_sc1(b.rec[1] + row[u], me[u]); push_record(1, row[u] - a.row0, me[u]); bb_thread += (double)r * (double)r; }      // what pass 0 of the neighbours gathers
@@ -514,12 +665,11 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgf_solve(SweepArgs a, dou
             for (int q = 0; q < kNQ; ++q) {
                 float hv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rH, row[u] * 4, q * plane, 0));
                 if (q == 0 && a.damping != 0.0f) hv += a.damping * hv;
-                hs[(u * kNQ + q) * kSolveThreads + tid] = hv;
+                hs_slot[q * kSolveThreads] = hv;
             }
             me[u] = b.rec[1][row[u]];            // {r_0, 0, 0, inv} written by the assembly kernel
         }
-#pragma unroll
-        for (int wd = 0; wd < (kNQ - 1) / 2; ++wd) cp[u][wd] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rC, row[u] * 4, wd * plane, 0);
+        solve_load_columns(b, row[u], cp[u]);
         x[u] = 0.f;
     }
     // |b|^2: from the assembly kernel's per-workgroup partials (an earlier kernel: plain loads) -- or, ASM, not known before the sums of pass 0
@@ -535,65 +685,29 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgf_solve(SweepArgs a, dou
       for (int i = 0; i < kSolveThreads / 64; ++i) bb += red[i];
       __syncthreads();
     } else {
-        // the records of this workgroup's rows are on their way: drained, then the flag the neighbours' pass 0 waits for (plane 7 of buffer 1)
+        // the records of this workgroup's rows are on their way: drained, then the flag the neighbours' pass 0 waits for
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid == 0) { __hip_atomic_store(gran + (size_t)(kSolveGranPlanes + 7) * kSolveMaxBlocks + lb, (double)(1 + my_xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (MR) peer_tag(2, xr_tag(1.0, etag0 | 1u)); }
+        if (tid == 0) wg.publish_prologue(true);
     }
     float rhsNorm2 = (float)bb;
     float thr = pcg_threshold(rhsNorm2);
     float alpha_prev = 0.f, beta = 0.f, rr_cur = rhsNorm2;
     if (!ASM && lb == 0 && tid == 0) fs[0] = bb;
     int k = 0, status = 1;                    // status 1 = finished, 2 = a wait timed out
-    // The workgroups whose records this one gathers from: rows within `reach` of its own range (a handful of neighbours in band order).
-    const int first = lb * rows_per_wg, last = first + rows_per_wg - 1;                    // (relative to row0)
-    const int nlo = max(0, (first - b.reach) / rows_per_wg), nhi = min(G - 1, (last + b.reach) / rows_per_wg);
-    // stage timestamps of pass 8 (timing hook only: force_passes > 0), wall clock at 100 MHz, written by thread 0 of two workgroups
-#define SOLVE_STAMP(j) do { if (force_passes > 0 && k == 8 && tid == 0 && (lb == 0 || lb == (G * 9) / 16)) mb[8 + (lb ? 8 : 0) + (j)] = (double)wall_clock64(); } while (0)
     for (;; ++k) {
         SOLVE_STAMP(0);
         const unsigned want = (unsigned)k & 3u;            // tag of pass k-1 = ((k-1) + 1) & 3
-        const double* gp = gran + (size_t)((k - 1) & 1) * kSolveGranPlanes * kSolveMaxBlocks;
-        // (the packed column deltas are loop-invariant: given the chance, the compiler precomputes all 18 R gather addresses as 64-bit pairs
-        // ahead of the loop and spills them -- an empty asm per word keeps the three-instruction address arithmetic inside the pass)
-#pragma unroll
-        for (int u = 0; u < R; ++u)
-#pragma unroll
-            for (int wd = 0; wd < (kNQ - 1) / 2; ++wd) asm volatile("" : "+v"(cp[u][wd]));
+        const int pb = (k - 1) & 1;                        // the buffer pass k-1 published in
+        const double* gp = wg.gran_plane(pb, 0);
+        solve_keep_columns_packed<R>(cp);
         if (k > 0 || ASM) {
-            // ---- A: the records this workgroup gathers from are those of its NEIGHBOURS in band order: wait for their pass k-1 only (the tag
-            // of a workgroup's first sum is stored after its records have drained), not for the whole device
+            // ---- A: wait for the neighbours' pass k-1 (ASM, pass 0: for their assembled records)
             if (tid == 0) { s_abort = 0; if (ASM && k == 0) s_foreign = 0; }
             __syncthreads();
-            if (tid <= nhi - nlo) {
-                int spins = 0;
-                // (ASM, pass 0: the neighbours' assembled records -- their flag in plane 7 of buffer 1)
-                const double* wp = k > 0 ? gp + nlo + tid : gran + (size_t)(kSolveGranPlanes + 7) * kSolveMaxBlocks + nlo + tid;
-                double seen = 0.0;
-                while (k > 0 ? gran_tag_of(seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != want : (seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0.0) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > kLocalSpins || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) { s_abort = 1; break; }
-                }
-                if (ASM && k == 0 && (int)seen != 1 + my_xcc) s_foreign = 1;      // (the relation is symmetric: whoever gathers from this workgroup is in [nlo, nhi])
-            }
-            if (MR) {
-                // rows within `reach` of a cut gather from halo rows: wait for the tags the neighbour slab's cut-side workgroups wrote into this rank's
-                // region after their records had drained (threads 64.. / 128..: wavefronts 1 and 2, next to the local pollers in wavefront 0)
-                const bool need_lo = xr.need_lo > 0 && wg_first < b.reach, need_hi = xr.need_hi > 0 && wg_last + b.reach >= own_n;
-                const int side = tid >= 128 ? 1 : 0, j = tid - (side ? 128 : 64);      // (kXrPeerTags = 64 slots per side: threads 64..127 / 128..191)
-                if (tid >= 64 && tid < 192 && j < (side ? xr.wait_hi : xr.wait_lo) && (side ? need_hi : need_lo)) {
-                    int spins = 0;
-                    const double* wp = xr_me + kXrPtag + (side * 3 + (k > 0 ? ((k - 1) & 1) : 2)) * kXrPeerTags + j;
-                    const unsigned wantx = etag0 | (k > 0 ? want : 1u);      // (prologue flag: pass tag 1 in buffer 2)
-                    while (xr_tag_of(__hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != wantx) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++spins > (1 << 24) || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0 || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0) { s_abort = 1; break; }
-                    }
-                }
-            }
-            __syncthreads();
-            if (s_abort) { if (tid == 0) { __hip_atomic_store(fs + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (MR) for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrAbort, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } status = 2; break; }
-            if (tid == 0) { if (MR) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }      // (MR: system scope -- the halo records came from another GPU)
+            wg.wait_band_neighbours(k == 0, pb, want, &s_abort, &s_foreign);
+            wg.wait_peer_tags(k == 0, pb, want, &s_abort);
+            if (!wg.neighbours_acquired(&s_abort)) { status = 2; break; }
             if (ASM && k == 0) xcd_local = a.pcg_xcd_local && !s_foreign;
             __syncthreads();
         }
@@ -649,57 +763,28 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgf_solve(SweepArgs a, dou
                     if (ASM && k == 1) { v[7] = __hip_atomic_load(gp + (size_t)7 * kSolveMaxBlocks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && gran_tag_of(v[7]) == want; }   // |b|^2 travels with the sums of pass 0
                     if (!ok) {
                         __builtin_amdgcn_s_sleep(1);
-                        if (++spins > kLocalSpins || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) { s_abort = 1; break; }
+                        if (++spins > wg.kLocalSpins || wg.aborted()) { s_abort = 1; break; }
                     }
                 }
             }
             double t0, t1; wave_sum8(v, t0, t1);
             wave_sum8_store<kSolveThreads / 64>(t0, t1, red, tid >> 6);
             __syncthreads();
-            if (s_abort) { if (tid == 0) { __hip_atomic_store(fs + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (MR) for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrAbort, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } status = 2; break; }
-            double t[kCgfSums];
+            if (s_abort) { if (tid == 0) wg.raise_abort(); status = 2; break; }
+            const bool with_bb = ASM && k == 1;
+            double t[kCgfSums + 1];      // [7], with_bb: |b|^2
 #pragma unroll
             for (int q = 0; q < kCgfSums; ++q) { double s_ = 0; for (int i = 0; i < kSolveThreads / 64; ++i) s_ += red[q * (kSolveThreads / 64) + i]; t[q] = s_; }
-            if (ASM && k == 1) {
-                bb = 0.0;
-                for (int i = 0; i < kSolveThreads / 64; ++i) bb += red[7 * (kSolveThreads / 64) + i];
-            }
+            t[7] = 0.0;
+            if (with_bb) for (int i = 0; i < kSolveThreads / 64; ++i) t[7] += red[7 * (kSolveThreads / 64) + i];
             __syncthreads();
             if (MR) {
-                // ---- C2: the sums just obtained are this RANK's (every local workgroup holds the same bits).  Workgroup 0 hands them to every rank as tagged
-                // granules; every workgroup then adds the R granules of its own region in rank order (one fixed tree: the same bits on every rank).
-                const int pb = (k - 1) & 1;
-                if (lb == 0 && tid < 8 && (tid < kCgfSums || (ASM && k == 1))) {
-                    const double mine = xr_tag(tid < kCgfSums ? t[tid] : bb, etag0 | want);
-                    for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrRankGran + (pb * 8 + tid) * kXrMaxRanks + xr.rank, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                double rv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) rv[q] = 0.0;
-                if (tid < xr.n_ranks) {
-                    int spins = 0; bool ok = false;
-                    while (!ok) {
-                        ok = true;
-#pragma unroll
-                        for (int q = 0; q < kCgfSums; ++q) { rv[q] = __hip_atomic_load(xr_me + kXrRankGran + (pb * 8 + q) * kXrMaxRanks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); ok = ok && xr_tag_of(rv[q]) == (etag0 | want); }
-                        if (ASM && k == 1) { rv[7] = __hip_atomic_load(xr_me + kXrRankGran + (pb * 8 + 7) * kXrMaxRanks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); ok = ok && xr_tag_of(rv[7]) == (etag0 | want); }
-                        if (!ok) {
-                            __builtin_amdgcn_s_sleep(1);
-                            if (++spins > (1 << 24) || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0 || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0) { s_abort = 1; break; }
-                        }
-                    }
-                }
-                double r0, r1; wave_sum8(rv, r0, r1);
-                wave_sum8_store<kSolveThreads / 64>(r0, r1, red, tid >> 6);
-                __syncthreads();
-                if (s_abort) { if (tid == 0) { __hip_atomic_store(fs + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrAbort, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } status = 2; break; }
-#pragma unroll
-                for (int q = 0; q < kCgfSums; ++q) t[q] = red[q * (kSolveThreads / 64)];      // (all R <= 32 granules sit in wavefront 0)
-                if (ASM && k == 1) bb = red[7 * (kSolveThreads / 64)];
+                // ---- C2: the sums just obtained are this RANK's: the sums over all ranks
+                if (!wg.exchange_rank_sums(t, kCgfSums + (with_bb ? 1 : 0), pb, want, red, &s_abort)) { status = 2; break; }
                 __syncthreads();
             }
-            if (ASM && k == 1) {
-                rhsNorm2 = (float)bb; thr = pcg_threshold(rhsNorm2);
+            if (with_bb) {
+                bb = t[7]; rhsNorm2 = (float)bb; thr = pcg_threshold(rhsNorm2);
                 if (lb == 0 && tid == 0) fs[0] = bb;
             }
             const float rz_old = (float)t[5];
@@ -754,49 +839,14 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgf_solve(SweepArgs a, dou
             double* gq = gran + (size_t)(k & 1) * kSolveGranPlanes * kSolveMaxBlocks + (size_t)tid * kSolveMaxBlocks + lb;
             __hip_atomic_store(gq, gran_tag(tot, (unsigned)(k + 1) & 3u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (MR && tid == 64) peer_tag(k & 1, xr_tag(1.0, etag0 | ((unsigned)(k + 1) & 3u)));      // (every wave drained its stores before the barrier above: the halo records are out)
+        if (MR && tid == 64) wg.peer_tag(k & 1, (unsigned)(k + 1) & 3u);      // (every wave drained its stores before the barrier above: the halo records are out)
         __syncthreads();
         SOLVE_STAMP(6);
         if (force_passes > 0 && k == 8 && tid == 0) fs[16 + lb] = (double)wall_clock64();                 // timing hook: when every workgroup published pass 8 ...
     }
-#undef SOLVE_STAMP
-    // ---- leave: x of the own rows; the outcome for the host and for the gated kernels behind this one
-#pragma unroll
-    for (int u = 0; u < R; ++u) if (live[u]) b.x[row[u]] = x[u];
-    if (a.pcg_apply) {
-        // the distance update (k_apply_dist: updateDist's accept rule, OptimizerAux.cpp:162-188) for the own rows, under the rule the host applies
-        // to the solve's outcome -- every workgroup holds the same |r|^2 and |b|^2.  The accepted count is a sum of integers: the per-workgroup
-        // counts go to the first G entries of the slot, the rest of the slot (k_apply_albedo's leftovers) is cleared.
-        const bool z0 = rhsNorm2 == 0.f;
-        const bool ok_all = status == 1 && (z0 || sqrt((double)rr_cur / (double)rhsNorm2) <= (double)FLT_EPSILON);
-        const bool apply = status == 1 && (a.pcg_apply == 1 || ok_all);
-        double cnt = 0;
-        if (apply) {
-#pragma unroll
-            for (int u = 0; u < R; ++u) if (live[u] && (double)fabsf(x[u]) < sqrt(3.0) * (double)a.grid.vs) { b.dist[row[u]] -= x[u]; cnt += 1.0; }
-        }
-        cnt = wave_sum(cnt);
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = cnt;
-        __syncthreads();
-        double* slot = PART(a, SC_ACCEPT);
-        if (tid == 0) { double t = 0; for (int i = 0; i < kSolveThreads / 64; ++i) t += red[i]; slot[lb] = t; }
-        for (int i = G + lb * kSolveThreads + tid; i < a.acc.PB; i += G * kSolveThreads) slot[i] = 0.0;
-    }
-    if (lb == 0 && tid == 0) {
-        const bool rhs_zero = rhsNorm2 == 0.f;
-        const bool ok = status == 1 && (rhs_zero || sqrt((double)rr_cur / (double)rhsNorm2) <= (double)FLT_EPSILON);
-        int iters = 0;
-        if (!rhs_zero && k > 0) iters = (rr_cur < thr) ? k - 1 : k;      // Eigen leaves the loop before ++i when it detects convergence; k == kmax otherwise
-        fs[1] = status == 1 ? (double)(k + 1) : 0.0; fs[2] = ok ? 1.0 : 0.0;      // a solve that gave up leaves BOTH gates closed: nothing behind it may act on it (the host re-runs the solve, loop.hip)
-        const double m0 = (double)iters, m1 = (double)rr_cur, m2 = (double)rhsNorm2, m3 = (double)status;
-        mb[0] = m0; mb[1] = m1; mb[2] = m2;
-        __threadfence_system();
-        mb[3] = m3;                            // the host watches this slot ...
-        // ... and takes the four words only together with their check word (engine.h FoldReq)
-        if (mb_key) reinterpret_cast<unsigned long long*>(mb)[4] = (unsigned long long)(__double_as_longlong(m0) ^ __double_as_longlong(m1) ^ __double_as_longlong(m2) ^ __double_as_longlong(m3)) ^ mb_key;
-        __threadfence_system();
-    }
+    // ---- leave: x of the own rows; the distance update; the outcome for the host and for the gated kernels behind this one
+    solve_apply_and_count<MR, R>(wg, x, row, live, status, rr_cur, rhsNorm2, red);
+    if (lb == 0 && tid == 0) solve_report(fs, mb, mb_key, status, k, rr_cur, rhsNorm2, thr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -853,76 +903,27 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
 #define CGP_ABORT (*(kFast ? &s_ab3[(k + 3) % 3] : &s_abort))
     __shared__ int s_foreign;
     const Band& b = a.b;
-    const int G = gridDim.x, tid = threadIdx.x;
-    const int my_xcc = (int)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));
+    const SolveWg<MR> wg(a, xr, fs, gran, rows_per_wg);
+    const int G = wg.G, tid = wg.tid, lb = wg.lb;
     bool xcd_local = false;
-    const int lb = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-    const int plane = b.Spad * 4;
-    const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)b.colp, 0, (kNQ - 1) / 2 * plane, 0x00020000);
     double* const recd[2] = {(double*)b.rec[0], (double*)b.rec[1]};      // m_k lives in recd[k & 1] (u_0 of the prologue in recd[1]): the first Spad doubles of a record plane
-    const int own_n = a.row1 - a.row0;
-    const int wg_first = lb * rows_per_wg, wg_last = min(own_n, wg_first + rows_per_wg) - 1;
-    const bool cut_lo = MR && xr.give_lo > 0 && wg_first < xr.give_lo && wg_first < own_n;
-    const bool cut_hi = MR && xr.give_hi > 0 && wg_last >= own_n - xr.give_hi && wg_first < own_n;
-    const int hi_first_wg = MR ? max(0, own_n - xr.give_hi) / rows_per_wg : 0;
-    double* const xr_me = MR ? xr.region[xr.rank] : nullptr;
-    const unsigned etag0 = MR ? (xr.epoch & kXrEpochMask) << 2 : 0u;
-    constexpr int kLocalSpins = MR ? (1 << 24) : (1 << 22);
-    auto peer_tag = [&](int buf, double v) {
-        if (cut_lo && lb < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank - 1] + kXrPtag + (1 * 3 + buf) * kXrPeerTags + lb, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (cut_hi && lb - hi_first_wg < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank + 1] + kXrPtag + (0 * 3 + buf) * kXrPeerTags + (lb - hi_first_wg), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    };
     // the neighbour slab's halo row of the same band row.  (xr.lo_rec / hi_rec point at the first halo RECORD, 16 bytes per row: the same row counted in doubles)
     const int lo_row0 = MR && xr.lo_rec[0] ? (int)(xr.lo_rec[0] - xr.lo_base[0]) : 0;
     auto push_record = [&](int buf, int rel, double v) {
         if (MR && rel < xr.give_lo) store8_sys((double*)xr.lo_base[buf] + lo_row0 + rel, v);
-        if (MR && rel >= own_n - xr.give_hi) store8_sys((double*)xr.hi_rec[buf] + (rel - (own_n - xr.give_hi)), v);
-    };
-    auto raise_abort = [&] {
-        __hip_atomic_store(fs + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (MR) for (int r = 0; r < xr.n_ranks; ++r) __hip_atomic_store(xr.region[r] + kXrAbort, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (MR && rel >= wg.own_n - xr.give_hi) store8_sys((double*)xr.hi_rec[buf] + (rel - (wg.own_n - xr.give_hi)), v);
     };
     float* hs = (float*)psg_dyn_smem;
     const unsigned mepoch = TM ? (1u + a.pcg_epoch % 3u) << 2 : 0u;      // 1 .. 3, never the epoch of the solve before; 0 = memory no solve has written yet (the planes are zeroed when the band is built)
     unsigned cp[R][(kNQ - 1) / 2]; int row[R]; bool live[R];
     double x[R], r[R], w[R], z[R], sv[R], pv[R]; float inv[R];      // every vector of the recurrences in double: see "precision" above
-    if (a.fold.n != 0 && blockIdx.x == 0) {      // the sums the distance sweep left pending (device_common.h fold_pending), in that function's order
-        double ftot[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int sl = 0; sl < a.fold.n; ++sl) {
-            const double* part = PART(a, a.fold.id[sl]);
-            double v = 0;
-            if (tid < kBlock) for (int i = tid; i < a.fold.nblk; i += kBlock) v += part[i];
-            v = wave_sum(v);
-            __syncthreads();
-            if ((tid & 63) == 0) red[tid >> 6] = v;
-            __syncthreads();
-            if (tid == 0) { double t = 0; for (int i = 0; i < kBlock / 64; ++i) t += red[i]; ftot[sl] = t; }
-        }
-        if (tid < 64) {      // (the exchange between the ranks takes the whole first wavefront; lane 0 holds the slab's sums)
-            if (a.fold.xf) fold_exchange(a.fold.xf, a.fold.xf_epoch, a.fold.n, ftot);      // multi-rank: the sums over all slabs
-            if (tid == 0) {
-                for (int sl = 0; sl < a.fold.n; ++sl) mbox_put(a.fold.out, a.fold.n, sl, ftot[sl], a.fold.key);
-                mbox_commit(a.fold.key);
-            }
-        }
-        __syncthreads();
-    }
+    fold_pending<kBlock>(a, red);      // the sums the distance sweep left pending
     // ---- once: assemble the rows of this thread (coefficients -> LDS), r_0 = b, u_0 = M^-1 b out for the neighbours
 #pragma unroll
     for (int u = 0; u < R; ++u) {
-        const int i = a.row0 + lb * rows_per_wg + u * kSolveThreads + tid;
-        live[u] = u * kSolveThreads + tid < rows_per_wg && i < a.row1; row[u] = live[u] ? i : a.row1 - 1;
-        double acc[kNQ], rhs;
-        assemble_row_regs(a, row[u], acc, rhs);
-#pragma unroll
-        for (int q = 0; q < kNQ; ++q) {
-            float hv = (float)acc[q];
-            if (q == 0 && a.damping != 0.0f) hv += a.damping * hv;
-            hs[(u * kNQ + q) * kSolveThreads + tid] = hv;
-        }
-        float dg = (float)acc[0];
-        if (a.damping != 0.0f) dg += a.damping * dg;
-        inv[u] = dg != 0.f ? 1.0f / dg : 1.0f;
+        row[u] = wg.own_row(u, live[u]);
+        double rhs;
+        solve_assemble_row(a, row[u], hs + (size_t)u * kNQ * kSolveThreads + tid, inv[u], rhs);
         r[u] = live[u] ? (double)(float)rhs : 0.0;      // (b is the float vector the reference solves for)
         x[u] = 0.0; z[u] = 0.0; sv[u] = 0.0; pv[u] = 0.0; w[u] = 0.0;
         if (live[u]) {
@@ -930,59 +931,30 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             if (TM) { const double ut = m_tag(u0, mepoch | 0u); __hip_atomic_store(recd[1] + row[u], ut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); push_record(1, row[u] - a.row0, ut); }
             else { store8_sc1(recd[1] + row[u], u0); push_record(1, row[u] - a.row0, u0); }
         }
-#pragma unroll
-        for (int wd = 0; wd < (kNQ - 1) / 2; ++wd) cp[u][wd] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rC, row[u] * 4, wd * plane, 0);
+        solve_load_columns(b, row[u], cp[u]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) { __hip_atomic_store(gran + (size_t)(kSolveGranPlanes + 7) * kSolveMaxBlocks + lb, (double)(1 + my_xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (MR && !TM) peer_tag(2, xr_tag(1.0, etag0 | 1u)); }
+    if (tid == 0) wg.publish_prologue(!TM);
     float rhsNorm2 = 0.f, thr = 0.f, rr_cur = 0.f;
     double gamma_old = 0.0, alpha = 0.0;
     int k = -1, status = 1;                   // k = -1: the extra round w_0 = A u_0
-    const int first = lb * rows_per_wg, last = first + rows_per_wg - 1;
-    const int nlo = max(0, (first - b.reach) / rows_per_wg), nhi = min(G - 1, (last + b.reach) / rows_per_wg);
-    const bool need_lo = MR && xr.need_lo > 0 && wg_first < b.reach, need_hi = MR && xr.need_hi > 0 && wg_last + b.reach >= own_n;
-#define SOLVE_STAMP(j) do { if (force_passes > 0 && k == 8 && tid == 0 && (lb == 0 || lb == (G * 9) / 16)) mb[8 + (lb ? 8 : 0) + (j)] = (double)wall_clock64(); } while (0)
     for (;; ++k) {
         SOLVE_STAMP(0);
         const unsigned want = (unsigned)(k + 1) & 3u;      // tag of the sums published for pass k (k >= 0)
-        const double* gp = gran + (size_t)(k & 1) * kSolveGranPlanes * kSolveMaxBlocks;
-#pragma unroll
-        for (int u = 0; u < R; ++u)
-#pragma unroll
-            for (int wd = 0; wd < (kNQ - 1) / 2; ++wd) asm volatile("" : "+v"(cp[u][wd]));
-        // ---- A: the values this workgroup gathers are those of its neighbours in band order: their tag (the first sum of pass k, stored after
-        // their m_k had drained; k = -1: the prologue's flag)
+        const int pb = k & 1;                              // the buffer they were published in
+        const double* gp = wg.gran_plane(pb, 0);
+        const int abl = (a.pcg_xcd_local >> 3) & 7;      // timing ablations (tools/pcg_variants.py; never set in production): 1 = every gather reads the row's own element, 2 = no neighbour-tag wait, 4 = the 8 in-plane columns are not fetched
+        solve_keep_columns_packed<R>(cp);
+        // ---- A: wait for the neighbours' m_k (k = -1: for their u_0).  TM: the values validate themselves, nothing to wait for
         if (!kFast || k < 0) {
             if (tid == 0) { s_abort = 0; s_ab3[0] = 0; s_ab3[1] = 0; s_ab3[2] = 0; if (k < 0) s_foreign = 0; }
             __syncthreads();
         }
-        if (!TM && tid <= nhi - nlo && !((a.pcg_xcd_local >> 3) & 2)) {
-            int spins = 0;
-            const double* wp = k >= 0 ? gp + nlo + tid : gran + (size_t)(kSolveGranPlanes + 7) * kSolveMaxBlocks + nlo + tid;
-            double seen = 0.0;
-            while (k >= 0 ? gran_tag_of(seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != want : (seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0.0) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > kLocalSpins || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) { CGP_ABORT = 1; break; }
-            }
-            if (k < 0 && (int)seen != 1 + my_xcc) s_foreign = 1;
-        }
-        if (MR && !TM) {
-            const int side = tid >= 128 ? 1 : 0, j = tid - (side ? 128 : 64);
-            if (tid >= 64 && tid < 192 && j < (side ? xr.wait_hi : xr.wait_lo) && (side ? need_hi : need_lo)) {
-                int spins = 0;
-                const double* wp = xr_me + kXrPtag + (side * 3 + (k >= 0 ? (k & 1) : 2)) * kXrPeerTags + j;
-                const unsigned wantx = etag0 | (k >= 0 ? want : 1u);
-                while (xr_tag_of(__hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != wantx) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > (1 << 24) || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0 || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0) { CGP_ABORT = 1; break; }
-                }
-            }
-        }
         if (!TM) {
-            __syncthreads();
-            if (CGP_ABORT) { if (tid == 0) raise_abort(); status = 2; break; }
-            if (tid == 0) { if (MR) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+            if (!(abl & 2)) wg.wait_band_neighbours(k < 0, pb, want, &CGP_ABORT, &s_foreign);
+            wg.wait_peer_tags(k < 0, pb, want, &CGP_ABORT);
+            if (!wg.neighbours_acquired(&CGP_ABORT)) { status = 2; break; }
             if (k < 0) xcd_local = (a.pcg_xcd_local & 1) && !s_foreign;
             __syncthreads();
         }
@@ -990,7 +962,6 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         if (force_passes > 0 && k == 9 && tid == 0) fs[16 + 1536 + lb] = (double)wall_clock64();      // ... neighbours' tags of pass 9 seen
         // ---- B: n = A m (k = -1: w_0 = A u_0): 18 four-byte gathers per row in two batches of 9, software-pipelined across the rows of the thread
         const double* __restrict__ rin = recd[k >= 0 ? (k & 1) : 1];
-        const int abl = (a.pcg_xcd_local >> 3) & 7;      // timing ablations (tools/pcg_variants.py; never set in production): 1 = every gather reads the row's own element, 2 = no neighbour-tag wait, 4 = the 8 in-plane columns are not fetched
         double nres[R];
         double ob[kCgpDepth][9];
         auto issue = [&](int t) {
@@ -1042,7 +1013,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
                     do {
                         __builtin_amdgcn_s_sleep(1);
                         vv = MR ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (a halo row is written by the neighbour RANK)
-                        if (++spins > kLocalSpins || ((spins & 255) == 0 && (__hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0 || (MR && __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0)))) { CGP_ABORT = 1; break; }
+                        if (++spins > wg.kLocalSpins || ((spins & 255) == 0 && (MR ? wg.aborted_by_rank() : wg.aborted()))) { CGP_ABORT = 1; break; }
                     } while (m_tag_of(vv) != wantm);
                     ob[t % kCgpDepth][j] = vv;
                 }
@@ -1057,7 +1028,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             __builtin_amdgcn_sched_barrier(0);
         }
         SOLVE_STAMP(2);
-        if (force_passes > 0 && k == 9 && tid == 0) { fs[16 + 1024 + lb] = (double)wall_clock64(); fs[16 + 768 + lb] = (double)my_xcc; fs[16 + 1792 + lb] = (double)(gran_tag_of(v[0]) == want && gran_tag_of(v[1]) == want && gran_tag_of(v[2]) == want); }      // timing hook (PSGSDF_SOLVE_DUMP): gathers of pass 9 done; was the prefetch of this thread's granules valid?
+        if (force_passes > 0 && k == 9 && tid == 0) { fs[16 + 1024 + lb] = (double)wall_clock64(); fs[16 + 768 + lb] = (double)wg.my_xcc; fs[16 + 1792 + lb] = (double)(gran_tag_of(v[0]) == want && gran_tag_of(v[1]) == want && gran_tag_of(v[2]) == want); }      // timing hook (PSGSDF_SOLVE_DUMP): gathers of pass 9 done; was the prefetch of this thread's granules valid?
         double beta = 0.0;
         bool stop = false;
         if (k >= 0) {
@@ -1067,7 +1038,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
                 bool ok = prefetched && gran_tag_of(v[0]) == want && gran_tag_of(v[1]) == want && gran_tag_of(v[2]) == want;
                 while (!ok) {
                     if (spins) __builtin_amdgcn_s_sleep(1);
-                    if (++spins > kLocalSpins || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) { CGP_ABORT = 1; break; }
+                    if (++spins > wg.kLocalSpins || wg.aborted()) { CGP_ABORT = 1; break; }
                     ok = true;
 #pragma unroll
                     for (int q = 0; q < kCgpSums; ++q) { v[q] = __hip_atomic_load(base + (size_t)q * kSolveMaxBlocks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && gran_tag_of(v[q]) == want; }
@@ -1076,40 +1047,14 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             if (tid < G) poll3(gp + tid, (a.pcg_xcd_local & 2) != 0);
             { const double v4[4] = {v[0], v[1], v[2], 0.0}; wave_sum4_store<kSolveThreads / 64>(wave_sum4(v4), red, tid >> 6); }      // (three sums: the four-value reduce-scatter, the same bits as wave_sum8's)
             __syncthreads();
-            if (CGP_ABORT) { if (tid == 0) raise_abort(); status = 2; break; }
+            if (CGP_ABORT) { if (tid == 0) wg.raise_abort(); status = 2; break; }
             double t[kCgpSums];
 #pragma unroll
             for (int q = 0; q < kCgpSums; ++q) { double s_ = 0; for (int i = 0; i < kSolveThreads / 64; ++i) s_ += red[q * (kSolveThreads / 64) + i]; t[q] = s_; }
             if (!kFast) __syncthreads();      // (kFast: stage E has a buffer of its own)
             if (MR) {
-                // ---- C2: this RANK's sums -> every rank's region (workgroup 0), then the R rank granules of the own region in rank order
-                const int pb = k & 1;
-                if (lb == 0 && tid < kCgpSums) {
-                    const double mine = xr_tag(t[tid], etag0 | want);
-                    for (int rk = 0; rk < xr.n_ranks; ++rk) __hip_atomic_store(xr.region[rk] + kXrRankGran + (pb * 8 + tid) * kXrMaxRanks + xr.rank, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                double rv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) rv[q] = 0.0;
-                if (tid < xr.n_ranks) {
-                    int spins = 0; bool ok = false;
-                    while (!ok) {
-                        ok = true;
-#pragma unroll
-                        for (int q = 0; q < kCgpSums; ++q) { rv[q] = __hip_atomic_load(xr_me + kXrRankGran + (pb * 8 + q) * kXrMaxRanks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); ok = ok && xr_tag_of(rv[q]) == (etag0 | want); }
-                        if (!ok) {
-                            __builtin_amdgcn_s_sleep(1);
-                            if (++spins > (1 << 24) || __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0 || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0) { CGP_ABORT = 1; break; }
-                        }
-                    }
-                }
-                double* const redR = kFast ? red3 : red;
-                double r0, r1; wave_sum8(rv, r0, r1);
-                wave_sum8_store<kSolveThreads / 64>(r0, r1, redR, tid >> 6);
-                __syncthreads();
-                if (CGP_ABORT) { if (tid == 0) raise_abort(); status = 2; break; }
-#pragma unroll
-                for (int q = 0; q < kCgpSums; ++q) t[q] = redR[q * (kSolveThreads / 64)];      // (all <= 32 rank granules sit in wavefront 0)
+                // ---- C2: the sums just obtained are this RANK's: the sums over all ranks
+                if (!wg.exchange_rank_sums(t, kCgpSums, pb, want, kFast ? red3 : red, &CGP_ABORT)) { status = 2; break; }
                 if (!kFast) __syncthreads();
             }
             if (k == 0) { rhsNorm2 = (float)t[2]; thr = pcg_threshold(rhsNorm2); if (lb == 0 && tid == 0) fs[0] = t[2]; }
@@ -1166,7 +1111,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         double* const redE = kFast ? red2 + ((k + 1) & 1) * (8 * kSolveThreads / 64) : red;
         wave_sum4_store<kSolveThreads / 64>(tE, redE, tid >> 6);
         __syncthreads();
-        if (TM && CGP_ABORT) { if (tid == 0) raise_abort(); status = 2; break; }      // (a gather of this pass gave up)
+        if (TM && CGP_ABORT) { if (tid == 0) wg.raise_abort(); status = 2; break; }      // (a gather of this pass gave up)
         if (kFast && tid == 0) s_ab3[(k + 5) % 3] = 0;      // the flag of pass k + 2: its readers (pass k - 1) are past this barrier, its raisers two barriers away
         SOLVE_STAMP(5);
         if (tid < kCgpSums) {
@@ -1175,7 +1120,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             double* gq = gran + (size_t)((k + 1) & 1) * kSolveGranPlanes * kSolveMaxBlocks + (size_t)tid * kSolveMaxBlocks + lb;
             __hip_atomic_store(gq, gran_tag(tot, (unsigned)(k + 2) & 3u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (MR && !TM && tid == 64) peer_tag((k + 1) & 1, xr_tag(1.0, etag0 | ((unsigned)(k + 2) & 3u)));
+        if (MR && !TM && tid == 64) wg.peer_tag((k + 1) & 1, (unsigned)(k + 2) & 3u);
         if (!kFast) __syncthreads();
         SOLVE_STAMP(6);
         if (force_passes > 0 && k == 8 && tid == 0) fs[16 + lb] = (double)wall_clock64();      // ... published at the end of pass 8 (m_9 and the sums of pass 9)
@@ -1184,91 +1129,58 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
 #undef SOLVE_STAMP
 #undef CGP_ABORT
     // ---- leave: x of the own rows; the distance update; the outcome for the host and for the gated kernels behind this one
+    // (Measured and rejected, profiles/r04_notes.md: the regrad -- k_derive -- in this epilogue behind one more neighbour hand-off.  Same bits, no
+    // launch, but 2 648 vs 2 680 it/s: with one workgroup of eight waves per CU the dependent loads of three rows per thread take longer than the
+    // 13 us the stand-alone kernel needs at full occupancy.)
     float xf[R];
 #pragma unroll
-    for (int u = 0; u < R; ++u) { xf[u] = (float)x[u]; if (live[u]) b.x[row[u]] = xf[u]; }
-    if (a.pcg_apply) {
-        const bool z0 = rhsNorm2 == 0.f;
-        const bool ok_all = status == 1 && (z0 || sqrt((double)rr_cur / (double)rhsNorm2) <= (double)FLT_EPSILON);
-        const bool apply = status == 1 && (a.pcg_apply == 1 || ok_all);
-        double cnt = 0;
-        if (apply) {
-#pragma unroll
-            for (int u = 0; u < R; ++u) if (live[u] && (double)fabsf(xf[u]) < sqrt(3.0) * (double)a.grid.vs) { b.dist[row[u]] -= xf[u]; cnt += 1.0; }
-        }
-        cnt = wave_sum(cnt);
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = cnt;
-        __syncthreads();
-        double* slot = PART(a, SC_ACCEPT);
-        if (tid == 0) { double t = 0; for (int i = 0; i < kSolveThreads / 64; ++i) t += red[i]; slot[lb] = t; }
-        for (int i = G + lb * kSolveThreads + tid; i < a.acc.PB; i += G * kSolveThreads) slot[i] = 0.0;
-        // (Measured and rejected, profiles/r04_notes.md: the regrad -- k_derive -- in this epilogue behind one more neighbour hand-off.  Same bits, no
-        // launch, but 2 648 vs 2 680 it/s: with one workgroup of eight waves per CU the dependent loads of three rows per thread take longer than the
-        // 13 us the stand-alone kernel needs at full occupancy.)
-    }
-    if (lb == 0 && tid == 0) {
-        const bool rhs_zero = rhsNorm2 == 0.f;
-        const bool ok = status == 1 && (rhs_zero || sqrt((double)rr_cur / (double)rhsNorm2) <= (double)FLT_EPSILON);
-        int iters = 0;
-        if (!rhs_zero && k > 0) iters = (rr_cur < thr) ? k - 1 : k;
-        fs[1] = status == 1 ? (double)(k + 1) : 0.0; fs[2] = ok ? 1.0 : 0.0;
-        const double m0 = (double)iters, m1 = (double)rr_cur, m2 = (double)rhsNorm2, m3 = (double)status;
-        mb[0] = m0; mb[1] = m1; mb[2] = m2;
-        __threadfence_system();
-        mb[3] = m3;
-        if (mb_key) reinterpret_cast<unsigned long long*>(mb)[4] = (unsigned long long)(__double_as_longlong(m0) ^ __double_as_longlong(m1) ^ __double_as_longlong(m2) ^ __double_as_longlong(m3)) ^ mb_key;
-        __threadfence_system();
-    }
+    for (int u = 0; u < R; ++u) xf[u] = (float)x[u];
+    solve_apply_and_count<MR, R>(wg, xf, row, live, status, rr_cur, rhsNorm2, red);
+    if (lb == 0 && tid == 0) solve_report(fs, mb, mb_key, status, k, rr_cur, rhsNorm2, thr);
 }
-static size_t cgf_solve_lds(int rows) { return sizeof(float) * (size_t)rows * kNQ * kSolveThreads; }
-static size_t cgp_solve_lds(int rows) { return cgf_solve_lds(rows); }
-template <int R, bool ASM, bool MR> static int cgf_solve_prepare() {      // > 64 KB of dynamic LDS has to be asked for, once per instance
-    static int per_cu = -1;
-    if (per_cu >= 0) return per_cu;
-    per_cu = 0;
-    if (hipFuncSetAttribute((const void*)k_cgf_solve<R, ASM, MR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cgf_solve_lds(R)) != hipSuccess) return per_cu;
+
+// ---- host side of the persistent solve: both kernels take the same arguments, the same launch shape and the same dynamic LDS
+using SolveKernel = void (*)(SweepArgs, double*, double*, int, int, double*, unsigned long long, int, XrArgs);
+static_assert(kCgpMaxRows == kSolveMaxRows && kSolveMaxRows == 4, "every row count has both kernels; solve_with_rows lists the row counts");
+static size_t solve_lds(int rows) { return sizeof(float) * (size_t)rows * kNQ * kSolveThreads; }
+// > 64 KB of dynamic LDS has to be asked for; returns the resident workgroups per CU (0: the instance cannot run)
+static int solve_prepare(SolveKernel kern, size_t lds) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_cgf_solve<R, ASM, MR>, kSolveThreads, cgf_solve_lds(R)) == hipSuccess) per_cu = n;
-    return per_cu;
+    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kern, kSolveThreads, lds) == hipSuccess ? n : 0;
 }
-template <int R, bool MR, bool TM = false> static int cgp_solve_prepare() {
-    static int per_cu = -1;
-    if (per_cu >= 0) return per_cu;
-    per_cu = 0;
-    if (hipFuncSetAttribute((const void*)k_cgp_solve<R, MR, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cgp_solve_lds(R)) != hipSuccess) return per_cu;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_cgp_solve<R, MR, TM>, kSolveThreads, cgp_solve_lds(R)) == hipSuccess) per_cu = n;
-    return per_cu;
-}
-template <int R> static int cgf_solve_prepare_both() {
-    const int classic = std::min(std::min(cgf_solve_prepare<R, false, false>(), cgf_solve_prepare<R, true, false>()), cgf_solve_prepare<R, true, true>());
-    if (R > kCgpMaxRows) return classic;
-    return std::min(classic, std::min(std::min(cgp_solve_prepare<R, false>(), cgp_solve_prepare<R, false, true>()), std::min(cgp_solve_prepare<R, true>(), cgp_solve_prepare<R, true, true>())));
+// f(std::integral_constant<int, R>) for the R = rows per thread
+template <class F> static auto solve_with_rows(int rows, F&& f) {
+    switch (rows) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
 }
 int cgf_solve_max_blocks(int rows) {
-    return rows == 1 ? cgf_solve_prepare_both<1>() : rows == 2 ? cgf_solve_prepare_both<2>() : rows == 3 ? cgf_solve_prepare_both<3>() : cgf_solve_prepare_both<4>();
-}
-template <int R>
-static void launch_cgf_solve_r(const SweepArgs& a, double* fs, double* gran, int G, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, hipStream_t s, const XrArgs* xr) {
-    XrArgs none{};
-    if (a.pcg_asm && a.pcg_pipe && R <= kCgpMaxRows) {      // the pipelined recurrences (always with the fused assembly)
-        if (xr && xr->n_ranks > 1 && a.pcg_pipe == 3) hipLaunchKernelGGL((k_cgp_solve<R, true, true>), dim3(G), dim3(kSolveThreads), cgp_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, *xr);      // ... across ranks too (PSGSDF_PCG_TAGM=2)
-        else if (xr && xr->n_ranks > 1) hipLaunchKernelGGL((k_cgp_solve<R, true>), dim3(G), dim3(kSolveThreads), cgp_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, *xr);
-        else if (a.pcg_pipe >= 2) { hipLaunchKernelGGL((k_cgp_solve<R, false, true>), dim3(G), dim3(kSolveThreads), cgp_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, none); }      // self-validating m (PSGSDF_PCG_TAGM)
-        else hipLaunchKernelGGL((k_cgp_solve<R, false>), dim3(G), dim3(kSolveThreads), cgp_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, none);
-        return;
-    }
-    if (xr && xr->n_ranks > 1 && a.pcg_asm) hipLaunchKernelGGL((k_cgf_solve<R, true, true>), dim3(G), dim3(kSolveThreads), cgf_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, *xr);
-    else if (a.pcg_asm) hipLaunchKernelGGL((k_cgf_solve<R, true, false>), dim3(G), dim3(kSolveThreads), cgf_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, none);
-    else hipLaunchKernelGGL((k_cgf_solve<R, false, false>), dim3(G), dim3(kSolveThreads), cgf_solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, none);
+    return solve_with_rows(rows, [](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        static const int per_cu = [] {      // once per row count: the least of all its instances
+            int n = INT_MAX;
+            for (SolveKernel kern : {(SolveKernel)k_cgf_solve<R, false, false>, (SolveKernel)k_cgf_solve<R, true, false>, (SolveKernel)k_cgf_solve<R, true, true>, (SolveKernel)k_cgp_solve<R, false, false>,
+                                     (SolveKernel)k_cgp_solve<R, false, true>, (SolveKernel)k_cgp_solve<R, true, false>, (SolveKernel)k_cgp_solve<R, true, true>})
+                n = std::min(n, solve_prepare(kern, solve_lds(R)));
+            return n;
+        }();
+        return per_cu;
+    });
 }
 void launch_cgf_solve(const SweepArgs& a, double* fs, double* gran, int G, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, hipStream_t s, const XrArgs* xr) {
-    const int rows = (rows_per_wg + kSolveThreads - 1) / kSolveThreads;
-    if (rows == 1) launch_cgf_solve_r<1>(a, fs, gran, G, rows_per_wg, kmax, mb, mb_key, force_passes, s, xr);
-    else if (rows == 2) launch_cgf_solve_r<2>(a, fs, gran, G, rows_per_wg, kmax, mb, mb_key, force_passes, s, xr);
-    else if (rows == 3) launch_cgf_solve_r<3>(a, fs, gran, G, rows_per_wg, kmax, mb, mb_key, force_passes, s, xr);
-    else launch_cgf_solve_r<4>(a, fs, gran, G, rows_per_wg, kmax, mb, mb_key, force_passes, s, xr);
+    const bool mr = a.pcg_asm && xr && xr->n_ranks > 1;      // (without the fused assembly the ranks meet between per-pass kernels, loop.hip)
+    solve_with_rows((rows_per_wg + kSolveThreads - 1) / kSolveThreads, [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        SolveKernel kern;
+        if (a.pcg_asm && a.pcg_pipe)      // the pipelined recurrences (always with the fused assembly); TM: self-validating m (PSGSDF_PCG_TAGM; across ranks: = 2)
+            kern = mr ? (a.pcg_pipe == 3 ? k_cgp_solve<R, true, true> : k_cgp_solve<R, true, false>) : (a.pcg_pipe >= 2 ? k_cgp_solve<R, false, true> : k_cgp_solve<R, false, false>);
+        else kern = mr ? k_cgf_solve<R, true, true> : a.pcg_asm ? k_cgf_solve<R, true, false> : k_cgf_solve<R, false, false>;
+        hipLaunchKernelGGL(kern, dim3(G), dim3(kSolveThreads), solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, mr ? *xr : XrArgs{});
+    });
 }
 
 // multi-rank: fold the partials of pass k (k = -1: |b|^2 of the init) into out[0..6] for the host program's all-reduce

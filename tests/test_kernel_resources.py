@@ -41,7 +41,13 @@ def test_persistent_distance_step_does_not_spill(tmp_path):
             assert v["scratch"] <= 128, (k, v)                         # the multi-rank instance at 3 rows per thread spills a little (a slab of a partitioned band rarely needs it)
             continue
         assert v["scratch"] == 0 and v["vgpr"] <= 256, (k, v)
-    passk = {k: v for k, v in res.items() if "k_cgf_pass" in k and "ILi1ELi4E" in k}
+    pipelined = {k: v for k, v in res.items() if "k_cgp_solve" in k}
+    assert len(pipelined) == 16                                        # the production kernels: R = 1..4 x {one rank, across ranks (MR)} x {ordered by flags, self-validating values (TM)}
+    for k, v in pipelined.items():
+        if "ILi4E" in k:
+            continue                                                   # 4 rows per thread: not tuned, as above
+        assert v["scratch"] == 0 and v["vgpr"] <= 256, (k, v)
+    passk ={k: v for k, v in res.items() if "k_cgf_pass" in k and "ILi1ELi4E" in k}
     assert passk and all(v["vgpr"] <= 128 and v["scratch"] == 0 for v in passk.values()), passk      # the per-pass kernel: 4 waves per SIMD
 
 
