@@ -78,6 +78,14 @@ class MeshFilter(C.Structure):      # psgsdf_mesh_filter (include/psgsdf_mesh.h)
     _fields_ = [("min_faces", C.c_int64), ("min_area", C.c_double), ("keep_largest", C.c_int32)]
 
 
+class Bake(C.Structure):      # psgsdf_bake (include/psgsdf_bake.h)
+    _fields_ = [("xyz", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("rgb", C.POINTER(C.c_uint8)), ("faces", C.POINTER(C.c_int32)), ("vertex_map", C.POINTER(C.c_int32)),
+                ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_vertices_in", C.c_int64), ("n_faces_in", C.c_int64),
+                ("uv", C.POINTER(C.c_float)), ("width", C.c_int32), ("height", C.c_int32),
+                ("albedo", C.POINTER(C.c_uint8)), ("normal", C.POINTER(C.c_float)), ("displacement", C.POINTER(C.c_float)), ("voxel", C.POINTER(C.c_int32)), ("face", C.POINTER(C.c_int32)),
+                ("n_texels", C.c_int64), ("n_hits", C.c_int64), ("n_hits_off_band", C.c_int64), ("n_buried", C.c_int64), ("n_misses", C.c_int64)]
+
+
 # psgsdf_mesh_component (include/psgsdf_mesh.h), 88 bytes
 MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_faces", "<i8"), ("n_edges", "<i8"), ("n_boundary_edges", "<i8"),
                                  ("n_nonmanifold_edges", "<i8"), ("area", "<f8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("kept", "<i4"), ("reserved", "<i4")])
@@ -444,6 +452,26 @@ class Api:
         arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
         return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
                     vertex_map=np.ctypeslib.as_array(vm, shape=(Vi,)).copy() if Vi else np.zeros(0, np.int32), n_vertices_in=Vi, n_faces_in=nfi.value)
+
+    def bake_lod(self, cell, res, reach=None, min_faces=0, min_area=0.0, keep_largest=0):
+        """Albedo, normal and displacement maps baked onto the level-of-detail mesh (include/psgsdf_bake.h psgsdf_bake_lod): extract_mesh_lod's dict for
+        the same cell and filter, plus uv [F, 3, 2] float32 (v pointing down), width, height, the atlas planes albedo [H, W, 3] uint8, normal [H, W, 3]
+        float32, displacement [H, W] float32, voxel [H, W] int32 (-1: no hit), face [H, W] int32 (-1: padding) and the counts n_texels, n_hits,
+        n_hits_off_band, n_buried, n_misses.  res: texels along a triangle's edge; reach: how far outside the coarse triangle a texel's ray starts, in
+        the mesh's units (None: cell).  Single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        b = Bake()
+        self._check(self._fn("bake_lod")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
+                                         C.c_double(float(cell if reach is None else reach)), C.byref(b)), "bake_lod")
+        V, F, Vi, W, H = b.n_vertices, b.n_faces, b.n_vertices_in, b.width, b.height
+        arr = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
+        out = dict(xyz=arr(b.xyz, (V, 3), np.float32), normals=arr(b.normals, (V, 3), np.float32), rgb=arr(b.rgb, (V, 3), np.uint8), faces=arr(b.faces, (F, 3), np.int32),
+                   vertex_map=arr(b.vertex_map, (Vi,), np.int32), n_vertices_in=Vi, n_faces_in=b.n_faces_in,
+                   uv=arr(b.uv, (F if W else 0, 3, 2), np.float32), width=W, height=H, albedo=arr(b.albedo, (H, W, 3), np.uint8), normal=arr(b.normal, (H, W, 3), np.float32),
+                   displacement=arr(b.displacement, (H, W), np.float32), voxel=arr(b.voxel, (H, W), np.int32), face=arr(b.face, (H, W), np.int32))
+        for k in ("n_texels", "n_hits", "n_hits_off_band", "n_buried", "n_misses"):
+            out[k] = int(getattr(b, k))
+        return out
 
     # -- the photometric fit resolved over the surface (include/psgsdf_fit.h)
     def band_fit(self):

@@ -2,7 +2,7 @@
 // (psgsdf_render_report).  Kernels: render.hip.
 // On a multi-rank context both are collective calls ("Multi-rank contexts"): every rank traces its own slab, and three sum all-reduces over the
 // context's communicator (brick marks + the call's checksum, per-pixel hit masks, the winners' records) give every rank the single-rank result.
-#include "engine_internal.h"
+#include "extract_internal.h"
 #include "../../include/psgsdf_render.h"
 
 using namespace psge;
@@ -121,6 +121,10 @@ int render_ranks_pass(psgsdf_ctx* c, RenderArgs& a, bool report, int chunk) {
 }
 
 }  // namespace
+
+namespace psge {
+int render_prepare(psgsdf_ctx* c, DevMem& m, RenderArgs& a, const char* what) { return render_args(c, m, a, 0.0, what, nullptr); }
+}  // namespace psge
 
 extern "C" {
 

@@ -41,6 +41,7 @@ enum XoSlot {
     XO_LOD_VERTEX_MAP,                                               // psgsdf_extract_mesh_lod
     XO_FIT_NOBS, XO_FIT_LOSS, XO_FIT_R2,                             // psgsdf_band_fit
     XO_VFIT_NOBS, XO_VFIT_RMS, XO_VFIT_LOSS,                         // psgsdf_extract_mesh_fit (its mesh: XO_IMESH_*)
+    XO_BAKE_UV, XO_BAKE_ALBEDO, XO_BAKE_NORMAL, XO_BAKE_DISPLACEMENT, XO_BAKE_VOXEL, XO_BAKE_FACE,   // psgsdf_bake_lod (its mesh: XO_IMESH_*, XO_LOD_VERTEX_MAP)
     XO_COUNT
 };
 }  // namespace psge

@@ -17,6 +17,10 @@ int crop_box_dev(psgsdf_ctx* c, int lo[3], int hi[3], bool* any);
 // state checks of every extraction call, pending work flushed, the band's state scattered into the dense arrays
 int extract_ready(psgsdf_ctx* c, const char* what);
 
+// api_render.hip: the renderer's prepare path for a single-rank call -- dense planes, band state and grid into `a`, the occupied-brick map and its box
+// built into `m` (k_render_bricks on the stream)
+int render_prepare(psgsdf_ctx* c, DevMem& m, RenderArgs& a, const char* what);
+
 // one result array of a call: `bytes` at `dev` go to the pinned slot, whose address goes to *out (nothing happens for 0 bytes)
 struct XoCopy {
     template <class T> XoCopy(XoSlot slot, const void* dev, size_t bytes, const T** out) : slot(slot), dev(dev), bytes(bytes), out(out) {}

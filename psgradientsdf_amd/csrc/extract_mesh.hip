@@ -1,7 +1,8 @@
 // extract_mesh.hip -- the C ABI of include/psgsdf_mesh.h: the welded, indexed mesh of the context's state (kernels: mesh.hip; DESIGN.md "Welded
 // meshes"), its connected components and the mesh without its small pieces (mesh_cc.hip; "Mesh components") and a level-of-detail mesh by vertex
 // clustering (mesh_lod.hip; "Level of detail"); and the C ABI of include/psgsdf_fit.h: the photometric fit per band row and per vertex of the welded
-// mesh (fit.hip; "Photometric fit per voxel and vertex").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
+// mesh (fit.hip; "Photometric fit per voxel and vertex"); and the C ABI of include/psgsdf_bake.h: detail maps of the level-of-detail mesh (bake.hip;
+// "Baked detail maps").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
 // welded mesh -> vertex fit -- that hand each other device arrays whose kernels may still be in flight.  The CALL owns all device memory of its
 // stages in one DevMem, which waits for the stream and frees when the call returns, whichever way it returns: a stage allocates from it and never frees.
 // The frame arithmetic (extract_internal.h crop_frame) runs on the host and its results are compared bit for bit: no FMA contraction here either.
@@ -9,7 +10,9 @@
 #include "extract_internal.h"
 #include "../../include/psgsdf_mesh.h"
 #include "../../include/psgsdf_fit.h"
+#include "../../include/psgsdf_bake.h"
 #include "mesh_lod.h"
+#include "bake.h"
 
 using namespace psge;
 
@@ -224,12 +227,12 @@ extern "C" int psgsdf_extract_mesh_components(psgsdf_ctx* c, const psgsdf_mesh_f
 }
 
 namespace {
-// ---- stage 3: the input mesh `in` (nv > 0, nf > 0) clustered, and the result in its pinned host slots
+// ---- stage 3: the input mesh `in` (nv > 0, nf > 0) clustered, and the result in its pinned host slots; dev (if asked for): the result's device arrays
 struct LodOut {
     const float** xyz; const float** normals; const uint8_t** rgb; int64_t* n_vertices; const int32_t** faces; int64_t* n_faces; const int32_t** vertex_map;
     int64_t* n_vertices_in; int64_t* n_faces_in;
 };
-int lod_from_device(psgsdf_ctx* c, DevMem& mem, const MeshView& in, double cell, const LodOut& o) {
+int lod_from_device(psgsdf_ctx* c, DevMem& mem, const MeshView& in, double cell, const LodOut& o, MeshView* dev = nullptr) {
     const char* me = "extract_mesh_lod";
     const int nv = in.nv, nf = in.nf;
     if (nv >= (1 << 30) || nf >= (1 << 30)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: %d vertices, %d faces", me, nv, nf);      // (slots are ints)
@@ -266,21 +269,18 @@ int lod_from_device(psgsdf_ctx* c, DevMem& mem, const MeshView& in, double cell,
     if (int rc = download(c, me, {{XO_LOD_VERTEX_MAP, vmap, sizeof(int) * (size_t)nv, o.vertex_map}, {XO_IMESH_XYZ, o_xyz, sizeof(float) * 3 * v, o.xyz}, {XO_IMESH_NORMALS, o_nrm, sizeof(float) * 3 * v, o.normals},
                                   {XO_IMESH_RGB, o_rgb, 3 * v, o.rgb}, {XO_IMESH_FACES, o_faces, sizeof(int) * 3 * f, o.faces}})) return rc;
     *o.n_vertices_in = nv; *o.n_faces_in = nf; *o.n_vertices = (int64_t)v; *o.n_faces = (int64_t)f;
+    if (dev) { dev->xyz = o_xyz; dev->nrm = o_nrm; dev->rgb = o_rgb; dev->faces = o_faces; dev->nv = (int)v; dev->nf = (int)f; }
     return PSGSDF_OK;
 }
-}  // namespace
-
-extern "C" int psgsdf_extract_mesh_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
-                                       const int32_t** faces, int64_t* n_faces, const int32_t** vertex_map, int64_t* n_vertices_in, int64_t* n_faces_in) {
-    const char* me = "extract_mesh_lod";
-    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_map || !n_vertices_in || !n_faces_in) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
-    // (before anything collective and before any device work: no rank waits for another)
+// what psgsdf_extract_mesh_lod and psgsdf_bake_lod check first (before anything collective and before any device work: no rank waits for another) ...
+int lod_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, double cell) {
     if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): clusters are not merged across z-slabs", me, c->rank, c->n_ranks);
     if (!(cell > 0.0) || std::isinf(cell)) return fail(c, PSGSDF_ERR_ARG, "%s: the cell must be a finite size > 0", me);
     if (filter && bad_filter(*filter)) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
-    { int rc = extract_ready(c, me); if (rc) return rc; }
-    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_map = nullptr; *n_vertices = 0; *n_faces = 0; *n_vertices_in = 0; *n_faces_in = 0;
-    DevMem mem(c);
+    return PSGSDF_OK;
+}
+// ... and the stages both run: the welded mesh, its components if there is a filter, the clusters
+int lod_stages(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, const LodOut& o, MeshView* dev = nullptr) {
     MeshView in;
     if (!filter) {      // the welded mesh as it is: no component pass
         WMeshDev m;
@@ -292,8 +292,20 @@ extern "C" int psgsdf_extract_mesh_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* 
         if (rc || d.nc == 0) return rc;      // (failed, or an empty mesh)
         in = d;
     }
-    if (in.nv > 0 && in.nf > 0) return lod_from_device(c, mem, in, cell, LodOut{xyz, normals, rgb, n_vertices, faces, n_faces, vertex_map, n_vertices_in, n_faces_in});
+    if (in.nv > 0 && in.nf > 0) return lod_from_device(c, mem, in, cell, o, dev);
     return hipStreamSynchronize(c->stream) != hipSuccess ? fail(c, PSGSDF_ERR_DEVICE, "%s: kernels", me) : PSGSDF_OK;
+}
+}  // namespace
+
+extern "C" int psgsdf_extract_mesh_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, const float** xyz, const float** normals, const uint8_t** rgb, int64_t* n_vertices,
+                                       const int32_t** faces, int64_t* n_faces, const int32_t** vertex_map, int64_t* n_vertices_in, int64_t* n_faces_in) {
+    const char* me = "extract_mesh_lod";
+    if (!xyz || !normals || !rgb || !n_vertices || !faces || !n_faces || !vertex_map || !n_vertices_in || !n_faces_in) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    if (int rc = lod_ready(c, me, filter, cell)) return rc;
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *xyz = nullptr; *normals = nullptr; *rgb = nullptr; *faces = nullptr; *vertex_map = nullptr; *n_vertices = 0; *n_faces = 0; *n_vertices_in = 0; *n_faces_in = 0;
+    DevMem mem(c);
+    return lod_stages(c, mem, me, filter, cell, LodOut{xyz, normals, rgb, n_vertices, faces, n_faces, vertex_map, n_vertices_in, n_faces_in});
 }
 
 namespace {
@@ -352,5 +364,64 @@ extern "C" int psgsdf_extract_mesh_fit(psgsdf_ctx* c, const float** xyz, const f
                                   {XO_IMESH_FACES, m.faces, sizeof(int) * 3 * nf, faces}, {XO_VFIT_NOBS, v_n, sizeof(int) * nv, vertex_n_obs}, {XO_VFIT_RMS, v_rms, sizeof(float) * nv, vertex_rms},
                                   {XO_VFIT_LOSS, v_loss, sizeof(float) * nv, vertex_loss}})) return rc;
     *n_vertices = m.nv; *n_faces = m.nf;
+    return PSGSDF_OK;
+}
+
+// ---- detail maps of the level-of-detail mesh (include/psgsdf_bake.h; kernel: bake.hip k_bake).  The clusters' device arrays are the kernel's mesh
+// (lod_from_device hands them out: nothing is uploaded again), the brick map comes from the renderer's prepare path.
+extern "C" int psgsdf_bake_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out) {
+    const char* me = "bake_lod";
+    if (!out) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    if (int rc = lod_ready(c, me, filter, cell)) return rc;
+    if (res < 1) return fail(c, PSGSDF_ERR_ARG, "%s: res %d (at least 1)", me, res);
+    if (!(reach > 0.0) || std::isinf(reach)) return fail(c, PSGSDF_ERR_ARG, "%s: the reach must be a finite length > 0", me);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *out = psgsdf_bake{};
+    DevMem mem(c);
+    MeshView lod;
+    if (int rc = lod_stages(c, mem, me, filter, cell, LodOut{&out->xyz, &out->normals, &out->rgb, &out->n_vertices, &out->faces, &out->n_faces, &out->vertex_map,
+                                                            &out->n_vertices_in, &out->n_faces_in}, &lod)) { *out = psgsdf_bake{}; return rc; }
+    if (lod.nf <= 0) return PSGSDF_OK;      // an empty level-of-detail mesh: all sizes 0
+    auto give_up = [&](int code, const char* what) { *out = psgsdf_bake{}; return fail(c, code, "%s: %s (%d faces, res %d)", me, what, lod.nf, res); };
+    // the atlas: two faces per block of (R + 1)^2 texels, the blocks in a near-square grid
+    psg::BakeArgs a{};
+    const long long B = (long long)res + 1, nblk = ((long long)lod.nf + 1) / 2;
+    long long bpr = (long long)sqrt((double)nblk);
+    while (bpr * bpr < nblk) ++bpr;
+    while (bpr > 1 && (bpr - 1) * (bpr - 1) >= nblk) --bpr;
+    const long long W = bpr * B, H = (nblk + bpr - 1) / bpr * B;
+    if (W > psg::kBakeMaxSide || H > psg::kBakeMaxSide) return give_up(PSGSDF_ERR_UNSUPPORTED, "the atlas would be larger than 16384 texels along a side");
+    { RenderArgs ra; int rc = render_prepare(c, mem, ra, me); if (rc) { *out = psgsdf_bake{}; return rc; } a.r = ra; }
+    a.has_band = c->inited ? 1 : 0;
+    a.xyz = lod.xyz; a.nrm = lod.nrm; a.rgb = lod.rgb; a.faces = lod.faces; a.nf = lod.nf;
+    a.res = res; a.bpr = (int)bpr; a.nblk = (int)nblk; a.W = (int)W; a.H = (int)H;
+    a.reach = reach; a.vs = (double)c->grid.vs;
+    const size_t px = (size_t)W * (size_t)H;
+    if (!mem.get(&a.albedo, 3 * px) || !mem.get(&a.normal, 3 * px) || !mem.get(&a.disp, px) || !mem.get(&a.voxel, px) || !mem.get(&a.face, px) || !mem.get(&a.counts, (size_t)psg::kBakeCounts))
+        return give_up(PSGSDF_ERR_DEVICE, "out of memory");
+    if (hipMemsetAsync(a.counts, 0, sizeof(unsigned long long) * psg::kBakeCounts, c->stream) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "memset");
+    timed(c, "bake", [&] { psg::launch_bake(a, c->stream); });
+    // the texture coordinates: integers over 6 W / 6 H, one division each
+    void* hu = nullptr;
+    if (int rc = host_out(c, XO_BAKE_UV, sizeof(float) * 6 * (size_t)lod.nf, &hu)) { *out = psgsdf_bake{}; return rc; }
+    float* uv = (float*)hu;
+    const long long R6 = 6 * (long long)res;
+    for (long long f = 0; f < lod.nf; ++f) {
+        const long long q = f >> 1, x0 = 6 * (q % bpr) * B, y0 = 6 * (q / bpr) * B;
+        const long long even[3][2] = {{1, 1}, {R6 + 7, 1}, {1, R6 + 7}}, odd[3][2] = {{R6 + 5, R6 + 5}, {-1, R6 + 5}, {R6 + 5, -1}};
+        for (int k = 0; k < 3; ++k) {
+            const long long* m = (f & 1) ? odd[k] : even[k];
+            uv[6 * f + 2 * k] = (float)((double)(x0 + m[0]) / (double)(6 * W));
+            uv[6 * f + 2 * k + 1] = (float)((double)(y0 + m[1]) / (double)(6 * H));
+        }
+    }
+    unsigned long long cnt[psg::kBakeCounts] = {};
+    if (hipMemcpyAsync(cnt, a.counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "download of the counts");
+    if (int rc = download(c, me, {{XO_BAKE_ALBEDO, a.albedo, 3 * px, &out->albedo}, {XO_BAKE_NORMAL, a.normal, sizeof(float) * 3 * px, &out->normal},
+                                  {XO_BAKE_DISPLACEMENT, a.disp, sizeof(float) * px, &out->displacement}, {XO_BAKE_VOXEL, a.voxel, sizeof(int) * px, &out->voxel},
+                                  {XO_BAKE_FACE, a.face, sizeof(int) * px, &out->face}})) { *out = psgsdf_bake{}; return rc; }
+    out->uv = uv; out->width = (int32_t)W; out->height = (int32_t)H;
+    out->n_texels = (int64_t)cnt[psg::BK_OWNED]; out->n_hits = (int64_t)cnt[psg::BK_HITS]; out->n_hits_off_band = (int64_t)cnt[psg::BK_OFF_BAND]; out->n_buried = (int64_t)cnt[psg::BK_BURIED];
+    out->n_misses = out->n_texels - out->n_hits - out->n_buried;
     return PSGSDF_OK;
 }

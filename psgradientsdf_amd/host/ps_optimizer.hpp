@@ -37,8 +37,10 @@
 #include "../../include/psgsdf_render.h"
 #include "../../include/psgsdf_mesh.h"
 #include "../../include/psgsdf_fit.h"
+#include "../../include/psgsdf_bake.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
+#include "obj_writer.hpp"
 
 namespace psgsdf_host {
 
@@ -101,6 +103,10 @@ inline psgsdf_mesh_filter& mesh_filter() { static psgsdf_mesh_filter f{0, 0.0, 0
 // voxelPS --mesh-lod S: next to every <name>_mesh.ply a <name>_mesh_lod.ply, the welded mesh (the filtered one, if a filter flag is given) with the vertices
 // of every cube of S voxels merged into one (psgsdf_extract_mesh_lod); 0: off; single process only
 inline double& mesh_lod_voxels() { static double v = 0.0; return v; }
+// voxelPS --mesh-bake R (with --mesh-lod S): next to every <name>_mesh_lod.ply the same mesh as <name>_mesh_lod.obj / .mtl with the reconstruction's detail
+// baked into <name>_mesh_lod_albedo.png and <name>_mesh_lod_normal.png (object space), R texels along a triangle's edge, rays from one cell outside
+// (psgsdf_bake_lod); 0: off; single process only
+inline int& mesh_bake_res() { static int v = 0; return v; }
 // voxelPS --mesh-fit: next to every <name>_mesh.ply a <name>_mesh_fit.ply, the welded mesh with the photometric fit of every vertex (psgsdf_extract_mesh_fit): how many
 // keyframes saw it, the rms residual and the mean robust loss; single process only
 inline bool& mesh_fit() { static bool v = false; return v; }
@@ -518,7 +524,12 @@ struct VolumetricGradSdf {
         psgsdf_info info{}; psgsdf_get_info(ctx, &info);
         const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr; const int32_t* vmap = nullptr;
         int64_t nv = 0, nf = 0, nv_in = 0, nf_in = 0;
-        if (psgsdf_extract_mesh_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, mesh_lod_voxels() * (double)info.voxel_size, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vmap, &nv_in, &nf_in) != 0
+        const double cell = mesh_lod_voxels() * (double)info.voxel_size;
+        psgsdf_bake bk{};      // --mesh-bake: the same level-of-detail arrays (bit for bit) and the atlas, in one call
+        if (mesh_bake_res() > 0) {
+            if (psgsdf_bake_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &bk) != 0 || bk.n_faces_in == 0) return false;
+            xyz = bk.xyz; nrm = bk.normals; rgb = bk.rgb; faces = bk.faces; nv = bk.n_vertices; nf = bk.n_faces; nv_in = bk.n_vertices_in; nf_in = bk.n_faces_in;
+        } else if (psgsdf_extract_mesh_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vmap, &nv_in, &nf_in) != 0
             || nf_in == 0) return false;
         char line[200];
         snprintf(line, sizeof line, "comment lod cell %.9g voxels from %lld vertices %lld faces\n", mesh_lod_voxels(), (long long)nv_in, (long long)nf_in);
@@ -531,6 +542,22 @@ struct VolumetricGradSdf {
                 std::cout << "couldn't save the level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure();
             }
         });
+        if (mesh_bake_res() > 0 && bk.width > 0) {
+            const int W = bk.width, H = bk.height; const size_t px = (size_t)W * H;
+            auto uv = std::make_shared<std::vector<float>>(bk.uv, bk.uv + 6 * nf);
+            auto alb = std::make_shared<std::vector<uint8_t>>(bk.albedo, bk.albedo + 3 * px);
+            auto nmap = std::make_shared<std::vector<uint8_t>>(3 * px);
+            for (size_t q = 0; q < 3 * px; ++q) (*nmap)[q] = normal_to_u8(bk.normal[q]);
+            std::cout << "baked " << bk.n_texels << " texels onto " << nf << " faces (" << W << " x " << H << "): " << bk.n_hits << " hits (" << bk.n_hits_off_band << " off the band), "
+                      << bk.n_buried << " buried, " << bk.n_misses << " misses" << std::endl;
+            DumpQueue::get().push([=] {
+                const std::string lod = base + "_mesh_lod";
+                bool ok = write_obj_bake(lod + ".obj", lod + ".mtl", lod + "_albedo.png", lod + "_normal.png", vx->data(), vn->data(), (size_t)nv, vf->data(), uv->data(), (size_t)nf);
+                ok = write_png(lod + "_albedo.png", W, H, 3, alb->data()) && ok;
+                ok = write_png(lod + "_normal.png", W, H, 3, nmap->data()) && ok;
+                if (!ok) { std::cout << "couldn't save the baked level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure(); }
+            });
+        }
         return true;
     }
     // <name>_mesh.ply -> <name>_mesh_fit.ply (write_mesh_fit_ply).  Before psgsdf_init there is no band: the mesh of psgsdf_extract_mesh_indexed with zeros

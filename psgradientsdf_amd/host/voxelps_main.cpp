@@ -130,6 +130,23 @@ static int selftest_ply_fit(const char* path) {
     return psgsdf_host::write_mesh_fit_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, rms, loss, n_obs) ? 0 : 1;
 }
 
+// `--selftest-obj-bake out.obj`: the same octahedron with made-up texture coordinates (dyadic, so that 1 - v is exact) through the writer of
+// `--mesh-bake` -- out.obj, out.mtl -- and three normals through the normal map's byte rule into out_normal.png (tests/test_bake_cpu.py parses them back)
+static int selftest_obj_bake(const char* path) {
+    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
+    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
+    float uv[8][3][2];
+    for (int f = 0; f < 8; ++f) for (int k = 0; k < 3; ++k) { uv[f][k][0] = (3 * f + k) / 32.0f; uv[f][k][1] = (f + k) / 16.0f; }
+    std::string base = path;
+    if (base.size() > 4 && base.compare(base.size() - 4, 4, ".obj") == 0) base.resize(base.size() - 4);
+    const float nm[3][3] = {{1.0f, 0.0f, -1.0f}, {0.0f, 0.0f, 0.0f}, {0.5f, -0.5f, 0.25f}};
+    uint8_t px[9];
+    for (int q = 0; q < 9; ++q) px[q] = psgsdf_host::normal_to_u8((&nm[0][0])[q]);
+    const bool ok = psgsdf_host::write_obj_bake(path, base + ".mtl", base + "_albedo.png", base + "_normal.png", &xyz[0][0], &nrm[0][0], 6, &faces[0][0], &uv[0][0][0], 8);
+    return ok && psgsdf_host::write_png(base + "_normal.png", 3, 1, 3, px) ? 0 : 1;
+}
+
 // the focus measure of one colour PNG as the keyframe selector computes it (SharpDetector.h:22-37), and the keyframe sub-sampling of
 // main_ps.cpp:392-421 on the index list 0..n-1: tests/test_host_tools.py compares both with numpy / scipy restatements (no GPU needed)
 static int selftest_lapm(const char* path) {
@@ -235,10 +252,12 @@ int main(int argc, char* argv[]) {
     if (argc >= 4 && std::string(argv[1]) == "--selftest-mc-ply") return selftest_mc_ply(atoi(argv[2]), argv[3]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-fit") return selftest_ply_fit(argv[2]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-obj-bake") return selftest_obj_bake(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
     std::string filter_flag;                  // the last of --mesh-min-faces / --mesh-keep-largest given
     bool lod_flag = false, lod_ok = true;     // --mesh-lod S given / S is a number > 0
+    bool bake_flag = false, bake_ok = true;   // --mesh-bake R given / R is a whole number >= 1
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
@@ -248,6 +267,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-min-faces" && i + 1 < argc) { mesh_filter().min_faces = atoll(argv[++i]); clean_mesh() = true; filter_flag = a; }      // <name>_mesh_clean.ply + <name>_mesh_components.txt next to every <name>_mesh.ply:
         else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
         else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_lod_voxels() = lod_ok ? v : 0.0; lod_flag = true; }      // <name>_mesh_lod.ply next to every <name>_mesh.ply: the vertices of every cube of S voxels merged (include/psgsdf_mesh.h psgsdf_extract_mesh_lod)
+        else if (a == "--mesh-bake" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); bake_ok = end != argv[i] && *end == 0 && v >= 1 && v <= 16383; mesh_bake_res() = bake_ok ? (int)v : 0; bake_flag = true; }      // with --mesh-lod: <name>_mesh_lod.obj / .mtl / _albedo.png / _normal.png next to every <name>_mesh_lod.ply: the reconstruction's albedo and normals baked onto the coarse mesh, R texels along a triangle's edge (include/psgsdf_bake.h)
         else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
@@ -259,7 +279,10 @@ int main(int argc, char* argv[]) {
     if (transport != "rccl" && transport != "sockets") { std::cerr << "--transport: rccl or sockets" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && host_writers()) { std::cerr << "--host-writers is the single-process cross-check" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && clean_mesh()) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
+    if (bake_flag && !bake_ok) { std::cerr << "--mesh-bake: texels along a triangle's edge, a whole number >= 1" << std::endl; return 1; }
+    if (bake_flag && !lod_flag) { std::cerr << "--mesh-bake needs --mesh-lod S: the maps are baked onto the level-of-detail mesh" << std::endl; return 1; }
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && bake_flag) { std::cerr << "--mesh-bake needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && lod_flag) { std::cerr << "--mesh-lod needs a single process: clusters are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && mesh_fit()) { std::cerr << "--mesh-fit needs a single process: the fit is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }

@@ -3,6 +3,8 @@ the welded mesh with its connected components labelled and filtered (psgsdf_extr
 and sizes of the level-of-detail mesh at cells of 2 and 4 voxels, without and with keep_largest = 1 (psgsdf_extract_mesh_lod; it repeats both).
 Then the photometric fit (include/psgsdf_fit.h): psgsdf_band_fit next to psgsdf_energy (the same gathers and arithmetic: k_band_fit stores 24 B per row
 where k_energy reduces) and psgsdf_extract_mesh_fit next to psgsdf_extract_mesh_indexed (it adds k_band_fit and k_wmesh_fit).
+Then the detail maps (include/psgsdf_bake.h): psgsdf_bake_lod at the same cells with 8 texels along an edge (it repeats the level-of-detail call and adds
+k_render_bricks and k_bake), its atlas sizes and counts.
 Wall-clock per call (host clock; both calls end in a stream synchronise) and the kernels' own times from psgsdf_kernel_times:
     python tools/time_mesh.py sokrates [reps]      the sokrates fixture fused at its poses (128^3 at 4 mm), one iteration
     python tools/time_mesh.py N [reps]             a synthetic SH1 scene on an N^3 grid
@@ -11,7 +13,7 @@ For the kernel times of record run it under the tracer in a run of its own:
 (kernel names: k_wmesh_mark, k_wmesh_faces, k_wmesh_verts, k_wmesh_or (multi-rank only) against k_mc_count, k_mc_emit; both share k_box_*, k_cscan_*;
 the components: k_mcomp_init, _hook, _flatten, _edges, _vstats, _fstats, _ecount, and with a filter that drops something _keep, _compact;
 the level of detail: k_mlod_cluster, _ftable, _fkeep, _vflag, _emit -- one launch of each per call, so their averages mix the two cell sizes:
-PSGSDF_TIME_MESH_LOD=2 or =4 restricts the run to one of them; the fit: k_band_fit against k_energy, k_wmesh_fit against k_wmesh_verts)."""
+PSGSDF_TIME_MESH_LOD=2 or =4 restricts the run to one of them (k_bake's average likewise); the fit: k_band_fit against k_energy, k_wmesh_fit against k_wmesh_verts)."""
 import json
 import os
 import sys
@@ -58,6 +60,10 @@ for s in lod_cells:
         m = eng.extract_mesh_lod(s * vs, **flt)
         lod_sizes[f"{s}vs_{name}"] = {"vertices_in": m["n_vertices_in"], "faces_in": m["n_faces_in"], "vertices": len(m["xyz"]), "faces": len(m["faces"]),
                                       "ply_body_bytes": 27 * len(m["xyz"]) + 13 * len(m["faces"])}
+bake_sizes = {}
+for s in lod_cells:
+    b = eng.bake_lod(s * vs, 8)
+    bake_sizes[f"{s}vs"] = {"faces": len(b["faces"]), "width": b["width"], "height": b["height"], **{k: b[k] for k in ("n_texels", "n_hits", "n_hits_off_band", "n_buried", "n_misses")}}
 eng.energy(); eng.band_fit(); fit = eng.extract_mesh_fit()
 eng.reset_kernel_times()
 eng.set_profiling(True)
@@ -82,6 +88,12 @@ for s in lod_cells:
         for _ in range(reps):
             eng.extract_mesh_lod(s * vs, **flt)
         t_lod[f"{s}vs_{name}"] = (time.perf_counter() - t0) / reps
+t_bake = {}
+for s in lod_cells:
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        eng.bake_lod(s * vs, 8)
+    t_bake[f"{s}vs"] = (time.perf_counter() - t0) / reps
 t_fit = {}
 for name, call in (("energy_ms", eng.energy), ("band_fit_ms", eng.band_fit), ("extract_mesh_fit_ms", eng.extract_mesh_fit)):
     t0 = time.perf_counter()
@@ -94,7 +106,8 @@ V, Fc = len(xyz), len(faces)
 print(json.dumps({"state": what, "grid": list(eng.info().dim), "extract_mesh_ms": round(1e3 * t_plain, 3), "extract_mesh_indexed_ms": round(1e3 * t_idx, 3),
                   "extract_mesh_components_ms": {k: round(1e3 * v, 3) for k, v in t_cc.items()},
                   "extract_mesh_lod_ms": {k: round(1e3 * v, 3) for k, v in t_lod.items()}, "lod": lod_sizes,
-                  "kernel_ms_per_launch": {k: round(ms / max(n, 1), 4) for k, (ms, n) in kt.items() if k.startswith(("mc_", "wmesh_", "mcomp_", "mlod_")) or k in ("band_fit", "energy")},
+                  "bake_lod_ms": {k: round(1e3 * v, 3) for k, v in t_bake.items()}, "bake": bake_sizes,
+                  "kernel_ms_per_launch": {k: round(ms / max(n, 1), 4) for k, (ms, n) in kt.items() if k.startswith(("mc_", "wmesh_", "mcomp_", "mlod_")) or k in ("band_fit", "energy", "bake", "k_render_bricks")},
                   **t_fit, "fit": {"n_band": int(eng.info().n_band), "vertex_observations": int(fit["n_obs"].sum()), "vertices_observed": int((fit["n_obs"] > 0).sum())},
                   "faces": Fc, "components": len(comps), "largest_component_faces": int(comps["n_faces"].max()) if len(comps) else 0, "vertices_indexed": V, "vertices_non_indexed": len(xn),
                   "indexed_ply_body_bytes": 27 * V + 13 * Fc}))
