@@ -428,6 +428,7 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* ctx, int64_t out[8]);
  *   PSGSDF_XR, PSGSDF_XF, PSGSDF_XS, PSGSDF_XH (0: that exchange through the communicator instead of IPC-mapped memory), PSGSDF_XR_MEM* (fine | uncached |
  *   coarse), PSGSDF_XWAIT_LOG2 (log2 of the polls an in-kernel wait for another rank may take), PSGSDF_CU_MASK (lo:hi)              multi-rank
  *   PSGSDF_WAIT_TIMEOUT_S*, PSGSDF_DESTROY_TIMEOUT_S*, PSGSDF_SOLVE_DUMP*                                                           host waits / diagnostics
+ *   PSGSDF_AO_CUT (0: the rays of psgsdf_occlusion.h walk on past their radius; the same bits)                                     ambient occlusion
  * DESIGN.md section 4 has the table with defaults and measured effects.
  * NOT in libpsgsdf.so: PSGSDF_FAULT_SOLVE, PSGSDF_FAULT_HALO (fault injection), PSGSDF_PCG_ABLATE (timing ablations: results are WRONG),
  * PSGSDF_MBOX_CHECK=0 (re-opens a race fixed in round 3).  They exist only in the development build libpsgsdf_dev.so (-DPSGSDF_DEV) the tests and

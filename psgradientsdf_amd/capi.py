@@ -86,6 +86,19 @@ class Bake(C.Structure):      # psgsdf_bake (include/psgsdf_bake.h)
                 ("n_texels", C.c_int64), ("n_hits", C.c_int64), ("n_hits_off_band", C.c_int64), ("n_buried", C.c_int64), ("n_misses", C.c_int64)]
 
 
+class AoParams(C.Structure):      # psgsdf_ao_params (include/psgsdf_occlusion.h)
+    _fields_ = [("n_dirs", C.c_int32), ("reserved", C.c_int32), ("radius", C.c_double), ("bias", C.c_double)]
+
+
+class AoCounts(C.Structure):      # psgsdf_ao_counts
+    _fields_ = [("n_samples", C.c_int64), ("n_valid", C.c_int64), ("n_rays", C.c_int64), ("n_occluded", C.c_int64), ("n_buried", C.c_int64)]
+
+
+class BakeAo(C.Structure):      # psgsdf_bake_ao
+    _fields_ = [("bake", Bake), ("occlusion", C.POINTER(C.c_uint8)), ("mask", C.POINTER(C.c_uint64)), ("dirs", C.POINTER(C.c_double)),
+                ("n_dirs", C.c_int32), ("reserved", C.c_int32), ("counts", AoCounts)]
+
+
 # psgsdf_mesh_component (include/psgsdf_mesh.h), 88 bytes
 MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_faces", "<i8"), ("n_edges", "<i8"), ("n_boundary_edges", "<i8"),
                                  ("n_nonmanifold_edges", "<i8"), ("area", "<f8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("kept", "<i4"), ("reserved", "<i4")])
@@ -463,6 +476,10 @@ class Api:
         b = Bake()
         self._check(self._fn("bake_lod")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
                                          C.c_double(float(cell if reach is None else reach)), C.byref(b)), "bake_lod")
+        return self._bake_dict(b)
+
+    @staticmethod
+    def _bake_dict(b):
         V, F, Vi, W, H = b.n_vertices, b.n_faces, b.n_vertices_in, b.width, b.height
         arr = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
         out = dict(xyz=arr(b.xyz, (V, 3), np.float32), normals=arr(b.normals, (V, 3), np.float32), rgb=arr(b.rgb, (V, 3), np.uint8), faces=arr(b.faces, (F, 3), np.int32),
@@ -471,6 +488,45 @@ class Api:
                    displacement=arr(b.displacement, (H, W), np.float32), voxel=arr(b.voxel, (H, W), np.int32), face=arr(b.face, (H, W), np.int32))
         for k in ("n_texels", "n_hits", "n_hits_off_band", "n_buried", "n_misses"):
             out[k] = int(getattr(b, k))
+        return out
+
+    # -- ambient occlusion (include/psgsdf_occlusion.h)
+    def _ao_params(self, n_dirs, radius, bias):
+        vs = float(np.float32(self.info().voxel_size))
+        return AoParams(int(n_dirs), 0, float(8 * vs if radius is None else radius), float(vs if bias is None else bias))
+
+    def occlusion_points(self, xyz, normals, n_dirs=16, radius=None, bias=None):
+        """Ambient occlusion of the reconstructed surface at the caller's points xyz [n, 3] and normals [n, 3] (float32, the mesh's units;
+        psgsdf_occlusion_points): n_dirs (8, 16, 32 or 64) cosine-weighted rays per point, each occluded if it meets the surface within `radius`
+        (None: 8 voxels) of its origin, which is lifted off the point by `bias` (None: 1 voxel) along the normal.  dict of occlusion [n] uint8
+        (255: open), mask [n] uint64 (bit i: ray i is occluded), dirs [n_dirs, 3] float64 and counts, a dict of n_samples, n_valid, n_rays, n_occluded,
+        n_buried (the last two count rays).  Single contexts only."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3); normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(xyz) != len(normals):
+            raise ValueError("occlusion_points: xyz and normals differ in length")
+        n, p = len(xyz), self._ao_params(n_dirs, radius, bias)
+        mask = C.POINTER(C.c_uint64)(); occ = C.POINTER(C.c_uint8)(); dirs = C.POINTER(C.c_double)(); cnt = AoCounts()
+        self._check(self._fn("occlusion_points")(self.ctx, xyz.ctypes.data_as(C.POINTER(C.c_float)), normals.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(n), C.byref(p),
+                                                 C.byref(mask), C.byref(occ), C.byref(dirs), C.byref(cnt)), "occlusion_points")
+        out = dict(occlusion=np.ctypeslib.as_array(occ, shape=(n,)).copy() if n else np.zeros(0, np.uint8),
+                   mask=np.ctypeslib.as_array(mask, shape=(n,)).copy() if n else np.zeros(0, np.uint64), dirs=np.ctypeslib.as_array(dirs, shape=(p.n_dirs, 3)).copy())
+        out["counts"] = {k: int(getattr(cnt, k)) for k, _ in AoCounts._fields_}
+        return out
+
+    def bake_lod_ao(self, cell, res, reach=None, n_dirs=16, radius=None, bias=None, min_faces=0, min_area=0.0, keep_largest=0):
+        """bake_lod's dict for the same arguments (bit for bit) plus the ambient-occlusion map of the atlas (psgsdf_bake_lod_ao): occlusion [H, W]
+        uint8 (255: open; padding 0), mask [H, W] uint64, dirs [n_dirs, 3] float64 and counts, a dict of n_samples (the owned texels), n_valid,
+        n_rays, n_occluded, n_buried (rays; the bake's own n_buried, texels, stays where it is).  n_dirs, radius, bias: as for occlusion_points.  Single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        b, p = BakeAo(), self._ao_params(n_dirs, radius, bias)
+        self._check(self._fn("bake_lod_ao")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
+                                            C.c_double(float(cell if reach is None else reach)), C.byref(p), C.byref(b)), "bake_lod_ao")
+        out = self._bake_dict(b.bake)
+        W, H = b.bake.width, b.bake.height
+        out["occlusion"] = np.ctypeslib.as_array(b.occlusion, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint8)
+        out["mask"] = np.ctypeslib.as_array(b.mask, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint64)
+        out["dirs"] = np.ctypeslib.as_array(b.dirs, shape=(b.n_dirs, 3)).copy()
+        out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in AoCounts._fields_}
         return out
 
     # -- the photometric fit resolved over the surface (include/psgsdf_fit.h)

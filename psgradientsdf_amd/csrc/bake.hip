@@ -11,15 +11,6 @@ namespace psg {
 
 __device__ __forceinline__ unsigned char bake_byte(float c) { return (unsigned char)(int)floorf(255.0f * fminf(fmaxf(c, 0.0f), 1.0f) + 0.5f); }      // (mesh.hip colour_byte)
 
-// v / |v| in double; false (and v untouched) if |v| is zero
-__device__ __forceinline__ bool bake_unit(double* v) {
-#pragma clang fp contract(off)
-    const double len = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    if (!(len > 0.0)) return false;
-    v[0] /= len; v[1] /= len; v[2] /= len;
-    return true;
-}
-
 __global__ void __launch_bounds__(64) k_bake(BakeArgs a) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
@@ -43,22 +34,9 @@ __global__ void __launch_bounds__(64) k_bake(BakeArgs a) {
     int vox = -1;
     bool hit = false, buried = false, off = false;
     if (owned) {
-        const double w1 = (3.0 * ta + 1.0) / (3.0 * (R + 1)), w2 = (3.0 * tb + 1.0) / (3.0 * (R + 1)), w0 = 1.0 - w1 - w2;
-        const int v0 = a.faces[3 * (size_t)f], v1 = a.faces[3 * (size_t)f + 1], v2 = a.faces[3 * (size_t)f + 2];
-        double p[3], n[3], x0[3], x1[3], x2[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            x0[k] = (double)a.xyz[3 * (size_t)v0 + k]; x1[k] = (double)a.xyz[3 * (size_t)v1 + k]; x2[k] = (double)a.xyz[3 * (size_t)v2 + k];
-            p[k] = (w0 * x0[k] + w1 * x1[k]) + w2 * x2[k];
-            n[k] = (w0 * (double)a.nrm[3 * (size_t)v0 + k] + w1 * (double)a.nrm[3 * (size_t)v1 + k]) + w2 * (double)a.nrm[3 * (size_t)v2 + k];
-        }
-        bool ray = bake_unit(n);
-        if (!ray) {      // the vertex normals cancel: the triangle's own
-            const double e1[3] = {x1[0] - x0[0], x1[1] - x0[1], x1[2] - x0[2]}, e2[3] = {x2[0] - x0[0], x2[1] - x0[1], x2[2] - x0[2]};
-            n[0] = e1[1] * e2[2] - e1[2] * e2[1]; n[1] = e1[2] * e2[0] - e1[0] * e2[2]; n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-            ray = bake_unit(n);
-            if (!ray) { n[0] = 0.0; n[1] = 0.0; n[2] = 0.0; }
-        }
+        double w0, w1, w2, p[3], n[3];
+        int v0, v1, v2;
+        const bool ray = bake_sample(a.xyz, a.nrm, a.faces, f, ta, tb, R, w0, w1, w2, v0, v1, v2, p, n);
         float t = 0.f; long long lin = -1;
         if (ray) {
             float uo[3], uw[3];

@@ -2,7 +2,8 @@
 // meshes"), its connected components and the mesh without its small pieces (mesh_cc.hip; "Mesh components") and a level-of-detail mesh by vertex
 // clustering (mesh_lod.hip; "Level of detail"); and the C ABI of include/psgsdf_fit.h: the photometric fit per band row and per vertex of the welded
 // mesh (fit.hip; "Photometric fit per voxel and vertex"); and the C ABI of include/psgsdf_bake.h: detail maps of the level-of-detail mesh (bake.hip;
-// "Baked detail maps").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
+// "Baked detail maps"); and the C ABI of include/psgsdf_occlusion.h: ambient occlusion at the caller's points and as a map of the bake
+// (occlusion.hip; "Ambient occlusion").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
 // welded mesh -> vertex fit -- that hand each other device arrays whose kernels may still be in flight.  The CALL owns all device memory of its
 // stages in one DevMem, which waits for the stream and frees when the call returns, whichever way it returns: a stage allocates from it and never frees.
 // The frame arithmetic (extract_internal.h crop_frame) runs on the host and its results are compared bit for bit: no FMA contraction here either.
@@ -11,8 +12,10 @@
 #include "../../include/psgsdf_mesh.h"
 #include "../../include/psgsdf_fit.h"
 #include "../../include/psgsdf_bake.h"
+#include "../../include/psgsdf_occlusion.h"
 #include "mesh_lod.h"
 #include "bake.h"
+#include "occlusion.h"
 
 using namespace psge;
 
@@ -369,15 +372,18 @@ extern "C" int psgsdf_extract_mesh_fit(psgsdf_ctx* c, const float** xyz, const f
 
 // ---- detail maps of the level-of-detail mesh (include/psgsdf_bake.h; kernel: bake.hip k_bake).  The clusters' device arrays are the kernel's mesh
 // (lod_from_device hands them out: nothing is uploaded again), the brick map comes from the renderer's prepare path.
-extern "C" int psgsdf_bake_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out) {
-    const char* me = "bake_lod";
-    if (!out) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+namespace {
+// what psgsdf_bake_lod and psgsdf_bake_lod_ao check first
+int bake_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach) {
     if (int rc = lod_ready(c, me, filter, cell)) return rc;
     if (res < 1) return fail(c, PSGSDF_ERR_ARG, "%s: res %d (at least 1)", me, res);
     if (!(reach > 0.0) || std::isinf(reach)) return fail(c, PSGSDF_ERR_ARG, "%s: the reach must be a finite length > 0", me);
-    { int rc = extract_ready(c, me); if (rc) return rc; }
+    return PSGSDF_OK;
+}
+// the bake of both calls, its results in their pinned host slots (the stream has been waited for); dev (if asked for): the kernel's arguments, the
+// atlas's device planes among them (dev->nf == 0: an empty level-of-detail mesh, nothing was baked)
+int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out, psg::BakeArgs* dev = nullptr) {
     *out = psgsdf_bake{};
-    DevMem mem(c);
     MeshView lod;
     if (int rc = lod_stages(c, mem, me, filter, cell, LodOut{&out->xyz, &out->normals, &out->rgb, &out->n_vertices, &out->faces, &out->n_faces, &out->vertex_map,
                                                             &out->n_vertices_in, &out->n_faces_in}, &lod)) { *out = psgsdf_bake{}; return rc; }
@@ -423,5 +429,121 @@ extern "C" int psgsdf_bake_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, 
     out->uv = uv; out->width = (int32_t)W; out->height = (int32_t)H;
     out->n_texels = (int64_t)cnt[psg::BK_OWNED]; out->n_hits = (int64_t)cnt[psg::BK_HITS]; out->n_hits_off_band = (int64_t)cnt[psg::BK_OFF_BAND]; out->n_buried = (int64_t)cnt[psg::BK_BURIED];
     out->n_misses = out->n_texels - out->n_hits - out->n_buried;
+    if (dev) *dev = a;
+    return PSGSDF_OK;
+}
+}  // namespace
+
+extern "C" int psgsdf_bake_lod(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out) {
+    const char* me = "bake_lod";
+    if (!out) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    if (int rc = bake_ready(c, me, filter, cell, res, reach)) return rc;
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    DevMem mem(c);
+    return bake_device(c, mem, me, filter, cell, res, reach, out);
+}
+
+// ---- ambient occlusion (include/psgsdf_occlusion.h; kernel: occlusion.hip k_occlusion): K short rays per sample through the renderer's walk, the
+// samples either the caller's points or the texels of a bake, whose planes are still on the device when the rays start from them.
+namespace {
+int ao_bad_params(psgsdf_ctx* c, const char* me, const psgsdf_ao_params* p) {
+    if (!p) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    if ((p->n_dirs != 8 && p->n_dirs != 16 && p->n_dirs != 32 && p->n_dirs != 64) || p->reserved != 0)
+        return fail(c, PSGSDF_ERR_ARG, "%s: n_dirs %d, reserved %d (8, 16, 32 or 64 directions; reserved 0)", me, p->n_dirs, p->reserved);
+    if (!(p->radius > 0.0) || std::isinf(p->radius) || !(p->bias > 0.0) || std::isinf(p->bias)) return fail(c, PSGSDF_ERR_ARG, "%s: radius and bias must be finite lengths > 0", me);
+    return PSGSDF_OK;
+}
+// the direction table into its pinned slot (the definition's arithmetic, in double)
+int ao_dirs(psgsdf_ctx* c, int K, const double** dirs) {
+    void* h = nullptr;
+    if (int rc = host_out(c, XO_AO_DIRS, sizeof(double) * 3 * (size_t)K, &h)) return rc;
+    double* D = (double*)h;
+    const double g = 0.6180339887498949, pi = 3.141592653589793;
+    for (int i = 0; i < K; ++i) {
+        const double u = ((double)i + 0.5) / (double)K, r = sqrt(u), z = sqrt(1.0 - u), phi = 2.0 * pi * ((double)i * g - floor((double)i * g));
+        D[3 * i] = r * cos(phi); D[3 * i + 1] = r * sin(phi); D[3 * i + 2] = z;
+    }
+    *dirs = D;
+    return PSGSDF_OK;
+}
+// the arguments both providers share (a.n and the provider's own arrays are set by the caller before): brick map, table, results, counts; launch; download
+int ao_run(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_ao_params& p, const double* dirs_host, psg::OcclusionArgs& a, bool bake, XoSlot s_mask, XoSlot s_occ,
+           const uint64_t** mask, const uint8_t** occlusion, psgsdf_ao_counts* counts) {
+    const int K = p.n_dirs;
+    a.K = K; a.log2K = K == 8 ? 3 : K == 16 ? 4 : K == 32 ? 5 : 6;
+    a.radius = p.radius; a.bias = p.bias; a.vs = (double)c->grid.vs;
+    a.t_max = (float)p.radius;      // rounded up if the conversion rounded down: no hit within the radius is cut off
+    if ((double)a.t_max < p.radius) a.t_max = nextafterf(a.t_max, INFINITY);
+    if (!c->ao_cut) a.t_max = FLT_MAX;      // (PSGSDF_AO_CUT=0; tools/time_mesh.py: what the cut buys -- the same bits)
+    double* d_dirs = nullptr;
+    const size_t n = (size_t)a.n;
+    if (!mem.get(&d_dirs, 3 * (size_t)K) || !mem.get(&a.mask, n) || !mem.get(&a.occ, n) || !mem.get(&a.counts, (size_t)psg::kAoCounts))
+        return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld samples)", me, a.n);
+    a.dirs = d_dirs;
+    if (hipMemcpyAsync(d_dirs, dirs_host, sizeof(double) * 3 * (size_t)K, hipMemcpyHostToDevice, c->stream) != hipSuccess
+        || hipMemsetAsync(a.counts, 0, sizeof(unsigned long long) * psg::kAoCounts, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: upload", me);
+    hipError_t launched = hipSuccess;
+    timed(c, "occlusion", [&] { launched = psg::launch_occlusion(a, bake, c->stream); });
+    if (launched != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld rays: %s", me, a.n * K, hipGetErrorString(launched));
+    unsigned long long cnt[psg::kAoCounts] = {};
+    if (hipMemcpyAsync(cnt, a.counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the counts", me);
+    if (int rc = download(c, me, {{s_mask, a.mask, sizeof(uint64_t) * n, mask}, {s_occ, a.occ, n, occlusion}})) return rc;
+    counts->n_samples = (int64_t)cnt[psg::AO_SAMPLES]; counts->n_valid = (int64_t)cnt[psg::AO_VALID]; counts->n_rays = (int64_t)K * counts->n_valid;
+    counts->n_occluded = (int64_t)cnt[psg::AO_OCCLUDED]; counts->n_buried = (int64_t)cnt[psg::AO_BURIED];
+    return PSGSDF_OK;
+}
+}  // namespace
+
+extern "C" int psgsdf_occlusion_points(psgsdf_ctx* c, const float* xyz, const float* normals, int64_t n, const psgsdf_ao_params* params,
+                                       const uint64_t** mask, const uint8_t** occlusion, const double** dirs, psgsdf_ao_counts* counts) {
+    const char* me = "occlusion_points";
+    if (!mask || !occlusion || !dirs || !counts || (n > 0 && (!xyz || !normals))) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    // (before anything collective and before any device work: no rank waits for another)
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): a slab holds only its own planes of the volume", me, c->rank, c->n_ranks);
+    if (int rc = ao_bad_params(c, me, params)) return rc;
+    if (n < 0) return fail(c, PSGSDF_ERR_ARG, "%s: %lld points", me, (long long)n);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *mask = nullptr; *occlusion = nullptr; *dirs = nullptr; *counts = psgsdf_ao_counts{};
+    const double* D = nullptr;
+    if (int rc = ao_dirs(c, params->n_dirs, &D)) return rc;
+    if (n > 0) {
+        DevMem mem(c);
+        psg::OcclusionArgs a{};
+        { RenderArgs ra; int rc = render_prepare(c, mem, ra, me); if (rc) return rc; a.r = ra; }
+        a.n = (long long)n;
+        float *d_xyz = nullptr, *d_nrm = nullptr;
+        if (!mem.get(&d_xyz, 3 * (size_t)n) || !mem.get(&d_nrm, 3 * (size_t)n)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld points)", me, (long long)n);
+        if (hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream) != hipSuccess
+            || hipMemcpyAsync(d_nrm, normals, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: upload", me);
+        a.pts = d_xyz; a.pts_n = d_nrm;
+        psgsdf_ao_counts cn{};
+        if (int rc = ao_run(c, mem, me, *params, D, a, false, XO_AO_MASK, XO_AO_OCCLUSION, mask, occlusion, &cn)) { *mask = nullptr; *occlusion = nullptr; return rc; }
+        *counts = cn;
+    }
+    *dirs = D;
+    return PSGSDF_OK;
+}
+
+extern "C" int psgsdf_bake_lod_ao(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, const psgsdf_ao_params* params, psgsdf_bake_ao* out) {
+    const char* me = "bake_lod_ao";
+    if (!out) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    if (int rc = bake_ready(c, me, filter, cell, res, reach)) return rc;
+    if (int rc = ao_bad_params(c, me, params)) return rc;
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *out = psgsdf_bake_ao{};
+    DevMem mem(c);
+    psg::BakeArgs b{};
+    if (int rc = bake_device(c, mem, me, filter, cell, res, reach, &out->bake, &b)) return rc;
+    const double* D = nullptr;
+    if (int rc = ao_dirs(c, params->n_dirs, &D)) { *out = psgsdf_bake_ao{}; return rc; }
+    out->n_dirs = params->n_dirs;
+    if (b.nf > 0) {
+        psg::OcclusionArgs a{};
+        a.r = b.r; a.n = (long long)b.W * b.H;
+        a.xyz = b.xyz; a.nrm = b.nrm; a.faces = b.faces; a.res = b.res; a.W = b.W;
+        a.normal = b.normal; a.disp = b.disp; a.voxel = b.voxel; a.face = b.face;
+        if (int rc = ao_run(c, mem, me, *params, D, a, true, XO_BAKE_AO_MASK, XO_BAKE_AO_OCCLUSION, &out->mask, &out->occlusion, &out->counts)) { *out = psgsdf_bake_ao{}; return rc; }
+    }
+    out->dirs = D;
     return PSGSDF_OK;
 }

@@ -1,5 +1,5 @@
 // render_trace.h -- the renderer's cell walk and first-order surface model, shared by the kernels that trace rays through the
-// reconstruction: render.hip (one ray per pixel of a view) and bake.hip (one ray per texel of a level-of-detail mesh's atlas).  One copy of the
+// reconstruction: render.hip (one ray per pixel of a view), bake.hip (one ray per texel of a level-of-detail mesh's atlas) and occlusion.hip (K short rays per sample).  One copy of the
 // arithmetic: whatever traces through this function meets the same cells, crossings and hit parameters.
 #pragma once
 #include "device_common.h"
@@ -13,8 +13,11 @@ namespace psg {
 // MR (a slab of a multi-rank context): the same walk over the same global brick map -- the same cells, crossings and t -- but only cells of the
 // owned planes a.zr are evaluated (dense planes at the local index lin - koff nx ny), and the walk ends once the ray has left them in its direction
 // of travel.  Along a ray z is monotonic, so the single-rank hit is the hit of the first slab (in the direction of travel) that has one.
-template <bool MR>
-__device__ __forceinline__ bool render_trace(const RenderArgs& a, const float* uo, const float* uw, float& t_hit, long long& lin_hit) {
+// CUT (occlusion.hip: short rays): the walk ends once a cell's entry parameter is beyond t_max.  t never decreases along the walk and a hit's parameter
+// is at least its cell's entry parameter, so every hit with t <= t_max is still found, with the same t and cell.  Without CUT the test is not
+// compiled: the renderer's and the bake's instantiations are the ones they were.
+template <bool MR, bool CUT = false>
+__device__ __forceinline__ bool render_trace(const RenderArgs& a, const float* uo, const float* uw, float& t_hit, long long& lin_hit, const float t_max = FLT_MAX) {
 #pragma clang fp contract(off)
     // the occupied-brick box, validated BEFORE any arithmetic on it: with no occupied brick the six words keep their 0x7f7f7f7f fill (bbox[k] >= nb[k]),
     // and only a box of brick indices inside [0, nb) turns into cell bounds inside [0, dim)
@@ -47,6 +50,7 @@ __device__ __forceinline__ bool render_trace(const RenderArgs& a, const float* u
     const long long nxy = (long long)a.grid.dim[0] * a.grid.dim[1];
     const int max_steps = (hi[0] - lo[0]) + (hi[1] - lo[1]) + (hi[2] - lo[2]) + 8;
     for (int it = 0; it < max_steps; ++it) {
+        if (CUT && t > t_max) return false;
         if (MR && (step[2] > 0 ? c[2] >= a.zr[1] : step[2] < 0 ? c[2] < a.zr[0] : (c[2] < a.zr[0] || c[2] >= a.zr[1]))) return false;   // past the owned planes
         const int bc[3] = {c[0] / kRenderBrick, c[1] / kRenderBrick, c[2] / kRenderBrick};
         if (!a.bricks[bc[0] + a.nb[0] * (bc[1] + a.nb[1] * bc[2])]) {

@@ -19,9 +19,10 @@ inline uint8_t normal_to_u8(float n) {
 }
 
 // xyz, nrm: [nv][3]; faces: [nf][3] (0-based); uv: [nf][3][2] with v pointing DOWN (row 0 of the image on top): OBJ's v points up, so 1 - v is written.
+// ao_png (if given): one more line `map_Ka <file>` in the material.
 // `f a/t/n`: position and normal share the vertex number, the texture coordinate of corner k of face f is number 3 f + k (all 1-based in the file)
 inline bool write_obj_bake(const std::string& obj_path, const std::string& mtl_path, const std::string& albedo_png, const std::string& normal_png,
-                           const float* xyz, const float* nrm, size_t nv, const int32_t* faces, const float* uv, size_t nf) {
+                           const float* xyz, const float* nrm, size_t nv, const int32_t* faces, const float* uv, size_t nf, const std::string& ao_png = "") {
     std::string s;
     s.reserve(64 * nv + 120 * nf + 256);
     char line[256];
@@ -39,7 +40,8 @@ inline bool write_obj_bake(const std::string& obj_path, const std::string& mtl_p
     FILE* fo = fopen(obj_path.c_str(), "wb");
     bool ok = fo && fwrite(s.data(), 1, s.size(), fo) == s.size();
     if (fo && fclose(fo) != 0) ok = false;
-    const std::string m = "newmtl baked\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nmap_Kd " + path_basename(albedo_png) + "\nnorm " + path_basename(normal_png) + "\n";
+    const std::string m = "newmtl baked\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nmap_Kd " + path_basename(albedo_png) + "\nnorm " + path_basename(normal_png) + "\n"
+                          + (ao_png.empty() ? "" : "map_Ka " + path_basename(ao_png) + "\n");      // (--mesh-bake-ao: the ambient-occlusion map)
     FILE* fm = fopen(mtl_path.c_str(), "wb");
     ok = fm && fwrite(m.data(), 1, m.size(), fm) == m.size() && ok;
     if (fm && fclose(fm) != 0) ok = false;

@@ -38,6 +38,7 @@
 #include "../../include/psgsdf_mesh.h"
 #include "../../include/psgsdf_fit.h"
 #include "../../include/psgsdf_bake.h"
+#include "../../include/psgsdf_occlusion.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 #include "obj_writer.hpp"
@@ -107,6 +108,9 @@ inline double& mesh_lod_voxels() { static double v = 0.0; return v; }
 // baked into <name>_mesh_lod_albedo.png and <name>_mesh_lod_normal.png (object space), R texels along a triangle's edge, rays from one cell outside
 // (psgsdf_bake_lod); 0: off; single process only
 inline int& mesh_bake_res() { static int v = 0; return v; }
+// voxelPS --mesh-bake-ao K (with --mesh-bake): <name>_mesh_lod_ao.png next to the other maps (grey, 255 = open) and one `map_Ka` line in the .mtl: the
+// ambient occlusion of the reconstructed surface from K rays per texel, radius 8 voxels, origins 1 voxel off the surface (psgsdf_bake_lod_ao); 0: off
+inline int& mesh_bake_ao_dirs() { static int v = 0; return v; }
 // voxelPS --mesh-fit: next to every <name>_mesh.ply a <name>_mesh_fit.ply, the welded mesh with the photometric fit of every vertex (psgsdf_extract_mesh_fit): how many
 // keyframes saw it, the rms residual and the mean robust loss; single process only
 inline bool& mesh_fit() { static bool v = false; return v; }
@@ -526,8 +530,14 @@ struct VolumetricGradSdf {
         int64_t nv = 0, nf = 0, nv_in = 0, nf_in = 0;
         const double cell = mesh_lod_voxels() * (double)info.voxel_size;
         psgsdf_bake bk{};      // --mesh-bake: the same level-of-detail arrays (bit for bit) and the atlas, in one call
+        psgsdf_bake_ao ao{};   // --mesh-bake-ao: the same bake (bit for bit) and the occlusion map
         if (mesh_bake_res() > 0) {
-            if (psgsdf_bake_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &bk) != 0 || bk.n_faces_in == 0) return false;
+            if (mesh_bake_ao_dirs() > 0) {
+                const psgsdf_ao_params ap{mesh_bake_ao_dirs(), 0, 8.0 * (double)info.voxel_size, (double)info.voxel_size};
+                if (psgsdf_bake_lod_ao(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &ap, &ao) != 0) return false;
+                bk = ao.bake;
+            } else if (psgsdf_bake_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &bk) != 0) return false;
+            if (bk.n_faces_in == 0) return false;
             xyz = bk.xyz; nrm = bk.normals; rgb = bk.rgb; faces = bk.faces; nv = bk.n_vertices; nf = bk.n_faces; nv_in = bk.n_vertices_in; nf_in = bk.n_faces_in;
         } else if (psgsdf_extract_mesh_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vmap, &nv_in, &nf_in) != 0
             || nf_in == 0) return false;
@@ -550,11 +560,19 @@ struct VolumetricGradSdf {
             for (size_t q = 0; q < 3 * px; ++q) (*nmap)[q] = normal_to_u8(bk.normal[q]);
             std::cout << "baked " << bk.n_texels << " texels onto " << nf << " faces (" << W << " x " << H << "): " << bk.n_hits << " hits (" << bk.n_hits_off_band << " off the band), "
                       << bk.n_buried << " buried, " << bk.n_misses << " misses" << std::endl;
+            const bool with_ao = mesh_bake_ao_dirs() > 0 && ao.occlusion;
+            auto occ = std::make_shared<std::vector<uint8_t>>();
+            if (with_ao) {
+                occ->assign(ao.occlusion, ao.occlusion + px);
+                std::cout << "ambient occlusion: " << ao.counts.n_rays << " rays (" << ao.n_dirs << " per texel), " << ao.counts.n_occluded << " occluded, " << ao.counts.n_buried << " of them buried" << std::endl;
+            }
             DumpQueue::get().push([=] {
                 const std::string lod = base + "_mesh_lod";
-                bool ok = write_obj_bake(lod + ".obj", lod + ".mtl", lod + "_albedo.png", lod + "_normal.png", vx->data(), vn->data(), (size_t)nv, vf->data(), uv->data(), (size_t)nf);
+                bool ok = write_obj_bake(lod + ".obj", lod + ".mtl", lod + "_albedo.png", lod + "_normal.png", vx->data(), vn->data(), (size_t)nv, vf->data(), uv->data(), (size_t)nf,
+                                         with_ao ? lod + "_ao.png" : std::string());
                 ok = write_png(lod + "_albedo.png", W, H, 3, alb->data()) && ok;
                 ok = write_png(lod + "_normal.png", W, H, 3, nmap->data()) && ok;
+                if (with_ao) ok = write_png(lod + "_ao.png", W, H, 1, occ->data()) && ok;
                 if (!ok) { std::cout << "couldn't save the baked level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure(); }
             });
         }

@@ -258,6 +258,7 @@ int main(int argc, char* argv[]) {
     std::string filter_flag;                  // the last of --mesh-min-faces / --mesh-keep-largest given
     bool lod_flag = false, lod_ok = true;     // --mesh-lod S given / S is a number > 0
     bool bake_flag = false, bake_ok = true;   // --mesh-bake R given / R is a whole number >= 1
+    bool ao_flag = false, ao_ok = true;       // --mesh-bake-ao K given / K is 8, 16, 32 or 64
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
@@ -268,6 +269,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
         else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_lod_voxels() = lod_ok ? v : 0.0; lod_flag = true; }      // <name>_mesh_lod.ply next to every <name>_mesh.ply: the vertices of every cube of S voxels merged (include/psgsdf_mesh.h psgsdf_extract_mesh_lod)
         else if (a == "--mesh-bake" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); bake_ok = end != argv[i] && *end == 0 && v >= 1 && v <= 16383; mesh_bake_res() = bake_ok ? (int)v : 0; bake_flag = true; }      // with --mesh-lod: <name>_mesh_lod.obj / .mtl / _albedo.png / _normal.png next to every <name>_mesh_lod.ply: the reconstruction's albedo and normals baked onto the coarse mesh, R texels along a triangle's edge (include/psgsdf_bake.h)
+        else if (a == "--mesh-bake-ao" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); ao_ok = end != argv[i] && *end == 0 && (v == 8 || v == 16 || v == 32 || v == 64); mesh_bake_ao_dirs() = ao_ok ? (int)v : 0; ao_flag = true; }      // with --mesh-bake: <name>_mesh_lod_ao.png and a map_Ka line in the .mtl: ambient occlusion of the reconstructed surface, K rays per texel (include/psgsdf_occlusion.h)
         else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
@@ -279,6 +281,9 @@ int main(int argc, char* argv[]) {
     if (transport != "rccl" && transport != "sockets") { std::cerr << "--transport: rccl or sockets" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && host_writers()) { std::cerr << "--host-writers is the single-process cross-check" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && clean_mesh()) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
+    if (ao_flag && !ao_ok) { std::cerr << "--mesh-bake-ao: rays per texel, 8, 16, 32 or 64" << std::endl; return 1; }
+    if (ao_flag && !bake_flag) { std::cerr << "--mesh-bake-ao needs --mesh-bake R: the occlusion is one more map of the bake" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && ao_flag) { std::cerr << "--mesh-bake-ao needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (bake_flag && !bake_ok) { std::cerr << "--mesh-bake: texels along a triangle's edge, a whole number >= 1" << std::endl; return 1; }
     if (bake_flag && !lod_flag) { std::cerr << "--mesh-bake needs --mesh-lod S: the maps are baked onto the level-of-detail mesh" << std::endl; return 1; }
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }

@@ -5,6 +5,10 @@ Then the photometric fit (include/psgsdf_fit.h): psgsdf_band_fit next to psgsdf_
 where k_energy reduces) and psgsdf_extract_mesh_fit next to psgsdf_extract_mesh_indexed (it adds k_band_fit and k_wmesh_fit).
 Then the detail maps (include/psgsdf_bake.h): psgsdf_bake_lod at the same cells with 8 texels along an edge (it repeats the level-of-detail call and adds
 k_render_bricks and k_bake), its atlas sizes and counts.
+Then ambient occlusion (include/psgsdf_occlusion.h): psgsdf_bake_lod_ao at a cell of 4 voxels, 8 texels along an edge, 16 and 64 rays per texel, radius 8
+voxels, bias 1 voxel: k_occlusion's event-timed ms per launch and rays per second, with the walk cut at the radius and -- alternating in the same run,
+on a second context created under PSGSDF_AO_CUT=0 and brought to the same state -- without the cut (the same bits), each as median and range over the
+repetitions (synthetic scenes only).
 Wall-clock per call (host clock; both calls end in a stream synchronise) and the kernels' own times from psgsdf_kernel_times:
     python tools/time_mesh.py sokrates [reps]      the sokrates fixture fused at its poses (128^3 at 4 mm), one iteration
     python tools/time_mesh.py N [reps]             a synthetic SH1 scene on an N^3 grid
@@ -101,12 +105,34 @@ for name, call in (("energy_ms", eng.energy), ("band_fit_ms", eng.band_fit), ("e
         call()
     t_fit[name] = round(1e3 * (time.perf_counter() - t0) / reps, 3)
 kt = eng.kernel_times()
+ao = {}
+if what != "sokrates":
+    os.environ["PSGSDF_AO_CUT"] = "0"      # (read when a context is created)
+    uncut = capi.load_engine(sc, sc.K, capi.default_settings(sc.model_id), 0)
+    del os.environ["PSGSDF_AO_CUT"]
+    uncut.load_scene(sc); uncut.init_albedo(); uncut.iterate(capi.ALL, 1)
+    uncut.bake_lod_ao(4 * vs, 8, None, 16, 8 * vs, vs)      # (warm-up)
+    uncut.set_profiling(True)
+    for K in (16, 64):
+        ms = {"cut": [], "no_cut": []}
+        for _ in range(reps):
+            for name, e in (("cut", eng), ("no_cut", uncut)):      # alternating: both see the same clocks and cache state
+                before = e.kernel_times().get("occlusion", (0.0, 0))
+                b = e.bake_lod_ao(4 * vs, 8, None, K, 8 * vs, vs)
+                after = e.kernel_times()["occlusion"]
+                assert after[1] == before[1] + 1
+                ms[name].append(after[0] - before[0])
+        cn = b["counts"]
+        ao[f"K{K}"] = {"texels": cn["n_samples"], "rays": cn["n_rays"], "occluded": cn["n_occluded"], "buried": cn["n_buried"],
+                       **{f"k_occlusion_ms_{n}": {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for n, v in ms.items()},
+                       **{f"rays_per_s_{n}": round(cn["n_rays"] / (1e-3 * float(np.median(v)))) for n, v in ms.items()}}
+    uncut.set_profiling(False)
 eng.set_profiling(False)
 V, Fc = len(xyz), len(faces)
 print(json.dumps({"state": what, "grid": list(eng.info().dim), "extract_mesh_ms": round(1e3 * t_plain, 3), "extract_mesh_indexed_ms": round(1e3 * t_idx, 3),
                   "extract_mesh_components_ms": {k: round(1e3 * v, 3) for k, v in t_cc.items()},
                   "extract_mesh_lod_ms": {k: round(1e3 * v, 3) for k, v in t_lod.items()}, "lod": lod_sizes,
-                  "bake_lod_ms": {k: round(1e3 * v, 3) for k, v in t_bake.items()}, "bake": bake_sizes,
+                  "bake_lod_ms": {k: round(1e3 * v, 3) for k, v in t_bake.items()}, "bake": bake_sizes, "ambient_occlusion_4vs_R8": ao,
                   "kernel_ms_per_launch": {k: round(ms / max(n, 1), 4) for k, (ms, n) in kt.items() if k.startswith(("mc_", "wmesh_", "mcomp_", "mlod_")) or k in ("band_fit", "energy", "bake", "k_render_bricks")},
                   **t_fit, "fit": {"n_band": int(eng.info().n_band), "vertex_observations": int(fit["n_obs"].sum()), "vertices_observed": int((fit["n_obs"] > 0).sum())},
                   "faces": Fc, "components": len(comps), "largest_component_faces": int(comps["n_faces"].max()) if len(comps) else 0, "vertices_indexed": V, "vertices_non_indexed": len(xn),
