@@ -34,7 +34,7 @@ const char* psgsdf_version(void) { return "psgsdf-hip gfx950 r5"; }
 // WRONG on purpose and are compiled out of libpsgsdf.so.
 static const char* const kKnobs[] = {
     "PSGSDF_PCG_POLL", "PSGSDF_SPECULATE", "PSGSDF_FOLD_IN_NEXT", "PSGSDF_FUSE_ALBEDO", "PSGSDF_FUSE_PCG_INIT", "PSGSDF_PCG_PERSIST", "PSGSDF_PCG_XCD_LOCAL",
-    "PSGSDF_PCG_FUSE_ASM", "PSGSDF_PCG_FUSE_APPLY", "PSGSDF_PCG_PIPELINE", "PSGSDF_PCG_TAGM", "PSGSDF_PCG_PREFETCH", "PSGSDF_PCG_COL16", "PSGSDF_PCG_ROWS", "PSGSDF_PCG_BLOCKS",
+    "PSGSDF_PCG_FUSE_ASM", "PSGSDF_PCG_FUSE_APPLY", "PSGSDF_PCG_PIPELINE", "PSGSDF_PCG_TAGM", "PSGSDF_PCG_WINDOW", "PSGSDF_PCG_SOLVE_ROWS", "PSGSDF_PCG_PREFETCH", "PSGSDF_PCG_COL16", "PSGSDF_PCG_ROWS", "PSGSDF_PCG_BLOCKS",
     "PSGSDF_FM_SOLVE", "PSGSDF_FRAME_SOLVE", "PSGSDF_FM_ROWS", "PSGSDF_IMG_COMPACT", "PSGSDF_XCD_MAP", "PSGSDF_XCD_STRIPE",
     "PSGSDF_XR", "PSGSDF_XF", "PSGSDF_XS", "PSGSDF_XH", "PSGSDF_XR_MEM", "PSGSDF_XWAIT_LOG2", "PSGSDF_SPECULATE_MR", "PSGSDF_CU_MASK",
     "PSGSDF_WAIT_TIMEOUT_S", "PSGSDF_DESTROY_TIMEOUT_S", "PSGSDF_SOLVE_DUMP", "PSGSDF_AO_CUT"};
@@ -62,6 +62,8 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     if (const char* e = getenv("PSGSDF_PCG_PIPELINE")) c->pcg_pipeline = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_PCG_TAGM")) { c->pcg_tagm = atoi(e) != 0; c->pcg_tagm_mr = atoi(e) >= 2; }
     if (const char* e = getenv("PSGSDF_PCG_PREFETCH")) c->pcg_prefetch = atoi(e) != 0;
+    if (const char* e = getenv("PSGSDF_PCG_WINDOW")) c->pcg_window = atoi(e) != 0;
+    if (const char* e = getenv("PSGSDF_PCG_SOLVE_ROWS")) { const int v = atoi(e); if (v > 0) c->pcg_solve_rows = v; }
     if (const char* e = getenv("PSGSDF_FM_SOLVE")) { c->fm_solve = atoi(e) != 0; c->fm_solve_led = atoi(e) == 1; }
     if (const char* e = getenv("PSGSDF_FRAME_SOLVE")) c->frame_solve = (!strcmp(e, "eigen") || !strcmp(e, "1")) ? 1 : 0;
     if (const char* e = getenv("PSGSDF_XF")) c->xf_enable = atoi(e) != 0;
@@ -137,7 +139,7 @@ void psgsdf_destroy(psgsdf_ctx* c) {
     free_dense(c);
     hipFree(c->vis_seq); hipFree(c->frame_idx); hipFree(c->img); hipFree(c->img8); hipFree(c->frames); hipFree(c->frames_undo); hipFree(c->led_light); hipFree(c->fs_stats);
     hipFree(c->band_mem); if (!c->leak_exported) hipFree(c->rec_mem); hipFree(c->obs_mem); hipFree(c->stage);
-    hipFree(c->ncache); hipFree(c->ntmp); hipFree(c->nout); hipFree(c->ndepth); hipFree(c->track_part); if (c->track_host) hipHostFree(c->track_host); hipFree(c->acc_frame); hipFree(c->frame_part); hipFree(c->frame_done); hipFree(c->part); hipFree(c->pcg_sc); hipFree(c->pcg_part); hipFree(c->pcg_gran); hipFree(c->d_total);
+    hipFree(c->ncache); hipFree(c->ntmp); hipFree(c->nout); hipFree(c->ndepth); hipFree(c->track_part); if (c->track_host) hipHostFree(c->track_host); hipFree(c->acc_frame); hipFree(c->frame_part); hipFree(c->frame_done); hipFree(c->part); hipFree(c->pcg_sc); hipFree(c->pcg_part); hipFree(c->pcg_gran); hipFree(c->win_tab); hipFree(c->d_total);
     for (void* p : c->xo_host) if (p) hipHostFree(p);
     if (c->pin_stage) hipHostFree(c->pin_stage);
     if (c->host_buf) hipHostFree(c->host_buf);

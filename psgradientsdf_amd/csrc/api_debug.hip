@@ -285,7 +285,19 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
              (int)c->pcg_prefetch, (int)c->pcg_fuse_asm, (int)c->pcg_fuse_apply, (int)c->pcg_xcd_local, (int)c->fm_solve, (int)c->fm_solve_led, c->frame_solve == 1 ? "eigen" : "ldlt", (int)c->img_compact, c->xcd_map,
              (int)c->xr_enable, (int)c->xf_enable, (int)c->xs_enable, (int)c->xh_enable, c->xr_mem_kind, (int)lround(log2((double)c->xwait_spins)), c->cu_mask_lo, c->cu_mask_hi,
              (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut);
-    o += buf; o += "}";
+    o += buf;
+    {   // the LDS window of the single-rank pipelined solve: the knob, what this band's partition needs and may hold, and what the last solve ran.
+        // "fallback" names why a context with the knob on gathers per thread all the same -- never silently
+        int Gs = 0, Rs = 0;
+        const bool shape = cgf_solve_shape(c, &Gs, &Rs);
+        const int budget = (shape && c->n_ranks <= 1) ? cgf_solve_window_budget(Rs) : 0;
+        const char* why = !c->pcg_window ? "" : c->n_ranks > 1 ? "multi-rank" : c->pcg_ablate ? "timing ablation" : !(c->pcg_pipeline && c->pcg_tagm && c->pcg_fuse_asm) ? "not the self-validating pipelined solve" : !c->inited ? "no band yet"
+                          : !shape ? "no persistent solve on this band" : (c->win_G != Gs || c->win_rows != Rs) ? "no table for this partition" : c->win_max > budget ? "window does not fit" : "";
+        snprintf(buf, sizeof(buf), ", \"pcg_window\": %d, \"pcg_solve_rows\": %d, \"solve_window\": {\"workgroups\": %d, \"rows_per_workgroup\": %d, \"window_doubles\": %d, \"budget_doubles\": %d, \"fits\": %d, \"fallback\": \"%s\", \"last_solve_windowed\": %d}",
+                 (int)c->pcg_window, c->pcg_solve_rows, shape ? Gs : 0, shape ? Rs : 0, c->win_max, budget, (int)(c->pcg_window && !*why), why, c->last_solve_windowed);
+        o += buf;
+    }
+    o += "}";
     if (c->n_ranks > 1) {      // the hand-off probe as THIS rank saw it, per memory kind tried (comm.hip xr_probe): a first multi-GPU run reads its pairs here
         snprintf(buf, sizeof(buf), ", \"xr_probe\": {\"rank\": %d, \"n_ranks\": %d, \"kind_chosen\": %d, \"stale_mappings\": %lld, \"fine_grained\": {\"tried\": %lld, \"stale_records_from_lower\": %lld, \"expired_waits_lower\": %lld, \"expired_waits_upper\": %lld}, "
                  "\"uncached\": {\"tried\": %lld, \"stale_records_from_lower\": %lld, \"expired_waits_lower\": %lld, \"expired_waits_upper\": %lld}}",

@@ -739,12 +739,12 @@ __device__ __forceinline__ void fm_for_each_obs(const Band& b, const FrameP& fp,
 }
 
 // ELL column offsets of one assembled distance row: self, 6 axis neighbours, 12 axis pairs
-__host__ __device__ inline void q_offset(int q, int* o) {
+__host__ __device__ constexpr inline void q_offset(int q, int* o) {
     o[0] = o[1] = o[2] = 0;
     if (q == 0) return;
     if (q <= 6) { int a = (q - 1) >> 1; o[a] = ((q - 1) & 1) ? -1 : 1; return; }
     // q 7..12: mixed-sign axis pairs (the only pair columns a forward-only stencil produces), q 13..18: (+,+) / (-,-)
-    int pi, sa, sb;
+    int pi = 0, sa = 0, sb = 0;
     if (q < kNQCommon) { pi = (q - 7) >> 1; sa = ((q - 7) & 1) ? -1 : 1; sb = -sa; }
     else { pi = (q - kNQCommon) >> 1; sa = ((q - kNQCommon) & 1) ? -1 : 1; sb = sa; }
     int a = pi == 2 ? 1 : 0, b = pi == 0 ? 1 : 2;

@@ -148,6 +148,8 @@ struct SweepArgs {
     int pcg_xcd_local;        // ... and keeps the records of workgroups whose neighbours all run on their own XCD in that XCD's L2 (plain stores)
     int pcg_apply;            // ... and applies the distance update itself (no k_apply_dist behind it): 1 = when finished, 2 = only on Success
     double* pcg_gran; int pcg_gran_n;   // persistent solve: the tagged per-workgroup sums, zeroed by the assembly kernel when non-null
+    const int* pcg_win;       // persistent solve, windowed instance (pcg.hip k_solve_windows): per workgroup {first row, length} of its three LDS window ranges; nullptr: off
+    int pcg_win_G, pcg_win_rows, pcg_win_max;      // ... the partition the table was computed for (workgroups, rows per workgroup) and the largest window (doubles)
     int pcg_fuse_init;        // assembly kernel also initialises the PCG (x = 0, records of pass -1, |b|^2 partials): no k_cgf_init launch
     int pcg_init_blocks;      // workgroups that wrote the |b|^2 partials (0: the pass kernel's own grid)
     int fuse_apply;           // albedo sweep: solve the voxel's diagonal system and apply the update in the same thread (no normal equations stored); 2: and keep the old albedo for an undo
@@ -254,7 +256,9 @@ void launch_cgf_sum(double* part, int G, int k, double* out, hipStream_t s);
 constexpr int kSolveGranPlanes = 8;
 constexpr int kSolveThreadsHost = 512, kSolveMaxBlocksHost = 256, kSolveMaxRowsHost = 4, kSolveMbSlots = 24;      // {iters, |r|^2, |b|^2, status} + stage timestamps of the timing hook
 int cgf_solve_max_blocks(int rows);      // resident workgroups per CU of the R-rows instance (occupancy query)
-void launch_cgf_solve(const SweepArgs& a, double* fs, double* gran, int G, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, hipStream_t s, const XrArgs* xr = nullptr);   // xr: multi-rank (z-slab) solve   // mb[4] = check word over mb[0..3] (FoldReq)
+void launch_solve_windows(const Band& b, int row0, int row1, int G, int rows_per_wg, int* tab /*[6 G]*/, int* max_total, hipStream_t s);   // window table of the partition (zeroes *max_total first)
+int cgf_solve_window_budget(int rows_per_wg);      // doubles the windowed instance's LDS window may hold at this partition
+int launch_cgf_solve(const SweepArgs& a, double* fs, double* gran, int G, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, hipStream_t s, const XrArgs* xr = nullptr);   // xr: multi-rank (z-slab) solve   // mb[4] = check word over mb[0..3] (FoldReq)
 // "reg albedo" path (albedo_reg.hip); every launch covers the whole band (single rank only)
 void launch_areg_tables(const DenseView& d, const GridP& g, const SweepArgs& a, hipStream_t s);
 void launch_areg_build(const SweepArgs& a, hipStream_t s);                       // J, res from the current albedo; sum of res -> SC_AUX0

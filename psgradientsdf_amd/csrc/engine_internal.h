@@ -105,6 +105,11 @@ struct psgsdf_ctx {
     bool pcg_fuse_apply = true;          // PSGSDF_PCG_FUSE_APPLY=0: k_apply_dist behind it
     bool pcg_xcd_local = true;           // PSGSDF_PCG_XCD_LOCAL=0: every record through memory (write-through stores)
     bool pcg_persist = true;             // PSGSDF_PCG_PERSIST=0: always the per-pass kernels
+    bool pcg_window = true;              // PSGSDF_PCG_WINDOW=0: the single-rank pipelined solve gathers per thread instead of reading an LDS window (pcg.hip k_cgp_solve<.., WIN>)
+    int pcg_solve_rows = 0;              // PSGSDF_PCG_SOLVE_ROWS: rows per workgroup of the persistent solve on one rank (0: as many workgroups as CUs); tests shape the partition with it
+    int* win_tab = nullptr;              // [6 kSolveMaxBlocksHost + 1] window table of this band and partition (pcg.hip k_solve_windows) + its largest total
+    int win_G = 0, win_rows = 0, win_max = 0;      // ... the partition it was computed for (0: no table) and the largest window in doubles
+    int last_solve_windowed = -1;        // the last persistent distance solve ran the windowed instance (1) or not (0); -1: none yet
     bool persist_off = false;            // a persistent solve gave up on this band (bounded wait expired): per-pass kernels until the next band is built (build_band re-arms)
     int num_cu = 0;
     int last_cg_iters = 0;

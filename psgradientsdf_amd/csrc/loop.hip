@@ -35,7 +35,12 @@ bool cgf_solve_shape(psgsdf_ctx* c, int* G, int* rows_per_wg, bool any_ranks) {
     int g = std::min(cap, (n + kSolveThreadsHost - 1) / kSolveThreadsHost);
     g = std::max(8, g / 8 * 8);
     if (g > cap) g = cap;
-    const int per = ((n + g - 1) / g + 63) / 64 * 64;
+    int per = ((n + g - 1) / g + 63) / 64 * 64;
+    if (c->pcg_solve_rows > 0 && c->n_ranks <= 1) {      // PSGSDF_PCG_SOLVE_ROWS: the rows per workgroup are given, the workgroups follow
+        per = (c->pcg_solve_rows + 63) / 64 * 64;
+        g = (n + per - 1) / per;
+        if (g > cap) return false;
+    }
     const int r = (per + kSolveThreadsHost - 1) / kSolveThreadsHost;
     if (r > kSolveMaxRowsHost || cgf_solve_max_blocks(r) < 1) return false;
     *G = g; *rows_per_wg = per;
@@ -85,7 +90,7 @@ int pcg_solve(psgsdf_ctx* c, SweepArgs& a, int* iters_out, int* success_out, dou
             }
         }
         as.pcg_epoch = ++c->pcg_solve_serial;
-        timed(c, "pcg_solve", [&] { launch_cgf_solve(as, c->pcg_sc, c->pcg_gran, G, rows, cap, c->mbox_dev + off, key, inject, c->stream, xr); });
+        timed(c, "pcg_solve", [&] { c->last_solve_windowed = launch_cgf_solve(as, c->pcg_sc, c->pcg_gran, G, rows, cap, c->mbox_dev + off, key, inject, c->stream, xr); });
         if (tail && !c->profiling) { tail(c->pcg_sc + (gate_on_converged ? 2 : 1)); if (tail_ran) *tail_ran = true; }
         // the four status words are taken only together with their check word (engine.h FoldReq)
         const bool chk = c->mbox_check;
