@@ -420,8 +420,8 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* ctx, int64_t out[8]);
  * between equivalent execution strategies -- results agree to rounding, most bit for bit (tests/test_knobs_gpu.py) -- and none is needed in
  * normal operation.  psgsdf_get_tuning reports what was set and what it resolved to.
  *   PSGSDF_PCG_POLL, PSGSDF_SPECULATE, PSGSDF_SPECULATE_MR, PSGSDF_FOLD_IN_NEXT, PSGSDF_FUSE_ALBEDO, PSGSDF_FUSE_PCG_INIT        (0 / 1) host-side scheduling
- *   PSGSDF_PCG_PERSIST, PSGSDF_PCG_PIPELINE, PSGSDF_PCG_TAGM (0: the pipelined solve's exchanged values without their own tags -- round 4's hand-off; 1: self-validating on one rank only; default 2: between ranks too), PSGSDF_PCG_WINDOW (0: the single-rank pipelined solve gathers its neighbour values per thread instead of reading them from an LDS window; the same bits;
- *   "effective.solve_window" says whether a band's windows fit and what the last solve ran), PSGSDF_PCG_SOLVE_ROWS (rows per workgroup of the persistent solve on one rank; default: as many workgroups as CUs), PSGSDF_PCG_PREFETCH, PSGSDF_PCG_FUSE_ASM, PSGSDF_PCG_FUSE_APPLY, PSGSDF_PCG_XCD_LOCAL,
+ *   PSGSDF_PCG_PERSIST (0: the per-pass kernels with the classic float recurrences instead of the persistent pipelined solve), PSGSDF_PCG_WINDOW (0: the single-rank persistent solve gathers its neighbour values per thread instead of reading them from an LDS window; the same bits;
+ *   "effective.solve_window" says whether a band's windows fit and what the last solve ran), PSGSDF_PCG_SOLVE_ROWS (rows per workgroup of the persistent solve on one rank; default: as many workgroups as CUs), PSGSDF_PCG_PREFETCH, PSGSDF_PCG_FUSE_APPLY,
  *   PSGSDF_PCG_COL16*, PSGSDF_PCG_ROWS*, PSGSDF_PCG_BLOCKS*                                                                        distance solve
  *   PSGSDF_FRAME_SOLVE (ldlt | eigen: psgsdf_set_frame_solver; the ONE knob that changes results beyond rounding),
  *   PSGSDF_FM_SOLVE, PSGSDF_FM_ROWS*, PSGSDF_IMG_COMPACT, PSGSDF_XCD_MAP, PSGSDF_XCD_STRIPE                                        sweeps

@@ -83,7 +83,7 @@ int psgsdf_debug_time_pcg_solve(psgsdf_ctx* c, int passes, int reps, double* ms_
     if (!cgf_solve_shape(c, &G, &rows)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "the persistent solve does not apply to this context");
     shape[0] = G; shape[1] = rows;      // rows = rows per workgroup
     SweepArgs a = make_args(c, c->reg_l != 0.f);
-    a.pcg_fuse_init = 1; a.pcg_init_blocks = band_blocks(c); a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = c->pcg_fuse_asm ? 1 : 0;
+    a.pcg_fuse_init = 1; a.pcg_init_blocks = band_blocks(c); a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1;
     hipEvent_t e0, e1; HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
     float total = 0;
     for (int r = 0; r < reps + 1; ++r) {
@@ -119,7 +119,7 @@ int psgsdf_debug_overlap_probe(psgsdf_ctx* c, int reps, double* out) {
     if (c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "overlap probe: one rank");
     HIPCHK(c, hipSetDevice(c->device));
     int G = 0, rows = 0;
-    if (!cgf_solve_shape(c, &G, &rows) || !c->pcg_fuse_asm) return fail(c, PSGSDF_ERR_UNSUPPORTED, "the persistent solve with its fused assembly does not apply to this context");
+    if (!cgf_solve_shape(c, &G, &rows)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "the persistent solve does not apply to this context");
     { int rc = flush(c); if (rc) return rc; }
     SweepArgs a = make_args(c, c->reg_l != 0.f);
     a.pcg_fuse_init = 1; a.pcg_init_blocks = band_blocks(c); a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1;
@@ -278,20 +278,20 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
     for (auto& kv : c->tuning_ignored) { o += (first ? "\"" : ", \"") + kv.first + "\": \"" + esc(kv.second) + "\""; first = false; }
     o += "}, \"effective\": {";
     char buf[1024];
-    snprintf(buf, sizeof(buf), "\"pcg_poll\": %d, \"speculate\": %d, \"speculate_mr\": %d, \"fold_in_next\": %d, \"fuse_albedo\": %d, \"fuse_pcg_init\": %d, \"pcg_persist\": %d, \"pcg_pipeline\": %d, \"pcg_tagm\": %d, "
-             "\"pcg_prefetch\": %d, \"pcg_fuse_asm\": %d, \"pcg_fuse_apply\": %d, \"pcg_xcd_local\": %d, \"fm_solve\": %d, \"fm_solve_led\": %d, \"frame_solve\": \"%s\", \"img_compact\": %d, \"xcd_map\": %d, "
+    snprintf(buf, sizeof(buf), "\"pcg_poll\": %d, \"speculate\": %d, \"speculate_mr\": %d, \"fold_in_next\": %d, \"fuse_albedo\": %d, \"fuse_pcg_init\": %d, \"pcg_persist\": %d, "
+             "\"pcg_prefetch\": %d, \"pcg_fuse_apply\": %d, \"fm_solve\": %d, \"fm_solve_led\": %d, \"frame_solve\": \"%s\", \"img_compact\": %d, \"xcd_map\": %d, "
              "\"xr\": %d, \"xf\": %d, \"xs\": %d, \"xh\": %d, \"xr_mem_kind\": %d, \"xwait_log2\": %d, \"cu_mask\": [%d, %d], \"mbox_check\": %d, \"pcg_ablate\": %d, \"fault_solve\": %d, \"fault_halo\": %lld, \"ao_cut\": %d",
-             (int)c->pcg_poll, (int)c->speculate, (int)c->speculate_mr, (int)c->fold_in_next, (int)c->fuse_albedo, (int)c->fuse_pcg_init, (int)c->pcg_persist, (int)c->pcg_pipeline, (c->pcg_pipeline && c->pcg_tagm) ? (c->n_ranks > 1 ? (c->pcg_tagm_mr ? 2 : 0) : 1) : 0,
-             (int)c->pcg_prefetch, (int)c->pcg_fuse_asm, (int)c->pcg_fuse_apply, (int)c->pcg_xcd_local, (int)c->fm_solve, (int)c->fm_solve_led, c->frame_solve == 1 ? "eigen" : "ldlt", (int)c->img_compact, c->xcd_map,
+             (int)c->pcg_poll, (int)c->speculate, (int)c->speculate_mr, (int)c->fold_in_next, (int)c->fuse_albedo, (int)c->fuse_pcg_init, (int)c->pcg_persist,
+             (int)c->pcg_prefetch, (int)c->pcg_fuse_apply, (int)c->fm_solve, (int)c->fm_solve_led, c->frame_solve == 1 ? "eigen" : "ldlt", (int)c->img_compact, c->xcd_map,
              (int)c->xr_enable, (int)c->xf_enable, (int)c->xs_enable, (int)c->xh_enable, c->xr_mem_kind, (int)lround(log2((double)c->xwait_spins)), c->cu_mask_lo, c->cu_mask_hi,
              (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut);
     o += buf;
-    {   // the LDS window of the single-rank pipelined solve: the knob, what this band's partition needs and may hold, and what the last solve ran.
+    {   // the LDS window of the single-rank persistent solve: the knob, what this band's partition needs and may hold, and what the last solve ran.
         // "fallback" names why a context with the knob on gathers per thread all the same -- never silently
         int Gs = 0, Rs = 0;
         const bool shape = cgf_solve_shape(c, &Gs, &Rs);
         const int budget = (shape && c->n_ranks <= 1) ? cgf_solve_window_budget(Rs) : 0;
-        const char* why = !c->pcg_window ? "" : c->n_ranks > 1 ? "multi-rank" : c->pcg_ablate ? "timing ablation" : !(c->pcg_pipeline && c->pcg_tagm && c->pcg_fuse_asm) ? "not the self-validating pipelined solve" : !c->inited ? "no band yet"
+        const char* why = !c->pcg_window ? "" : c->n_ranks > 1 ? "multi-rank" : c->pcg_ablate ? "timing ablation" : !c->inited ? "no band yet"
                           : !shape ? "no persistent solve on this band" : (c->win_G != Gs || c->win_rows != Rs) ? "no table for this partition" : c->win_max > budget ? "window does not fit" : "";
         snprintf(buf, sizeof(buf), ", \"pcg_window\": %d, \"pcg_solve_rows\": %d, \"solve_window\": {\"workgroups\": %d, \"rows_per_workgroup\": %d, \"window_doubles\": %d, \"budget_doubles\": %d, \"fits\": %d, \"fallback\": \"%s\", \"last_solve_windowed\": %d}",
                  (int)c->pcg_window, c->pcg_solve_rows, shape ? Gs : 0, shape ? Rs : 0, c->win_max, budget, (int)(c->pcg_window && !*why), why, c->last_solve_windowed);

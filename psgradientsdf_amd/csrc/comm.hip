@@ -238,7 +238,7 @@ int comm_xfer(psgsdf_ctx* c, const std::vector<psgsdf_comm_xfer>& sends, const s
 //   polled words (the mailbox region: tags, rank granules, abort flag; KB-sized)   -> hipDeviceMallocUncached (every access goes to memory)
 //   the two PCG record planes (their halo rows are written by the neighbours)      -> hipDeviceMallocFinegrained (kind 1) or uncached (kind 2)
 // Which of the two carries the hand-offs between the REAL neighbours is not assumed but probed once per context (xr_probe): the very store /
-// load / fence forms of pcg.hip k_cgf_solve<.., MR> over the real mappings, the reader holding stale copies of the payload in its caches first.
+// load / fence forms of pcg_solve.h k_cgp_solve<.., MR> (and of the record hand-off it replaced) over the real mappings, the reader holding stale copies of the payload in its caches first.
 // On one GPU (the tests) every kind passes; what the first multi-GPU run finds is reported in psgsdf_debug_sync_stats / the bench line.
 int xr_alloc(psgsdf_ctx* c, void** p, size_t bytes, bool polled) {
     *p = nullptr;
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256) k_xr_probe(double* myF, const float4* myP
             for (int i = threadIdx.x; i < kProbeRecs; i += blockDim.x) sink += myP[i].x + (float)((const double*)myP)[2 * i + 1];      // (stale copies of both forms in this device's caches)
             __syncthreads();
             if ((r & 3) == 3) {
-                // every fourth round: the pipelined solve's SELF-VALIDATING hand-off (pcg.hip k_cgp_solve<.., MR, TM>) -- no flag wait, no fence:
+                // every fourth round: the pipelined solve's SELF-VALIDATING hand-off (pcg_solve.h k_cgp_solve<.., MR>) -- no flag wait, no fence:
                 // every word is polled with system-scope relaxed loads until it carries the round's 2-bit tag, as a halo row's m is.  The previous round of
                 // this kind (r - 4) left words with the SAME tag in the same place, and this device holds cached copies of them (the loop above): a word
                 // that validates by its tag but is not this round's is exactly the silent failure a two-valued tag would allow -- counted as stale.
@@ -299,8 +299,9 @@ __global__ void __launch_bounds__(256) k_xr_probe(double* myF, const float4* myP
     }
     if (blockIdx.x == 1 && has_hi) {
         for (int r = 1; r <= kProbeRounds; ++r) {
-            // even rounds: k_cgf_solve's hand-off (16-byte sc0 sc1 records); odd rounds: k_cgp_solve's, the frame rows' and the scalar folds' (8-byte
-            // sc0 sc1 words: device_common.h store8_system / pcg.hip store8_sys) -- the default solve is the pipelined one
+            // even rounds: 16-byte sc0 sc1 records (no kernel hands these over any more; the rounds stay because the probe's verdict on real multi-GPU
+            // hosts was established with them); odd rounds: k_cgp_solve's, the frame rows' and the scalar folds' hand-off (8-byte sc0 sc1 words:
+            // device_common.h store8_system / pcg_solve.h store8_sys)
             if ((r & 3) == 3) for (int i = threadIdx.x; i < kProbeRecs; i += blockDim.x) probe_store8((double*)hiP + 2 * i, (double)(((long long)(r >> 2) << 14) | (3ll << 12) | (long long)i));      // tagged words: (round / 4) << 14 | tag 3 << 12 | index
             else if (r & 1) for (int i = threadIdx.x; i < kProbeRecs; i += blockDim.x) { probe_store8((double*)hiP + 2 * i, (double)r); probe_store8((double*)hiP + 2 * i + 1, (double)(r + i)); }
             else for (int i = threadIdx.x; i < kProbeRecs; i += blockDim.x) {
@@ -468,7 +469,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     hipIpcMemHandle_t hx{}, hb{}, hh{};
     c->hx_ready = false; c->hx_peer[0] = c->hx_peer[1] = nullptr;
     int Gs, Rs;
-    bool ok = c->xr_enable && c->pcg_persist && c->pcg_fuse_asm && c->xr_mem_kind > 0 && c->rec_mem;
+    bool ok = c->xr_enable && c->pcg_persist && c->xr_mem_kind > 0 && c->rec_mem;
     // the region: the solve's fixed words + the frame rows' exchange area (engine.h XfTable) for this many ranks and keyframes.  (Every peer closed
     // its mapping of the old region in xr_quiesce at the top of build_band: it may be replaced here.)
     const size_t frows = (size_t)2 * R * std::max(c->F, 1);

@@ -12,8 +12,8 @@
 //                    (frame-major, wave + LDS reduction); k_solve_light, k_solve_pose (LDL^T per frame)
 //   fit.hip        : k_band_fit (k_energy's loop with the row's sums stored, not reduced), k_wmesh_fit (those sums on the welded mesh's vertices)
 //   dist.hip       : k_sweep_dist, k_assemble (per-pass path only)
-//   pcg.hip        : k_cgp_solve (the whole distance step as ONE persistent kernel: assembly into LDS, pipelined Jacobi-PCG in double, update; the
-//                    default), k_cgf_solve (the same with the classic recurrences), k_cgf_init / k_cgf_pass / k_cgf_sum (one kernel per pass:
+//   pcg.hip        : k_cgp_solve (pcg_solve.h; the whole distance step as ONE persistent kernel: assembly into LDS, pipelined Jacobi-PCG in double,
+//                    update; the default), k_cgf_init / k_cgf_pass / k_cgf_sum (one kernel per pass, the classic recurrences in float:
 //                    bands that do not fit the LDS, multi-rank contexts without mappings, the fall-back), k_apply_dist
 //   albedo_reg.hip : k_areg_*                          frontend.hip: k_integrate, k_normals_h/v, k_track, k_try_pack_f32, k_pack_rgb8
 //   extract.hip    : k_box_*, k_mc_count / k_mc_emit (marching cubes), k_pc_flags / k_pc_fill (point clouds), k_sdf_crop, k_cscan_*
@@ -34,7 +34,7 @@
 //   8  sums over a voxel's / a thread's observations in double (the oracle's accumulators) instead of float
 //  16  the Jacobian chains in the reference's order of evaluation: image_grad x pi_grad first, then R^T, then the direction (PsOptimizerJa.cpp:78-100,
 //      160-289; LedOptimizerJa.cpp:117-218), the SH2 / LED shading terms per channel and stencil slot -- not contracted from the right
-// (The solver of the light / pose blocks and the recurrences of the distance solve are run-time switches: PSGSDF_FRAME_SOLVE, PSGSDF_PCG_PIPELINE / _PERSIST.)
+// (The solver of the light / pose blocks and the recurrences of the distance solve are run-time switches: PSGSDF_FRAME_SOLVE, PSGSDF_PCG_PERSIST.)
 #ifndef PSG_STRICT
 #define PSG_STRICT 0
 #endif

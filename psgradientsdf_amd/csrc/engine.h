@@ -143,9 +143,9 @@ struct SweepArgs {
     AlbedoReg ar;             // ar.anb == nullptr unless "reg albedo" != 0
     double* pcg_part; double* pcg_fs;   // fused PCG state (pcg.hip)
     int pcg_asm;              // persistent solve assembles the distance system itself (no k_assemble launch in front of it)
-    unsigned pcg_epoch;       // serial number of this context's distance solve (k_cgp_solve<.., TM>: the tag of its exchanged values; the launch sites count it)
-    int pcg_pipe;             // ... and runs the pipelined recurrences (pcg.hip k_cgp_solve: the sums of a pass travel while the next pass gathers)
-    int pcg_xcd_local;        // ... and keeps the records of workgroups whose neighbours all run on their own XCD in that XCD's L2 (plain stores)
+    unsigned pcg_epoch;       // serial number of this context's distance solve (k_cgp_solve: the tag of its exchanged values; the launch sites count it)
+    int pcg_pipe;             // unused, always 0 (it selected among persistent kernels that are gone); the slot stays: every kernel's argument layout depends on it
+    int pcg_xcd_local;        // persistent solve, a bit set despite its name: 2 = the sums of a pass are requested behind the last gather batch (PSGSDF_PCG_PREFETCH), << 3: the timing ablations; bit 0 unused
     int pcg_apply;            // ... and applies the distance update itself (no k_apply_dist behind it): 1 = when finished, 2 = only on Success
     double* pcg_gran; int pcg_gran_n;   // persistent solve: the tagged per-workgroup sums, zeroed by the assembly kernel when non-null
     const int* pcg_win;       // persistent solve, windowed instance (pcg.hip k_solve_windows): per workgroup {first row, length} of its three LDS window ranges; nullptr: off
@@ -164,8 +164,8 @@ struct SweepArgs {
     const double* ext;        // multi-rank PCG: the 7 globally reduced sums of the previous pass (|b|^2 in ext[0] for pass 0), else nullptr
 };
 
-// Cross-rank hand-offs of the persistent distance solve on a z-slab partition (pcg.hip k_cgf_solve<.., MR = true>, comm.hip xr_setup): every rank owns one
-// small mailbox region that ALL ranks can write (IPC-mapped over xGMI), and the records of the rows next to a cut are written straight into the
+// Cross-rank hand-offs of the persistent distance solve on a z-slab partition (pcg_solve.h k_cgp_solve<.., MR = true>, comm.hip xr_setup): every rank owns one
+// small mailbox region that ALL ranks can write (IPC-mapped over xGMI), and the values of the rows next to a cut are written straight into the
 // neighbour's halo rows.  Both live in memory another device may write and this device may poll WHILE A KERNEL RUNS: the region is allocated
 // uncached, the two record planes fine-grained (comm.hip xr_alloc; plain hipMalloc memory is only coherent across devices at kernel boundaries),
 // and the hand-off forms are verified between the real neighbours before they are relied on (comm.hip xr_probe).
@@ -173,7 +173,7 @@ struct SweepArgs {
 // word a fast rank wrote before this rank even started its solve -- can neither be mistaken for the current one nor be wiped.
 // Layout of a region, in doubles:
 constexpr int kXrMaxRanks = 32;      // rank-level sums: [2 buffers][8 planes][kXrMaxRanks] tagged granules (plane 7: |b|^2 with the sums of pass 0)
-constexpr int kXrPeerTags = 64;      // 'records are out' tags of the neighbour's workgroups next to the cut: [2 sides][3 buffers (2 pass parities + prologue)][kXrPeerTags]
+constexpr int kXrPeerTags = 64;      // [2 sides][3 buffers][kXrPeerTags] words no kernel writes or reads any more (the halo values carry their own tags); the slots stay: the layout of a region is shared by every rank
 constexpr int kXrRankGran = 0, kXrPtag = 2 * 8 * kXrMaxRanks, kXrAbort = kXrPtag + 2 * 3 * kXrPeerTags, kXrDoubles = kXrAbort + 8;
 // kXrAbort + 0: the persistent solve's abort flag (raised in every rank's region; cleared with the region at the next band).  kXrLate + 0 / 1 / 2: the
 // number of the last frame-row exchange / scalar fold / halo pull of THIS rank whose bounded wait for a peer expired (0: none) -- the NaN such an
@@ -186,7 +186,7 @@ struct XrArgs {
     float4* lo_rec[2]; float4* hi_rec[2];   // where this slab's boundary records go: first upper-halo row of the lower neighbour / first lower-halo row of the upper one (per record buffer)
     float4* lo_base[2];                     // row 0 of the lower neighbour's record planes (k_cgp_solve stores ONE double per row at the head of a plane: row index counted in doubles)
     int give_lo, give_hi;            // own rows the lower / upper neighbour holds as halo (the first give_lo / last give_hi own rows)
-    int wait_lo, wait_hi;            // workgroups of the lower / upper neighbour whose tags this slab's cut-side workgroups wait for
+    int wait_lo, wait_hi;            // workgroups of the lower / upper neighbour next to the cut (xr_setup bounds them by kXrPeerTags; no kernel reads them any more, the fields keep the layout)
     int need_lo, need_hi;            // halo rows this slab gathers from
     unsigned epoch;                  // solve counter of the context (the same on every rank), 14 bits: tags of the cross-rank words are (epoch << 2 | pass tag)
 };
@@ -251,8 +251,8 @@ void launch_assemble(const SweepArgs& a, hipStream_t s);
 void launch_cgf_init(const SweepArgs& a, double* fs, double* part, int G, hipStream_t s);
 void launch_cgf_pass(const SweepArgs& a, double* fs, double* part, int G, int rows, int k, int kmax, double* mb, hipStream_t s, int ablate = 0);
 void launch_cgf_sum(double* part, int G, int k, double* out, hipStream_t s);
-// the whole solve as one persistent kernel (pcg.hip: k_cgf_solve); gran = [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums (plane 7: |b|^2 of
-// the fused assembly in buffer 0, its 'records are out' flag in buffer 1), zeroed by the kernel in front (assembly kernel / distance sweep)
+// the whole solve as one persistent kernel (pcg_solve.h: k_cgp_solve); gran = [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums (planes 0-2; plane 7 of
+// buffer 1: the prologue's flag), zeroed by the kernel in front (assembly kernel / distance sweep)
 constexpr int kSolveGranPlanes = 8;
 constexpr int kSolveThreadsHost = 512, kSolveMaxBlocksHost = 256, kSolveMaxRowsHost = 4, kSolveMbSlots = 24;      // {iters, |r|^2, |b|^2, status} + stage timestamps of the timing hook
 int cgf_solve_max_blocks(int rows);      // resident workgroups per CU of the R-rows instance (occupancy query)

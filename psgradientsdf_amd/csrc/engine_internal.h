@@ -95,17 +95,12 @@ struct psgsdf_ctx {
     double* pcg_sc = nullptr; int pcg_cap = 4096;
     double* pcg_part = nullptr;          // [2][7][kPcgMaxBlocks]
     double* pcg_gran = nullptr;          // persistent solve: [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums
-    bool pcg_fuse_asm = true;            // PSGSDF_PCG_FUSE_ASM=0: k_assemble in front of the persistent solve (round-2a)
     unsigned pcg_solve_serial = 0;       // distance solves launched on this context (SweepArgs::pcg_epoch)
-    bool pcg_tagm_mr = true;             // ... also between the ranks of a multi-rank context (the default, PSGSDF_PCG_TAGM=2: halo rows gathered at system scope from the first attempt on); PSGSDF_PCG_TAGM=1: on one rank only
-    bool pcg_tagm = true;                // PSGSDF_PCG_TAGM (default 2): the pipelined solve with self-validating exchanged values (pcg.hip k_cgp_solve<.., TM>); 0 = round 4's ordered hand-off; whether it also runs BETWEEN ranks: pcg_tagm_mr
-    int pcg_ablate = 0;                  // PSGSDF_PCG_ABLATE: timing ablations of the pipelined solve (wrong results; tools only)
+    int pcg_ablate = 0;                  // PSGSDF_PCG_ABLATE: timing ablations of the persistent solve, bits 1 and 4 (wrong results; tools only)
     bool pcg_prefetch = true;            // PSGSDF_PCG_PREFETCH=0: pipelined solve: the sums of a pass are only fetched after its gathers (not behind the last gather batch)
-    bool pcg_pipeline = true;            // PSGSDF_PCG_PIPELINE=0: the persistent solve with round 2's recurrences (k_cgf_solve: a pass waits for its own reduction)
     bool pcg_fuse_apply = true;          // PSGSDF_PCG_FUSE_APPLY=0: k_apply_dist behind it
-    bool pcg_xcd_local = true;           // PSGSDF_PCG_XCD_LOCAL=0: every record through memory (write-through stores)
     bool pcg_persist = true;             // PSGSDF_PCG_PERSIST=0: always the per-pass kernels
-    bool pcg_window = true;              // PSGSDF_PCG_WINDOW=0: the single-rank pipelined solve gathers per thread instead of reading an LDS window (pcg.hip k_cgp_solve<.., WIN>)
+    bool pcg_window = true;              // PSGSDF_PCG_WINDOW=0: the single-rank pipelined solve gathers per thread instead of reading an LDS window (pcg_solve.h k_cgp_solve<.., WIN>)
     int pcg_solve_rows = 0;              // PSGSDF_PCG_SOLVE_ROWS: rows per workgroup of the persistent solve on one rank (0: as many workgroups as CUs); tests shape the partition with it
     int* win_tab = nullptr;              // [6 kSolveMaxBlocksHost + 1] window table of this band and partition (pcg.hip k_solve_windows) + its largest total
     int win_G = 0, win_rows = 0, win_max = 0;      // ... the partition it was computed for (0: no table) and the largest window in doubles
@@ -139,7 +134,7 @@ struct psgsdf_ctx {
     int rank = 0, n_ranks = 1;
     int row0 = 0, row1 = 0, halo = 0;
     psge::Comm* comm = nullptr;          // transport of the multi-rank exchanges (comm.hip); null on a single-rank context
-    // cross-rank persistent solve (comm.hip xr_setup, pcg.hip k_cgf_solve<.., MR>): this rank's mailbox region, every rank's region and the two
+    // cross-rank persistent solve (comm.hip xr_setup, pcg_solve.h k_cgp_solve<.., MR>): this rank's mailbox region, every rank's region and the two
     // neighbours' band arenas mapped through IPC handles; rebuilt with every band
     bool xr_enable = true;               // PSGSDF_XR=0: multi-rank contexts always use the per-pass kernels + RCCL all-reduce (round 2)
     bool xr_ready = false; long long xr_solves = 0;

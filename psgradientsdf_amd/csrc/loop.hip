@@ -22,7 +22,7 @@ void cgf_shape(int nblk, int* G, int* rows) {
     *G = (per + trips - 1) / trips; *rows = r;
 }
 
-// Shape of the persistent solve (pcg.hip: k_cgf_solve): G workgroups of 512 threads, at most one per CU (all co-resident), the band dealt
+// Shape of the persistent solve (pcg_solve.h: k_cgp_solve): G workgroups of 512 threads, at most one per CU (all co-resident), the band dealt
 // evenly to them (<= 4 rows per thread).  One rank only -- a slab needs the other slabs' sums every pass,
 // which is the per-pass kernels' all-reduce -- and only with 16-bit column deltas and the assembly kernel's fused initialisation.
 bool cgf_solve_shape(psgsdf_ctx* c, int* G, int* rows_per_wg, bool any_ranks) {
@@ -76,7 +76,7 @@ int pcg_solve(psgsdf_ctx* c, SweepArgs& a, int* iters_out, int* success_out, dou
         const unsigned long long key = (++c->mbox_serial << 8) | 0x80u;
         st[3] = NAN; st[4] = 0.0;
         const int inject = (c->fault_solve > 0 && ++c->solves_seen == c->fault_solve) ? -7 : 0;      // PSGSDF_FAULT_SOLVE=n: one workgroup of the n-th solve stops publishing (tests the fallback below)
-        const XrArgs* xr = (c->n_ranks > 1 && c->xr_ready && as.pcg_asm) ? &c->xr_args : nullptr;
+        const XrArgs* xr = (c->n_ranks > 1 && c->xr_ready) ? &c->xr_args : nullptr;
         if (xr) {
             // the solve's epoch (the same on every rank: all ranks run the same solves) goes into every cross-rank tag, so nothing in the mailbox
             // regions is ever cleared between solves.  When the 14-bit epoch wraps, every region is cleared once behind an all-rank barrier
@@ -303,7 +303,7 @@ int step_begin(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* s
             }
             else {
                 materialize_fold(c);
-                { int Gs, Rs; if (c->pcg_fuse_asm && c->fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; } }   // the sweep clears the LOCAL tags of the persistent solve behind it (the cross-rank words carry the solve's epoch and are never cleared)
+                { int Gs, Rs; if (c->fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; } }   // the sweep clears the LOCAL tags of the persistent solve behind it (the cross-rank words carry the solve's epoch and are never cleared)
                 timed(c, "sweep_dist", [&] { launch_sweep_dist(a, c->stream); });
             }   // (LED: the fused albedo sweep's sums are still pending and this sweep writes the same slots)
             const int slots[2] = {SC_ENERGY, SC_NOBS}; double s[2];
@@ -418,7 +418,7 @@ int step_finish(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* 
             take_fold(c, a, 0u);
             if (c->fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks) { a.pcg_fuse_init = 1; a.pcg_init_blocks = band_blocks(c); }   // the assembly kernel initialises the PCG
             bool apply_in_solve = false;      // (the accepted count goes to the first G entries of a partial slot that holds one entry per 256 rows)
-            { int Gs, Rs; if (a.pcg_fuse_init && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = c->pcg_fuse_asm ? 1 : 0; apply_in_solve = a.pcg_asm && c->pcg_fuse_apply && Gs <= band_blocks(c); } }   // the assembly kernel also clears the persistent solve's tags
+            { int Gs, Rs; if (a.pcg_fuse_init && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; apply_in_solve = c->pcg_fuse_apply && Gs <= band_blocks(c); } }   // the assembly kernel also clears the persistent solve's tags
             if ((rc = comm_halo(c, c->band.blk, 14, 1))) return rc;   // multi-rank: rows of H next to a cut take contributions from the neighbour slab's voxel blocks
             if (!a.pcg_asm) { timed(c, "assemble", [&] { launch_assemble(a, c->stream); }); a.fold.n = 0; }      // (pcg_asm: the persistent solve assembles its rows itself; the distance sweep cleared its tags)
             int iters = 0, ok = 1; double err = 0;

@@ -1,7 +1,7 @@
 // pcg.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the Gradient-SDF photometric-stereo hot path:
 // the fused Jacobi-PCG of the distance system and the distance update.  No CUDA compatibility layer, no other back end.
 // Shared device helpers: device_common.h; the launchers are declared in engine.h.
-// The persistent solve's shared parts and its pipelined kernel: pcg_solve.h.
+// The persistent solve (k_cgp_solve) is a template in pcg_solve.h; its gathering instances are instantiated here.
 #include "pcg_solve.h"
 
 namespace psg {
@@ -319,242 +319,13 @@ void launch_cgf_pass(const SweepArgs& a, double* fs, double* part, int G, int ro
     else hipLaunchKernelGGL((k_cgf_pass<1, 4, false>), dim3(G), dim3(kBlock), 0, s, a, fs, part, k, kmax, mb, ablate);
 }
 
-// MR (multi-rank, z-slabs): the same kernel on every rank's slab, meeting the other ranks in two places.  (1) The records of the rows next to a cut
-// are ALSO written into the neighbour's halo rows (system-scope write-through stores through the IPC mapping), followed -- once the wave's stores
-// have drained -- by a tag in the neighbour's mailbox region; the neighbour's workgroups whose gathers reach across the cut wait for those tags
-// next to the tags of their local neighbours.  (2) The seven sums: every workgroup first obtains the rank's sums from the local all-gather exactly
-// as on one GPU; workgroup 0 then writes them as tagged granules into EVERY rank's region, and every workgroup sums the R rank granules of its
-// own region in rank order -- the same bits on every rank, one more hop per pass instead of a kernel boundary, a fold kernel and an RCCL
-// all-reduce (loop.hip: the per-pass path stays as the fallback and as the reference of the tests).
-template <int R, bool ASM, bool MR>
-__global__ void __launch_bounds__(kSolveThreads, 2) k_cgf_solve(SweepArgs a, double* fs, double* gran, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, XrArgs xr) {
-    __shared__ double red[8 * kSolveThreads / 64];
-    __shared__ int s_abort;
-    __shared__ int s_foreign;      // a neighbour workgroup (in band order) runs on another XCD
-    const Band& b = a.b;
-    const SolveWg<MR> wg(a, xr, fs, gran, rows_per_wg);
-    const int G = wg.G, tid = wg.tid, lb = wg.lb;
-    bool xcd_local = false;
-    const int plane = b.Spad * 4;
-    const __amdgpu_buffer_rsrc_t rH = __builtin_amdgcn_make_buffer_rsrc((void*)b.H, 0, kNQ * plane, 0x00020000);
-    auto push_record = [&](int buf, int rel, const float4& rec) {      // rel = row - row0
-        if (MR && rel < xr.give_lo) store16_sys(xr.lo_rec[buf] + rel, rec);
-        if (MR && rel >= wg.own_n - xr.give_hi) store16_sys(xr.hi_rec[buf] + (rel - (wg.own_n - xr.give_hi)), rec);
-    };
-    // ---- once: the rows of this thread.  The 19 coefficients of a row live in LDS ([row slot][column][thread]: conflict-free, R x 38 KB of
-    // the CU's 160 KB), the 9 index words and the row's own state in registers.
-    float* hs = (float*)psg_dyn_smem;
-    unsigned cp[R][(kNQ - 1) / 2]; float4 me[R]; float x[R]; int row[R]; bool live[R];
-    if (ASM) fold_pending<kBlock>(a, red);      // (no k_assemble in front of this kernel to fold the sums the distance sweep left pending)
-    double bb_thread = 0.0;                     // ASM: |b|^2 of this thread's rows (summed over the device with the sums of pass 0)
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-        row[u] = wg.own_row(u, live[u]);
-        float* hs_slot = hs + (size_t)u * kNQ * kSolveThreads + tid;
-        if (ASM) {
-            float inv; double rhs;
-            solve_assemble_row(a, row[u], hs_slot, inv, rhs);
-            const float r = (float)rhs;
-            me[u] = make_float4(r, 0.f, 0.f, inv);
-            if (live[u]) { store16_sc1(b.rec[1] + row[u], me[u]); push_record(1, row[u] - a.row0, me[u]); bb_thread += (double)r * (double)r; }      // what pass 0 of the neighbours gathers
-        } else {
-#pragma unroll
-            for (int q = 0; q < kNQ; ++q) {
-                float hv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rH, row[u] * 4, q * plane, 0));
-                if (q == 0 && a.damping != 0.0f) hv += a.damping * hv;
-                hs_slot[q * kSolveThreads] = hv;
-            }
-            me[u] = b.rec[1][row[u]];            // {r_0, 0, 0, inv} written by the assembly kernel
-        }
-        solve_load_columns(b, row[u], cp[u]);
-        x[u] = 0.f;
-    }
-    // |b|^2: from the assembly kernel's per-workgroup partials (an earlier kernel: plain loads) -- or, ASM, not known before the sums of pass 0
-    double bb = 0.0;
-    if (!ASM) {
-      double* src[1] = {fpart(a.pcg_part, -1, 6)};
-      double v = 0.0;
-      for (int i = tid; i < a.pcg_init_blocks; i += kSolveThreads) v += src[0][i];
-      v = wave_sum(v);
-      if ((tid & 63) == 0) red[tid >> 6] = v;
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < kSolveThreads / 64; ++i) bb += red[i];
-      __syncthreads();
-    } else {
-        // the records of this workgroup's rows are on their way: drained, then the flag the neighbours' pass 0 waits for
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) wg.publish_prologue(true);
-    }
-    float rhsNorm2 = (float)bb;
-    float thr = pcg_threshold(rhsNorm2);
-    float alpha_prev = 0.f, beta = 0.f, rr_cur = rhsNorm2;
-    if (!ASM && lb == 0 && tid == 0) fs[0] = bb;
-    int k = 0, status = 1;                    // status 1 = finished, 2 = a wait timed out
-    for (;; ++k) {
-        SOLVE_STAMP(0);
-        const unsigned want = (unsigned)k & 3u;            // tag of pass k-1 = ((k-1) + 1) & 3
-        const int pb = (k - 1) & 1;                        // the buffer pass k-1 published in
-        const double* gp = wg.gran_plane(pb, 0);
-        solve_keep_columns_packed<R>(cp);
-        if (k > 0 || ASM) {
-            // ---- A: wait for the neighbours' pass k-1 (ASM, pass 0: for their assembled records)
-            if (tid == 0) { s_abort = 0; if (ASM && k == 0) s_foreign = 0; }
-            __syncthreads();
-            wg.wait_band_neighbours(k == 0, pb, want, &s_abort, &s_foreign);
-            wg.wait_peer_tags(k == 0, pb, want, &s_abort);
-            if (!wg.neighbours_acquired(&s_abort)) { status = 2; break; }
-            if (ASM && k == 0) xcd_local = a.pcg_xcd_local && !s_foreign;
-            __syncthreads();
-        }
-        SOLVE_STAMP(1);
-        // ---- B: t = A p_k is linear in the gathered fields (A1 - alpha A2 + beta A3): the gathers run BEFORE alpha and beta exist, i.e.
-        // while the sums of the far workgroups are still on their way
-        const float4* __restrict__ rin = b.rec[(k + 1) & 1];
-        float4* __restrict__ rout = b.rec[k & 1];
-        double A1[R], A2[R], A3[R];
-        // the 18 neighbour records of a row in two batches of 9, software-pipelined ACROSS the rows of the thread: two batches (72 registers)
-        // are in flight at any time -- batch t+2 is requested into the registers batch t has just been consumed from, so a wave's memory
-        // requests never run dry while it converts and multiplies (one row at a time did: gather stage 4.1-5.1 -> 3.5-3.8 us)
-        float4 ob[2][9];
-        auto issue = [&](int t) {
-            const int u = t >> 1, j0 = (t & 1) * 9;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) { const int jj = j0 + j; const int pk = (int)cp[u][jj >> 1]; ob[t & 1][j] = rin[row[u] + ((jj & 1) ? (pk >> 16) : ((pk << 16) >> 16))]; }
-        };
-        issue(0);
-        issue(1);
-        double a1 = 0, a2 = 0, a3 = 0;
-#pragma unroll
-        for (int t = 0; t < 2 * R; ++t) {
-            const int u = t >> 1, j0 = (t & 1) * 9;
-            const float* hrow = hs + (size_t)u * kNQ * kSolveThreads + tid;
-            if (!(t & 1)) { const double hq = (double)hrow[0], iv = (double)me[u].w; a1 = hq * (iv * (double)me[u].x); a2 = hq * (iv * (double)me[u].y); a3 = hq * (double)me[u].z; }
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const double hq = (double)hrow[(j0 + j + 1) * kSolveThreads], iv = (double)ob[t & 1][j].w;
-                a1 += hq * (iv * (double)ob[t & 1][j].x); a2 += hq * (iv * (double)ob[t & 1][j].y); a3 += hq * (double)ob[t & 1][j].z;
-            }
-            asm volatile("" : "+v"(a1), "+v"(a2), "+v"(a3));      // the sums exist HERE: without this the compiler sinks the consumption of the
-            if (t & 1) { A1[u] = a1; A2[u] = a2; A3[u] = a3; }     // gathered records below the wait for the global sums (72 registers live across it)
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 2 < 2 * R) issue(t + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        SOLVE_STAMP(2);
-        if (force_passes > 0 && k == 9 && tid == 0) fs[16 + 1024 + lb] = (double)wall_clock64();            // gathers of pass 9 done
-        if (k > 0) {
-            // ---- C: the seven sums of pass k-1 of EVERY workgroup (data and tag in one granule: no fence needed for them)
-            // (requesting these granules ahead of time -- in front of the gathers or behind the last batch -- measured SLOWER: the sc1 loads
-            // lengthen the gather stage by 1-2 us, and the stage is a wait for the late workgroups, not a load latency; profiles/r02_notes.md)
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = 0.0;
-            if (tid < G) {
-                int spins = 0; bool ok = false;
-                while (!ok) {
-                    ok = true;
-#pragma unroll
-                    for (int q = 0; q < kCgfSums; ++q) { v[q] = __hip_atomic_load(gp + (size_t)q * kSolveMaxBlocks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && gran_tag_of(v[q]) == want; }
-                    if (ASM && k == 1) { v[7] = __hip_atomic_load(gp + (size_t)7 * kSolveMaxBlocks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && gran_tag_of(v[7]) == want; }   // |b|^2 travels with the sums of pass 0
-                    if (!ok) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++spins > wg.kLocalSpins || wg.aborted()) { s_abort = 1; break; }
-                    }
-                }
-            }
-            double t0, t1; wave_sum8(v, t0, t1);
-            wave_sum8_store<kSolveThreads / 64>(t0, t1, red, tid >> 6);
-            __syncthreads();
-            if (s_abort) { if (tid == 0) wg.raise_abort(); status = 2; break; }
-            const bool with_bb = ASM && k == 1;
-            double t[kCgfSums + 1];      // [7], with_bb: |b|^2
-#pragma unroll
-            for (int q = 0; q < kCgfSums; ++q) { double s_ = 0; for (int i = 0; i < kSolveThreads / 64; ++i) s_ += red[q * (kSolveThreads / 64) + i]; t[q] = s_; }
-            t[7] = 0.0;
-            if (with_bb) for (int i = 0; i < kSolveThreads / 64; ++i) t[7] += red[7 * (kSolveThreads / 64) + i];
-            __syncthreads();
-            if (MR) {
-                // ---- C2: the sums just obtained are this RANK's: the sums over all ranks
-                if (!wg.exchange_rank_sums(t, kCgfSums + (with_bb ? 1 : 0), pb, want, red, &s_abort)) { status = 2; break; }
-                __syncthreads();
-            }
-            if (with_bb) {
-                bb = t[7]; rhsNorm2 = (float)bb; thr = pcg_threshold(rhsNorm2);
-                if (lb == 0 && tid == 0) fs[0] = bb;
-            }
-            const float rz_old = (float)t[5];
-            alpha_prev = rz_old / (float)t[0];
-            const double al = (double)alpha_prev;
-            const float rz_cur = (float)(t[5] - 2.0 * al * t[1] + al * al * t[2]);
-            rr_cur = (float)(t[6] - 2.0 * al * t[3] + al * al * t[4]);
-            beta = rz_cur / rz_old;
-            if (force_passes > 0 && k == 9 && tid == 0) fs[16 + 256 + lb] = (double)wall_clock64();         // ... and when it had the sums of pass 8 of all the others
-            if (force_passes > 0 && k == 9 && tid == 0) fs[16 + 768 + lb] = (double)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));   // XCC_ID
-        }
-        if (force_passes > 0 && k == 9 && tid == 0) fs[16 + 512 + lb] = (double)wall_clock64();
-        SOLVE_STAMP(3);
-        const bool rhs_zero = (!ASM || k > 0) && rhsNorm2 == 0.f;          // (ASM: |b|^2 arrives with the sums of pass 0)
-        const bool stop = force_passes > 0 ? k >= force_passes : (rhs_zero || k == kmax || (k > 0 && rr_cur < thr));
-        // ---- D: finish pass k-1 for the own rows; pass k
-        double s[kCgfSums];
-#pragma unroll
-        for (int q = 0; q < kCgfSums; ++q) s[q] = 0;
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            if (k > 0 && !rhs_zero) x[u] = x[u] + alpha_prev * me[u].z;
-            if (stop) continue;
-            const float r_i = me[u].x - alpha_prev * me[u].y;
-            const float z_i = me[u].w * r_i;
-            const float p_i = z_i + beta * me[u].z;
-            const float tt = (float)(A1[u] - (double)alpha_prev * A2[u] + (double)beta * A3[u]);
-            me[u] = make_float4(r_i, tt, p_i, me[u].w);
-            if (live[u]) {
-                if (xcd_local) rout[row[u]] = me[u]; else store16_sc1(rout + row[u], me[u]);      // (all its readers share this XCD's L2 / through memory)
-                push_record(k & 1, row[u] - a.row0, me[u]);
-                const double rd = (double)r_i, td = (double)tt, iv = (double)me[u].w;
-                s[0] += (double)p_i * td; s[1] += iv * rd * td; s[2] += iv * td * td; s[3] += rd * td; s[4] += td * td;
-                s[5] += rd * (double)z_i; s[6] += rd * rd;
-            }
-        }
-        if (stop) break;
-        if (force_passes == -7 && k == 2 && lb == 1) { status = 2; break; }      // fault injection (psgsdf_debug_time_pcg_solve(passes = -7)): this workgroup never publishes pass 2 -- every other one must give up waiting, not hang
-        SOLVE_STAMP(4);
-        // ---- E: publish: the records have to be out (write-through, drained) before the seven tagged sums
-        double sv[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) sv[q] = q < kCgfSums ? s[q] : ((ASM && k == 0) ? bb_thread : 0.0);
-        double t0, t1; wave_sum8(sv, t0, t1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_sum8_store<kSolveThreads / 64>(t0, t1, red, tid >> 6);
-        __syncthreads();
-        SOLVE_STAMP(5);
-        if (tid < kCgfSums || (ASM && k == 0 && tid == 7)) {
-            double tot = 0;
-            for (int i = 0; i < kSolveThreads / 64; ++i) tot += red[tid * (kSolveThreads / 64) + i];
-            double* gq = gran + (size_t)(k & 1) * kSolveGranPlanes * kSolveMaxBlocks + (size_t)tid * kSolveMaxBlocks + lb;
-            __hip_atomic_store(gq, gran_tag(tot, (unsigned)(k + 1) & 3u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (MR && tid == 64) wg.peer_tag(k & 1, (unsigned)(k + 1) & 3u);      // (every wave drained its stores before the barrier above: the halo records are out)
-        __syncthreads();
-        SOLVE_STAMP(6);
-        if (force_passes > 0 && k == 8 && tid == 0) fs[16 + lb] = (double)wall_clock64();                 // timing hook: when every workgroup published pass 8 ...
-    }
-    // ---- leave: x of the own rows; the distance update; the outcome for the host and for the gated kernels behind this one
-    solve_apply_and_count<MR, R>(wg, x, row, live, status, rr_cur, rhsNorm2, red);
-    if (lb == 0 && tid == 0) solve_report(fs, mb, mb_key, status, k, rr_cur, rhsNorm2, thr);
-}
-#undef SOLVE_STAMP
-
 // ---- host side of the persistent solve (pcg_solve.h: one solve_prepare, one row-count dispatch)
 int cgf_solve_max_blocks(int rows) {
     return solve_with_rows(rows, [](auto rc) {
         constexpr int R = decltype(rc)::value;
         static const int per_cu = [] {      // once per row count: the least of all its instances
             int n = INT_MAX;
-            for (SolveKernel kern : {(SolveKernel)k_cgf_solve<R, false, false>, (SolveKernel)k_cgf_solve<R, true, false>, (SolveKernel)k_cgf_solve<R, true, true>, (SolveKernel)k_cgp_solve<R, false, false>,
-                                     (SolveKernel)k_cgp_solve<R, false, true>, (SolveKernel)k_cgp_solve<R, true, false>, (SolveKernel)k_cgp_solve<R, true, true>})
+            for (SolveKernel kern : {(SolveKernel)k_cgp_solve<R, false>, (SolveKernel)k_cgp_solve<R, true>})
                 n = std::min(n, solve_prepare(kern, solve_lds(R)));
             return n;
         }();
@@ -563,17 +334,14 @@ int cgf_solve_max_blocks(int rows) {
 }
 // returns 1 if the solve ran the windowed instance
 int launch_cgf_solve(const SweepArgs& a, double* fs, double* gran, int G, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, hipStream_t s, const XrArgs* xr) {
-    const bool mr = a.pcg_asm && xr && xr->n_ranks > 1;      // (without the fused assembly the ranks meet between per-pass kernels, loop.hip)
-    // The windowed instance: decided here, per launch, from the table's maximum -- only the single-rank production kernel, only on the partition the
+    const bool mr = xr && xr->n_ranks > 1;
+    // The windowed instance: decided here, per launch, from the table's maximum -- only on one rank, only on the partition the
     // table was computed for, only if the worst workgroup's window fits (pcg_window.hip)
-    if (!mr && a.pcg_asm && a.pcg_pipe == 2 && a.pcg_win && a.pcg_win_G == G && a.pcg_win_rows == rows_per_wg
+    if (!mr && a.pcg_win && a.pcg_win_G == G && a.pcg_win_rows == rows_per_wg
         && launch_cgp_solve_window(a, fs, gran, G, rows_per_wg, kmax, mb, mb_key, force_passes, s)) return 1;
     solve_with_rows((rows_per_wg + kSolveThreads - 1) / kSolveThreads, [&](auto rc) {
         constexpr int R = decltype(rc)::value;
-        SolveKernel kern;
-        if (a.pcg_asm && a.pcg_pipe)      // the pipelined recurrences (always with the fused assembly); TM: self-validating m (PSGSDF_PCG_TAGM; across ranks: = 2)
-            kern = mr ? (a.pcg_pipe == 3 ? k_cgp_solve<R, true, true> : k_cgp_solve<R, true, false>) : (a.pcg_pipe >= 2 ? k_cgp_solve<R, false, true> : k_cgp_solve<R, false, false>);
-        else kern = mr ? k_cgf_solve<R, true, true> : a.pcg_asm ? k_cgf_solve<R, true, false> : k_cgf_solve<R, false, false>;
+        const SolveKernel kern = mr ? k_cgp_solve<R, true> : k_cgp_solve<R, false>;
         hipLaunchKernelGGL(kern, dim3(G), dim3(kSolveThreads), solve_lds(R), s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, mr ? *xr : XrArgs{});
     });
     return 0;

@@ -1,6 +1,6 @@
-// pcg_solve.h -- the persistent distance solve as templates: what its kernels share (the workgroup's place in the band, the bounded waits of the
-// hand-off protocol, the assembly of a thread's rows, the epilogue), the pipelined production kernel k_cgp_solve, and the host-side row-count dispatch.
-// Instantiated by pcg.hip (every gathering instance, and the classic k_cgf_solve defined there) and by pcg_window.hip (the windowed instances).
+// pcg_solve.h -- the persistent distance solve as templates: the workgroup's place in the band, the bounded waits of the hand-off protocol, the
+// assembly of a thread's rows, the epilogue, the pipelined kernel k_cgp_solve itself, and the host-side row-count dispatch.
+// Instantiated by pcg.hip (the gathering instances) and by pcg_window.hip (the windowed instances).
 #pragma once
 #include "device_common.h"
 
@@ -9,26 +9,24 @@ namespace psg {
 __device__ __forceinline__ float pcg_threshold(float rhsNorm2) { return fmaxf(FLT_EPSILON * FLT_EPSILON * rhsNorm2, FLT_MIN); }
 
 // ------------------------------------------------------------------------------------------
-// The whole solve as ONE persistent kernel (single-rank contexts whose band fits the register file).
+// The whole solve as ONE persistent kernel (contexts whose band fits the register file and the LDS).
 //
 // A per-pass launch re-streams the 19 ELL coefficients and 9 index words of every row (152 B/row, 51 MB at the 256^3 band:
 // 9.7 of the pass's 14.3 us at the ~5.3 TB/s the L2-miss path sustains; profiles/r01_notes.md) although the matrix never
-// changes during a solve.  Here every thread loads the coefficients and column deltas of its R rows ONCE into registers
-// (28 dwords per row; 38 MB of the chip's 128 MB of VGPRs at 256^3), keeps its own {r, t, p, x} there too, and loops over
-// the passes; per pass it gathers the 18 neighbour records (16 B each, L2-resident: 5.4 MB per buffer), computes exactly what
-// k_cgf_pass computes (same recurrences, same seven sums, same fixed-order reduction, same stop rule) and meets the other
-// workgroups at a device-wide all-gather of the seven per-workgroup sums:
-//   publish : records with 16-byte write-through (sc1) stores -> every wave s_waitcnt vmcnt(0) -> __syncthreads -> seven 8-byte
-//             granules {sum with a 2-bit pass tag in its two lowest mantissa bits}, one sc1 store each: data and tag arrive
-//             together, no flag, no ordering between the seven.  (Plain stores + an agent-scope release fence measured 4.8 us
-//             for drain + write-back per pass; profiles/r02_notes.md.)
-//   wait    : in two steps.  The gathers only need the records of the few workgroups that are this one's neighbours in band order,
-//             and -- t = A1 - alpha A2 + beta A3 -- neither alpha nor beta: a few threads poll those neighbours' tags, lane 0 does an
-//             agent-scope acquire, and the gathers run while the sums of the far workgroups are still on their way.  Then thread t
-//             polls the seven granules of workgroup t until their tags name the pass, and the fixed-order sum over workgroups that
+// changes during a solve.  Here every thread assembles the coefficients of its R rows ONCE into LDS, keeps the column deltas
+// (9 packed words per row) and the row's own vectors in registers, and loops over the passes; per pass it obtains the 18
+// neighbour values of each row (L2-resident), updates its rows and meets the other workgroups at a device-wide all-gather of
+// the per-workgroup sums (k_cgp_solve below says which values and which sums):
+//   publish : a row's value is ONE double that carries its own tag (m_tag below), stored at agent scope; the sums are 8-byte granules
+//             {sum with a 2-bit pass tag in its two lowest mantissa bits}, one store each: data and tag arrive together, no flag, no
+//             ordering between them, no drain of the stores in front of them.  (Measured on the way here: plain stores + an agent-scope
+//             release fence cost 4.8 us for drain + write-back per pass, profiles/r02_notes.md; write-through stores, a drain, and a wait
+//             for the band neighbours' tags with an acquire behind it cost 1 us per pass more than this, profiles/r05_notes.md.  Both are
+//             gone: a value that is not the pass's yet is simply asked for again.)
+//   wait    : thread t polls the granules of workgroup t until their tags name the pass, and the fixed-order sum over workgroups that
 //             every workgroup computes identically gives alpha, beta, |r|^2 and the stop decision -- the same everywhere, so all
-//             workgroups leave in the same pass.  The records double-buffer exactly as in k_cgf_pass: a workgroup writes its pass-k
-//             records only after it has seen EVERY workgroup's pass k-1 sums, i.e. after every reader of the old ones is done.
+//             workgroups leave in the same pass.  The values double-buffer exactly as k_cgf_pass's records do: a workgroup writes its
+//             pass-k values only after it has seen EVERY workgroup's pass k-1 sums, i.e. after every reader of the old ones is done.
 // One workgroup of 512 threads per CU at most (grid <= the CU count, so all workgroups are co-resident); logical workgroup ids
 // are remapped so that every XCD owns a contiguous range of rows (gathers stay in that XCD's L2).  Every wait is bounded:
 // a workgroup that sees nothing for ~1 s raises the abort flag and every workgroup leaves (the host reports PSGSDF_ERR_DEVICE).
@@ -38,17 +36,6 @@ constexpr int kSolveThreads = 512;            // one workgroup of 8 waves per CU
 constexpr int kSolveMaxBlocks = 256;          // one per CU
 constexpr int kSolveMaxRows = 4;              // rows per thread: R x 38 KB of coefficients in the CU's 160 KB of LDS
 typedef float v4f_t __attribute__((ext_vector_type(4)));
-// 16-byte write-through store (sc1): the record reaches memory without a later L2 write-back, so publishing needs no release fence
-// (MI355X_MICROARCH.md "publish-large": 3.0 vs 8.2 us); the trailing s_nop keeps the assembler's hazard rules for inline VMEM
-__device__ __forceinline__ void store16_sc1(float4* p, const float4& v) {
-    const v4f_t d = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(d) : "memory");
-}
-// the same towards another GPU's memory (a neighbour slab's halo rows, IPC-mapped over xGMI): write-through at SYSTEM scope
-__device__ __forceinline__ void store16_sys(float4* p, const float4& v) {
-    const v4f_t d = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(d) : "memory");
-}
 __device__ __forceinline__ double gran_tag(double v, unsigned tag) { return __longlong_as_double((long long)(((unsigned long long)__double_as_longlong(v) & ~3ull) | tag)); }
 __device__ __forceinline__ unsigned gran_tag_of(double v) { return (unsigned)((unsigned long long)__double_as_longlong(v) & 3ull); }
 // cross-rank words (multi-rank solve): the tag is 16 bits wide, (epoch of the solve << 2 | pass tag) -- 2^-36 of the value, still far below the float the
@@ -107,11 +94,9 @@ __device__ __forceinline__ void assemble_row_regs(const SweepArgs& a, int i, dou
 }
 
 // ------------------------------------------------------------------------------------------
-// What the two persistent kernels share (k_cgf_solve: the classic recurrences; k_cgp_solve: the pipelined ones, production): the workgroup's place in
-// the band and in the slab, every bounded wait of the hand-off protocol with its abort path, the assembly of a thread's rows, the
-// distance update of the epilogue and the outcome the host reads.  The kernels differ in the recurrences, in what travels and in the barrier scheme --
-// and, as far as this code is concerned, in four parameters: the pass index of the prologue round, the LDS word that carries 'a wait gave up', the
-// buffer a stage sums in, and the number of sums.
+// The parts of k_cgp_solve that do not depend on its recurrences: the workgroup's place in the band and in the slab, the exchange of the ranks' sums
+//  with its bounded waits and the abort path, the assembly of a thread's rows, the distance update of the epilogue and the
+// outcome the host reads.
 // ------------------------------------------------------------------------------------------
 constexpr int kXrSpins = 1 << 24;            // bound of every wait for another RANK (~1 s)
 // stage timestamps of pass 8 (timing hook only: force_passes > 0), wall clock at 100 MHz, written by thread 0 of two workgroups
@@ -121,25 +106,17 @@ template <bool MR> struct SolveWg {
     static constexpr int kLocalSpins = MR ? kXrSpins : (1 << 22);      // MR: a local neighbour may itself be waiting for a late RANK -- the local waits must not expire first
     const SweepArgs& a; const XrArgs& xr; double* const fs; double* const gran; const int rows_per_wg;
     const int G = gridDim.x, tid = threadIdx.x;
-    // The XCD this workgroup REALLY runs on (HW_REG_XCC_ID): if every workgroup that gathers from its rows sits on the same XCD, its records can stay
-    // in that XCD's L2 (plain stores) instead of going through memory with write-through stores, which drop the line and make every reader fetch it at the
-    // cross-XCD rate (MI355X_MICROARCH.md: same-XCD hand-offs 1.7x; r02 notes section 8 measured 9.5-9.6 vs 9.9-10.5 us per pass but would not rely on an
-    // ASSUMED placement).  Here the neighbours tell each other where they are: the 'records are out' flag of the prologue carries 1 + the XCD id.
+    // The XCD this workgroup REALLY runs on (HW_REG_XCC_ID): what the prologue's flag and the timing hook report
     const int my_xcc = (int)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));
     // XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs; logical block lb gives XCD x the contiguous blocks [x G/8, (x+1) G/8)
     const int lb = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-    // MR: which of this workgroup's rows the neighbours hold as halo, and whose tags it has to wait for
     const int own_n = a.row1 - a.row0;
-    const int wg_first = lb * rows_per_wg, wg_last = min(own_n, wg_first + rows_per_wg) - 1;      // (relative to row0)
-    const bool cut_lo = MR && xr.give_lo > 0 && wg_first < xr.give_lo && wg_first < own_n;          // owns rows of the lower neighbour's upper halo
-    const bool cut_hi = MR && xr.give_hi > 0 && wg_last >= own_n - xr.give_hi && wg_first < own_n;
-    const int hi_first_wg = MR ? max(0, own_n - xr.give_hi) / rows_per_wg : 0;                      // first workgroup that owns such rows
+    // The workgroups whose rows this one gathers from, in band order.  (No reader since the values validate themselves.  Kept: without these two lines the
+    // compiler orders the prologue of the gathering instances differently, and the kernels are to stay as measured: profiles/r08_notes.md)
+    const int wg_first = lb * rows_per_wg;      // (relative to row0)
+    const int nlo = max(0, (wg_first - a.b.reach) / rows_per_wg), nhi = min(G - 1, (wg_first + rows_per_wg - 1 + a.b.reach) / rows_per_wg);
     double* const xr_me = MR ? xr.region[xr.rank] : nullptr;
     const unsigned etag0 = MR ? (xr.epoch & kXrEpochMask) << 2 : 0u;      // cross-rank tags: (epoch << 2 | pass tag)
-    // The workgroups whose records this one gathers from: rows within `reach` of its own range (a handful of neighbours in band order) ...
-    const int nlo = max(0, (wg_first - a.b.reach) / rows_per_wg), nhi = min(G - 1, (wg_first + rows_per_wg - 1 + a.b.reach) / rows_per_wg);
-    // ... and, MR, the neighbour slabs: rows within `reach` of a cut gather from halo rows
-    const bool need_lo = MR && xr.need_lo > 0 && wg_first < a.b.reach, need_hi = MR && xr.need_hi > 0 && wg_last + a.b.reach >= own_n;
 
     __device__ __forceinline__ SolveWg(const SweepArgs& a_, const XrArgs& xr_, double* fs_, double* gran_, int rows_per_wg_) : a(a_), xr(xr_), fs(fs_), gran(gran_), rows_per_wg(rows_per_wg_) {}
 
@@ -151,12 +128,6 @@ template <bool MR> struct SolveWg {
         return live ? i : a.row1 - 1;
     }
     __device__ __forceinline__ double* gran_plane(int buf, int q) const { return gran + ((size_t)buf * kSolveGranPlanes + q) * kSolveMaxBlocks; }
-    // the neighbour's mailbox slots this workgroup tags: it is the (lb)-th cut-side workgroup towards the lower neighbour, the (lb - hi_first_wg)-th towards the upper one
-    __device__ __forceinline__ void peer_tag(int buf, unsigned pass_tag) const {
-        const double v = xr_tag(1.0, etag0 | pass_tag);
-        if (cut_lo && lb < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank - 1] + kXrPtag + (1 * 3 + buf) * kXrPeerTags + lb, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);              // (side 1 of the lower rank = tags of its UPPER neighbour)
-        if (cut_hi && lb - hi_first_wg < kXrPeerTags) __hip_atomic_store(xr.region[xr.rank + 1] + kXrPtag + (0 * 3 + buf) * kXrPeerTags + (lb - hi_first_wg), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
     // 'a wait gave up': here and in every rank's region, so that every workgroup of every rank leaves
     __device__ __forceinline__ void raise_abort() const {
         __hip_atomic_store(fs + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -164,46 +135,10 @@ template <bool MR> struct SolveWg {
     }
     __device__ __forceinline__ bool aborted() const { return __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0; }
     __device__ __forceinline__ bool aborted_by_rank() const { return aborted() || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0; }
-    // Prologue (thread 0, behind the barrier that follows the drain of the workgroup's first stores): the flag the neighbours' first round waits for
-    // (plane 7 of buffer 1) carries 1 + the XCD id; tag_peers: the same news for the neighbour slabs (pass tag 1 in buffer 2)
-    __device__ __forceinline__ void publish_prologue(bool tag_peers) const {
+    // Prologue (thread 0, behind the barrier that follows the drain of the workgroup's first stores): 1 + the XCD id into plane 7 of buffer 1.
+    // (Nothing waits for this flag any more -- the exchanged values validate themselves -- but the store is part of the kernel as measured: kept.)
+    __device__ __forceinline__ void publish_prologue() const {
         __hip_atomic_store(gran_plane(1, 7) + lb, (double)(1 + my_xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (MR && tag_peers) peer_tag(2, 1u);
-    }
-    // Stage A, local: the records this workgroup gathers from are those of its NEIGHBOURS in band order: thread j waits for the tag of neighbour nlo + j
-    // (the tag of a workgroup's first sum of buffer pb is stored after its records have drained; prologue: its flag), not for the whole device.
-    // *foreign = 1 if a neighbour sits on another XCD (the relation is symmetric: whoever gathers from this workgroup is in [nlo, nhi])
-    __device__ __forceinline__ void wait_band_neighbours(bool prologue, int pb, unsigned want, int* abort_word, int* foreign) const {
-        if (tid > nhi - nlo) return;
-        int spins = 0;
-        const double* wp = (prologue ? gran_plane(1, 7) : gran_plane(pb, 0)) + nlo + tid;
-        double seen = 0.0;
-        while (prologue ? (seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0.0 : gran_tag_of(seen = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != want) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > kLocalSpins || aborted()) { *abort_word = 1; break; }
-        }
-        if (prologue && (int)seen != 1 + my_xcc) *foreign = 1;
-    }
-    // Stage A, MR: wait for the tags the neighbour slab's cut-side workgroups wrote into this rank's region after their records had drained
-    // (kXrPeerTags = 64 slots per side: threads 64..127 / 128..191 -- wavefronts 1 and 2, next to the local pollers in wavefront 0)
-    __device__ __forceinline__ void wait_peer_tags(bool prologue, int pb, unsigned want, int* abort_word) const {
-        const int side = tid >= 128 ? 1 : 0, j = tid - (side ? 128 : 64);
-        if (!MR || tid < 64 || tid >= 192 || j >= (side ? xr.wait_hi : xr.wait_lo) || !(side ? need_hi : need_lo)) return;
-        int spins = 0;
-        const double* wp = xr_me + kXrPtag + (side * 3 + (prologue ? 2 : pb)) * kXrPeerTags + j;
-        const unsigned wantx = etag0 | (prologue ? 1u : want);
-        while (xr_tag_of(__hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != wantx) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > kXrSpins || aborted_by_rank()) { *abort_word = 1; break; }
-        }
-    }
-    // Stage A, end (all threads): false = a wait gave up and the abort flag is raised; else the records are visible to this workgroup
-    // (MR: system scope -- the halo records came from another GPU).  The caller's next barrier publishes the acquire to the other wavefronts.
-    __device__ __forceinline__ bool neighbours_acquired(const int* abort_word) const {
-        __syncthreads();
-        if (*abort_word) { if (tid == 0) raise_abort(); return false; }
-        if (tid == 0) { if (MR) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
-        return true;
     }
     // Stage C2 (MR): t[0..n) are this RANK's sums (every local workgroup holds the same bits).  Workgroup 0 hands them to every rank as tagged granules of
     // buffer pb; every workgroup then adds the granules of its own region in rank order (one fixed tree: the same bits on every rank) -- all <= 32 of them
@@ -312,16 +247,17 @@ __device__ __forceinline__ void solve_report(double* fs, double* mb, unsigned lo
 }
 
 // ------------------------------------------------------------------------------------------
-// The persistent solve, PIPELINED (round 4): the same matrix-in-LDS kernel, the same hand-offs, but with the recurrences of
-// Ghysels & Vanroose's pipelined CG so that a pass no longer waits for its own reduction.
+// The persistent solve is PIPELINED (round 4): the recurrences of Ghysels & Vanroose's pipelined CG, so that a pass does not
+// wait for its own reduction.
 //
-// In k_cgf_solve the seven sums of pass k contain t_k = A p_k, i.e. they can only be published AFTER the gathers of pass k, and the next pass can
-// only start after they have gone round the device: per pass  tags ~0.9 + gathers ~4.2 + sums ~2.7 + finish ~1.1 = 9.5 us (tools/pcg_solve_time.py),
-// the 2.7 us being a pure wait for the slowest workgroup's publish to arrive.  Here a pass publishes, at its END, the next search-direction input
+// With the classic recurrences (k_cgf_pass; round 2's persistent kernel ran them too) the sums of pass k contain t_k = A p_k, i.e. they can only be
+// published AFTER the gathers of pass k, and the next pass can only start after they have gone round the device: per pass  tags ~0.9 + gathers ~4.2 +
+// sums ~2.7 + finish ~1.1 = 9.5 us (profiles/r02_notes.md), the 2.7 us being a pure wait for the slowest workgroup's publish to arrive.  Here a pass
+// publishes, at its END, the next search-direction input
 // m_{k+1} = M^-1 w_{k+1} AND the three sums of the NEXT pass -- gamma = r.u, delta = w.u, |r|^2 with u = M^-1 r, w = A u carried by recurrence --
 // none of which involves the matrix-vector product n_{k+1} = A m_{k+1} that the next pass gathers for.  The all-gather of the sums therefore runs
-// concurrently with the neighbour hand-off and the gathers, and is complete when they are:
-//     per pass  tags + gathers + finish   (~6 us: profiles/r04_notes.md)
+// concurrently with the gathers, and is complete when they are:
+//     per pass  gathers + finish   (~6 us: profiles/r04_notes.md)
 // Recurrences (Jacobi M = diag, so q = M^-1 s and m = M^-1 w need no extra vectors), Eigen's x0 = 0:
 //     r_0 = b, u_0 = M^-1 b, w_0 = A u_0 (one extra gather round in front);   pass k:  n = A (M^-1 w)   ||   gamma, delta, |r|^2 over the device
 //     beta = gamma / gamma_old (0 in pass 0), alpha = gamma / (delta - beta gamma / alpha_old)
@@ -331,7 +267,7 @@ __device__ __forceinline__ void solve_report(double* fs, double* mb, unsigned lo
 // measured margins in profiles/r04_parity_margins.json).  Stop rule, iteration count and info() are Eigen's: |r_k|^2 of the recursively updated
 // residual against max(eps^2 |b|^2, FLT_MIN), checked before update k + 1.  Gather rounds per solve: iterations + 2 (w_0, and the round that is in
 // flight when the stop is detected) instead of iterations + 1.
-// What travels: ONE float per row (m) instead of a 16-byte record, three tagged sums instead of seven (+ |b|^2 = the |r|^2 of pass 0).
+// What travels: ONE double per row (m) instead of k_cgf_pass's 16-byte record, three tagged sums instead of seven (+ |b|^2 = the |r|^2 of pass 0).
 // ------------------------------------------------------------------------------------------
 constexpr int kCgpSums = 3;
 constexpr int kCgpMaxRows = 4;                // row slots per thread the pipelined kernel supports
@@ -345,16 +281,16 @@ constexpr int kCgpMaxRows = 4;                // row slots per thread the pipeli
 #define PSG_WIN_PREFETCH 2                    // windowed instance: the sums are requested 0 = right behind the window's loads, 1 = behind the window's stores, 2 = behind the products of the
 #endif                                        // thread's first row (measured, profiles/r07_notes.md: 6.68 / 5.90 / 5.89 us per pass, 2 930 / 3 003 / 3 044 it/s: the earlier, the more often re-polled)
 constexpr int kCgpDepth = PSG_CGP_DEPTH;      // gather batches (of 9 doubles) in flight per thread
-__device__ __forceinline__ void store8_sc1(double* p, double v) { asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory"); }
 __device__ __forceinline__ void store8_sys(double* p, double v) { asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory"); }
 
-// TM (round 5, single rank, PSGSDF_PCG_TAGM): SELF-VALIDATING m.  Every exchanged value carries (solve epoch << 2 | pass tag) in its four lowest mantissa bits
+// SELF-VALIDATING m (round 5; between ranks too).  Every exchanged value carries (solve epoch << 2 | pass tag) in its four lowest mantissa bits
 // (2^-48 of a double that multiplies float coefficients), is stored write-through and gathered with agent-scope loads that are re-issued until the tag is
-// the pass's: no neighbour-tag wait, no acquire, no drain of the stores in front of the sums -- the hand-off of a pass is ONE trip through memory.
+// the pass's: no neighbour-tag wait, no acquire, no drain of the stores in front of the sums -- the hand-off of a pass is ONE trip through memory
+// (round 4's ordered hand-off -- store, drain, tag, poll, acquire, gather: three trips -- measured 7.9 us per pass against 6.9-7.0, profiles/r05_notes.md).
 __device__ __forceinline__ double m_tag(double v, unsigned tag) { return __longlong_as_double((long long)(((unsigned long long)__double_as_longlong(v) & ~15ull) | tag)); }
 __device__ __forceinline__ unsigned m_tag_of(double v) { return (unsigned)((unsigned long long)__double_as_longlong(v) & 15ull); }
 
-// WIN (single rank, TM; PSGSDF_PCG_WINDOW): the neighbour values of a pass come from an LDS WINDOW instead of 18 scattered gathers per row.  The rows of a
+// WIN (single rank; PSGSDF_PCG_WINDOW): the neighbour values of a pass come from an LDS WINDOW instead of 18 scattered gathers per row.  The rows of a
 // workgroup reference about three times its own row count in distinct band rows, in three contiguous ranges -- the z - 1 columns, the in-plane columns
 // (the own rows and their xy halo) and the z + 1 columns; which range a column belongs to is a compile-time property of its index (solve_col_seg).  The
 // static table a.pcg_win (k_solve_windows: once per band and partition) holds {first band row, length} of the three ranges of every workgroup; they lie
@@ -371,27 +307,26 @@ constexpr unsigned kWinZp = (1u << 4) | (1u << 9) | (1u << 11) | (1u << 14) | (1
 __host__ __device__ constexpr int solve_col_seg(int jj) { return ((kWinZm >> jj) & 1u) ? 0 : ((kWinZp >> jj) & 1u) ? 2 : 1; }
 constexpr bool solve_col_segs_match() { for (int jj = 0; jj < kNQ - 1; ++jj) { int o[3] = {0, 0, 0}; q_offset(jj + 1, o); if (solve_col_seg(jj) != o[2] + 1) return false; } return true; }
 static_assert(solve_col_segs_match(), "the window segment of a column is its z offset");
-template <int R, bool MR, bool TM = false, bool WIN = false>
+template <int R, bool MR, bool WIN = false>
 __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, double* fs, double* gran, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, XrArgs xr) {
     __shared__ double red[8 * kSolveThreads / 64];
-    __shared__ int s_abort;
-    // kFast (self-validating values: the production kernels): TWO workgroup barriers per pass instead of five (round 6: 7.05 -> 6.5 us per
+    [[maybe_unused]] __shared__ int s_abort;      // (no reader: cleared in the prologue round only.  Kept: the store is part of the kernel as measured)
+    // TWO workgroup barriers per pass instead of the five of a kernel that waits for its neighbours' tags (round 6: 7.05 -> 6.5 us per
     // pass).  What is left is one barrier per cross-wavefront sum: in front of stage C's reads of `red` and in front of stage E's reads of `red2`.  The sums
     // of C and E meet in buffers of their own, E's alternating by pass parity -- so neither the barrier between C's reads and E's writes nor the one behind
     // E's reads is needed: whoever writes a buffer again is two barriers further on than its last reader.  The 'a wait gave up' flag rotates through three
     // words (pass mod 3): thread 0 clears the word of pass k + 2 behind stage E's barrier of pass k -- its last readers passed that barrier with it, its next
     // raisers are two barriers away -- so the barrier that only published the cleared flag at the top of a pass goes too.  Every read of a pass's word lies
     // behind a barrier of that pass and every raise in front of it: all threads of the workgroup take the same decision.
-    constexpr bool kFast = TM;      // (multi-rank too: its stage C2 -- the ranks' sums -- gets a third buffer and keeps the one barrier in front of its reads: three per pass instead of seven)
-    __shared__ double red2[kFast ? 2 * 8 * kSolveThreads / 64 : 1];
-    __shared__ double red3[(kFast && MR) ? 8 * kSolveThreads / 64 : 1];
+    // (Multi-rank too: its stage C2 -- the ranks' sums -- gets a third buffer and keeps the one barrier in front of its reads: three per pass instead of seven.)
+    __shared__ double red2[2 * 8 * kSolveThreads / 64];
+    __shared__ double red3[MR ? 8 * kSolveThreads / 64 : 1];
     __shared__ int s_ab3[3];
-#define CGP_ABORT (*(kFast ? &s_ab3[(k + 3) % 3] : &s_abort))
-    __shared__ int s_foreign;
+#define CGP_ABORT s_ab3[(k + 3) % 3]
+    [[maybe_unused]] __shared__ int s_foreign;      // (no reader: see s_abort)
     const Band& b = a.b;
     const SolveWg<MR> wg(a, xr, fs, gran, rows_per_wg);
     const int G = wg.G, tid = wg.tid, lb = wg.lb;
-    bool xcd_local = false;
     double* const recd[2] = {(double*)b.rec[0], (double*)b.rec[1]};      // m_k lives in recd[k & 1] (u_0 of the prologue in recd[1]): the first Spad doubles of a record plane
     // the neighbour slab's halo row of the same band row.  (xr.lo_rec / hi_rec point at the first halo RECORD, 16 bytes per row: the same row counted in doubles)
     const int lo_row0 = MR && xr.lo_rec[0] ? (int)(xr.lo_rec[0] - xr.lo_base[0]) : 0;
@@ -400,7 +335,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         if (MR && rel >= wg.own_n - xr.give_hi) store8_sys((double*)xr.hi_rec[buf] + (rel - (wg.own_n - xr.give_hi)), v);
     };
     float* hs = (float*)psg_dyn_smem;
-    static_assert(!WIN || (TM && !MR), "the windowed instance exists for the single-rank production kernel only");
+    static_assert(!WIN || !MR, "the windowed instance exists for the single-rank kernel only");
     // WIN: the three ranges of this workgroup back to back behind the coefficients; band row i of segment s sits at win[wb<s> + i]
     double* const win = (double*)(psg_dyn_smem + sizeof(float) * (size_t)R * kNQ * kSolveThreads);
     int wb0 = 0, wb1 = 0, wb2 = 0, woff1 = 0, woff2 = 0, own_s = 0, own_cnt = 0, nforeign = 0;
@@ -414,7 +349,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         own_s = own_cnt > 0 ? wb1 + first : 0;      // the own rows' slots [own_s, own_s + own_cnt) lie inside the in-plane range
         nforeign = l0 + l1 + l2 - own_cnt;
     }
-    const unsigned mepoch = TM ? (1u + a.pcg_epoch % 3u) << 2 : 0u;      // 1 .. 3, never the epoch of the solve before; 0 = memory no solve has written yet (the planes are zeroed when the band is built)
+    const unsigned mepoch = (1u + a.pcg_epoch % 3u) << 2;      // 1 .. 3, never the epoch of the solve before; 0 = memory no solve has written yet (the planes are zeroed when the band is built)
     unsigned cp[R][(kNQ - 1) / 2]; int row[R]; bool live[R];
     double x[R], r[R], w[R], z[R], sv[R], pv[R]; float inv[R];      // every vector of the recurrences in double: see "precision" above
     fold_pending<kBlock>(a, red);      // the sums the distance sweep left pending
@@ -428,14 +363,14 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         x[u] = 0.0; z[u] = 0.0; sv[u] = 0.0; pv[u] = 0.0; w[u] = 0.0;
         if (live[u]) {
             const double u0 = (double)inv[u] * r[u];
-            if (TM) { const double ut = m_tag(u0, mepoch | 0u); __hip_atomic_store(recd[1] + row[u], ut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); push_record(1, row[u] - a.row0, ut); if constexpr (WIN) win[wb1 + row[u]] = ut; }
-            else { store8_sc1(recd[1] + row[u], u0); push_record(1, row[u] - a.row0, u0); }
+            const double ut = m_tag(u0, mepoch | 0u);
+            __hip_atomic_store(recd[1] + row[u], ut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); push_record(1, row[u] - a.row0, ut); if constexpr (WIN) win[wb1 + row[u]] = ut;
         }
         solve_load_columns(b, row[u], cp[u]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) wg.publish_prologue(!TM);
+    if (tid == 0) wg.publish_prologue();
     float rhsNorm2 = 0.f, thr = 0.f, rr_cur = 0.f;
     double gamma_old = 0.0, alpha = 0.0;
     int k = -1, status = 1;                   // k = -1: the extra round w_0 = A u_0
@@ -444,18 +379,11 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         const unsigned want = (unsigned)(k + 1) & 3u;      // tag of the sums published for pass k (k >= 0)
         const int pb = k & 1;                              // the buffer they were published in
         const double* gp = wg.gran_plane(pb, 0);
-        const int abl = (a.pcg_xcd_local >> 3) & 7;      // timing ablations (tools/pcg_variants.py; never set in production): 1 = every gather reads the row's own element, 2 = no neighbour-tag wait, 4 = the 8 in-plane columns are not fetched
+        const int abl = (a.pcg_xcd_local >> 3) & 7;      // timing ablations (tools/pcg_variants.py; never set in production): 1 = every gather reads the row's own element, 4 = the 8 in-plane columns are not fetched
         solve_keep_columns_packed<R>(cp);
-        // ---- A: wait for the neighbours' m_k (k = -1: for their u_0).  TM: the values validate themselves, nothing to wait for
-        if (!kFast || k < 0) {
-            if (tid == 0) { s_abort = 0; s_ab3[0] = 0; s_ab3[1] = 0; s_ab3[2] = 0; if (k < 0) s_foreign = 0; }
-            __syncthreads();
-        }
-        if (!TM) {
-            if (!(abl & 2)) wg.wait_band_neighbours(k < 0, pb, want, &CGP_ABORT, &s_foreign);
-            wg.wait_peer_tags(k < 0, pb, want, &CGP_ABORT);
-            if (!wg.neighbours_acquired(&CGP_ABORT)) { status = 2; break; }
-            if (k < 0) xcd_local = (a.pcg_xcd_local & 1) && !s_foreign;
+        // ---- A: the neighbours' m_k (k = -1: their u_0) validate themselves: nothing to wait for.  Once per solve: the 'a wait gave up' words
+        if (k < 0) {
+            if (tid == 0) { s_abort = 0; s_ab3[0] = 0; s_ab3[1] = 0; s_ab3[2] = 0; s_foreign = 0; }
             __syncthreads();
         }
         SOLVE_STAMP(1);
@@ -542,8 +470,8 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
                 //  a HALO row's value is written by the neighbour RANK: gathered at system scope from the first attempt on -- the tag alone cannot tell
                 // this pass's value from the one of four passes ago (a buffer's tags alternate between two values), so the load itself must not be served from a
                 // copy this device cached then.  Own rows: agent scope, as on one rank.
-                if (TM && MR && (srow < a.row0 || srow >= a.row1)) ob[t % kCgpDepth][j] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                else ob[t % kCgpDepth][j] = TM ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *src;
+                if (MR && (srow < a.row0 || srow >= a.row1)) ob[t % kCgpDepth][j] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                else ob[t % kCgpDepth][j] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         };
         // The sums of pass k were published when m_k was: by the time the last gather batch is on its way they have normally arrived, but FETCHING
@@ -558,7 +486,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             const int u = t >> 1, j0 = (t & 1) * 9;
             const float* hrow = hs + (size_t)u * kNQ * kSolveThreads + tid;
             if (!(t & 1)) { const double mine = (double)inv[u] * (k >= 0 ? w[u] : r[u]); acc = (double)hrow[0] * mine; }      // (the row's own m: what it published)
-            if (TM) {      // a value that is not this pass's yet: ask again (the producer is at most one hand-off behind)
+            {      // a value that is not this pass's yet: ask again (the producer is at most one hand-off behind)
                 const unsigned wantm = mepoch | want;
 #pragma unroll
                 for (int j = 0; j < 9; ++j) {
@@ -609,11 +537,9 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             double t[kCgpSums];
 #pragma unroll
             for (int q = 0; q < kCgpSums; ++q) { double s_ = 0; for (int i = 0; i < kSolveThreads / 64; ++i) s_ += red[q * (kSolveThreads / 64) + i]; t[q] = s_; }
-            if (!kFast) __syncthreads();      // (kFast: stage E has a buffer of its own)
             if (MR) {
                 // ---- C2: the sums just obtained are this RANK's: the sums over all ranks
-                if (!wg.exchange_rank_sums(t, kCgpSums, pb, want, kFast ? red3 : red, &CGP_ABORT)) { status = 2; break; }
-                if (!kFast) __syncthreads();
+                if (!wg.exchange_rank_sums(t, kCgpSums, pb, want, red3, &CGP_ABORT)) { status = 2; break; }
             }
             if (k == 0) { rhsNorm2 = (float)t[2]; thr = pcg_threshold(rhsNorm2); if (lb == 0 && tid == 0) fs[0] = t[2]; }
             rr_cur = (float)t[2];
@@ -651,26 +577,19 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             if (live[u]) {
                 s[0] += r[u] * ui; s[1] += w[u] * ui; s[2] += r[u] * r[u];
                 double* dst = recd[(k + 1) & 1] + row[u];
-                // readers on this XCD hit the line in its L2 if it is DIRTY there (a plain store: the per-pass acquire only drops clean lines); readers
-                // on another XCD need it in memory (write-through store).  A workgroup with neighbours on both sides does both.
-                if (TM) { const double mt = m_tag(mnext, mepoch | ((unsigned)(k + 2) & 3u)); __hip_atomic_store(dst, mt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); push_record((k + 1) & 1, row[u] - a.row0, mt); if constexpr (WIN) win[wb1 + row[u]] = mt; }
-                else {
-                    if (!xcd_local) store8_sc1(dst, mnext);
-                    *dst = mnext;
-                    push_record((k + 1) & 1, row[u] - a.row0, mnext);
-                }
+                const double mt = m_tag(mnext, mepoch | ((unsigned)(k + 2) & 3u));
+                __hip_atomic_store(dst, mt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); push_record((k + 1) & 1, row[u] - a.row0, mt); if constexpr (WIN) win[wb1 + row[u]] = mt;
             }
         }
         SOLVE_STAMP(4);
-        // ---- E: publish: m has to be out (drained) before the tagged sums
+        // ---- E: publish the three sums (m carries its own tag: no drain of its stores in front of them)
         const double s4[4] = {s[0], s[1], s[2], 0.0};
         const double tE = wave_sum4(s4);
-        if (!TM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        double* const redE = kFast ? red2 + ((k + 1) & 1) * (8 * kSolveThreads / 64) : red;
+        double* const redE = red2 + ((k + 1) & 1) * (8 * kSolveThreads / 64);
         wave_sum4_store<kSolveThreads / 64>(tE, redE, tid >> 6);
         __syncthreads();
-        if (TM && CGP_ABORT) { if (tid == 0) wg.raise_abort(); status = 2; break; }      // (a gather of this pass gave up)
-        if (kFast && tid == 0) s_ab3[(k + 5) % 3] = 0;      // the flag of pass k + 2: its readers (pass k - 1) are past this barrier, its raisers two barriers away
+        if (CGP_ABORT) { if (tid == 0) wg.raise_abort(); status = 2; break; }      // (a gather of this pass gave up)
+        if (tid == 0) s_ab3[(k + 5) % 3] = 0;      // the flag of pass k + 2: its readers (pass k - 1) are past this barrier, its raisers two barriers away
         SOLVE_STAMP(5);
         if (tid < kCgpSums) {
             double tot = 0;
@@ -678,13 +597,12 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
             double* gq = gran + (size_t)((k + 1) & 1) * kSolveGranPlanes * kSolveMaxBlocks + (size_t)tid * kSolveMaxBlocks + lb;
             __hip_atomic_store(gq, gran_tag(tot, (unsigned)(k + 2) & 3u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (MR && !TM && tid == 64) wg.peer_tag((k + 1) & 1, (unsigned)(k + 2) & 3u);
-        if (!kFast) __syncthreads();
         SOLVE_STAMP(6);
         if (force_passes > 0 && k == 8 && tid == 0) fs[16 + lb] = (double)wall_clock64();      // ... published at the end of pass 8 (m_9 and the sums of pass 9)
         if (force_passes > 0 && k == 9 && tid == 0) fs[16 + 1280 + lb] = (double)wall_clock64();  // ... and at the end of pass 9
     }
 #undef CGP_ABORT
+#undef SOLVE_STAMP
     // ---- leave: x of the own rows; the distance update; the outcome for the host and for the gated kernels behind this one
     // (Measured and rejected, profiles/r04_notes.md: the regrad -- k_derive -- in this epilogue behind one more neighbour hand-off.  Same bits, no
     // launch, but 2 648 vs 2 680 it/s: with one workgroup of eight waves per CU the dependent loads of three rows per thread take longer than the
@@ -696,9 +614,9 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
     if (lb == 0 && tid == 0) solve_report(fs, mb, mb_key, status, k, rr_cur, rhsNorm2, thr);
 }
 
-// ---- host side of the persistent solve: both kernels take the same arguments, the same launch shape and the same dynamic LDS
+// ---- host side of the persistent solve: every instance takes the same arguments and the same launch shape
 using SolveKernel = void (*)(SweepArgs, double*, double*, int, int, double*, unsigned long long, int, XrArgs);
-static_assert(kCgpMaxRows == kSolveMaxRows && kSolveMaxRows == 4, "every row count has both kernels; solve_with_rows lists the row counts");
+static_assert(kCgpMaxRows == kSolveMaxRows && kSolveMaxRows == 4, "solve_with_rows lists the row counts");
 static size_t solve_lds(int rows) { return sizeof(float) * (size_t)rows * kNQ * kSolveThreads; }
 // > 64 KB of dynamic LDS has to be asked for; returns the resident workgroups per CU (0: the instance cannot run)
 static int solve_prepare(SolveKernel kern, size_t lds) {

@@ -1,10 +1,10 @@
-// pcg_window.hip -- the windowed instances of the persistent distance solve (pcg_solve.h k_cgp_solve<R, false, true, WIN = true>): their static window
+// pcg_window.hip -- the windowed instances of the persistent distance solve (pcg_solve.h k_cgp_solve<R, false, WIN = true>): their static window
 // table, whether a band's windows fit next to the coefficients, and their launch.  A translation unit of its own: pcg.hip holds the gathering instances.
 #include "pcg_solve.h"
 
 namespace psg {
 
-// ---- the windowed instance (k_cgp_solve<R, false, true, true>): its static table and whether a band's windows fit
+// ---- the windowed instance (k_cgp_solve<R, false, true>): its static table and whether a band's windows fit
 // Per workgroup of the partition (G x rows_per_wg contiguous rows) and per segment s = z - 1, in-plane, z + 1: tab[6 lb + 2 s] = the first band row,
 // tab[6 lb + 2 s + 1] = the length of the range that covers every row the workgroup's rows reference through their packed column deltas, clipped to the
 // band; the in-plane range always contains the own rows, an absent column (delta 0) widens nothing.  *max_total = the largest sum of the three lengths.
@@ -56,7 +56,7 @@ static int solve_window_capacity(int rows) {      // doubles a window may hold a
         else {
         static const int cap = [] {
             hipFuncAttributes fa{};
-            if (hipFuncGetAttributes(&fa, (const void*)k_cgp_solve<R, false, true, true>) != hipSuccess || fa.sharedSizeBytes + solve_lds(R) >= kSolveLdsBytes) return 0;
+            if (hipFuncGetAttributes(&fa, (const void*)k_cgp_solve<R, false, true>) != hipSuccess || fa.sharedSizeBytes + solve_lds(R) >= kSolveLdsBytes) return 0;
             return (int)std::min<size_t>((kSolveLdsBytes - fa.sharedSizeBytes - solve_lds(R)) / sizeof(double), (size_t)kWinLoads * kSolveThreads);
         }();
         return cap;
@@ -71,7 +71,7 @@ static size_t solve_window_lds(int rows, int doubles) {
         else {
         static size_t prepared = 0; static int resident = 0;      // the last size this instance was prepared for
         const size_t lds = solve_lds(R) + sizeof(double) * (size_t)doubles;
-        if (lds != prepared) { resident = solve_prepare(k_cgp_solve<R, false, true, true>, lds); prepared = lds; }
+        if (lds != prepared) { resident = solve_prepare(k_cgp_solve<R, false, true>, lds); prepared = lds; }
         return resident >= 1 ? lds : 0;
         }
     });
@@ -83,7 +83,7 @@ bool launch_cgp_solve_window(const SweepArgs& a, double* fs, double* gran, int G
     if (!lds) return false;
     solve_with_rows(rows, [&](auto rc) {
         constexpr int R = decltype(rc)::value;
-        if constexpr (R < kCgpMaxRows) hipLaunchKernelGGL((k_cgp_solve<R, false, true, true>), dim3(G), dim3(kSolveThreads), lds, s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, XrArgs{});
+        if constexpr (R < kCgpMaxRows) hipLaunchKernelGGL((k_cgp_solve<R, false, true>), dim3(G), dim3(kSolveThreads), lds, s, a, fs, gran, rows_per_wg, kmax, mb, mb_key, force_passes, XrArgs{});
     });
     return true;
 }

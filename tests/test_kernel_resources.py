@@ -32,20 +32,12 @@ def resources(src, tmp_path):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_persistent_distance_step_does_not_spill(tmp_path):
     res = resources("pcg.hip", tmp_path)
-    solve = {k: v for k, v in res.items() if "k_cgf_solve" in k}
-    assert len(solve) == 12                                            # R = 1..4 x {without, with the fused assembly, with it across ranks (MR)}
-    for k, v in solve.items():
-        if "ILi4E" in k:
-            continue                                                   # 4 rows per thread (bands of 393k-524k rows): not tuned
-        if "ILi3ELb1ELb1E" in k:
-            assert v["scratch"] <= 128, (k, v)                         # the multi-rank instance at 3 rows per thread spills a little (a slab of a partitioned band rarely needs it)
-            continue
-        assert v["scratch"] == 0 and v["vgpr"] <= 256, (k, v)
+    assert not [k for k in res if "k_cgf_solve" in k]                  # (round 2's persistent kernel with the classic recurrences is gone)
     pipelined = {k: v for k, v in res.items() if "k_cgp_solve" in k}
-    assert len(pipelined) == 16                                        # the production kernels: R = 1..4 x {one rank, across ranks (MR)} x {ordered by flags, self-validating values (TM)}
+    assert len(pipelined) == 8                                         # the gathering instances: R = 1..4 x {one rank, across ranks (MR)}
     for k, v in pipelined.items():
         if "ILi4E" in k:
-            continue                                                   # 4 rows per thread: not tuned, as above
+            continue                                                   # 4 rows per thread (bands of 393k-524k rows): not tuned
         assert v["scratch"] == 0 and v["vgpr"] <= 256, (k, v)
     passk ={k: v for k, v in res.items() if "k_cgf_pass" in k and "ILi1ELi4E" in k}
     assert passk and all(v["vgpr"] <= 128 and v["scratch"] == 0 for v in passk.values()), passk      # the per-pass kernel: 4 waves per SIMD

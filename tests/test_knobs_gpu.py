@@ -1,7 +1,7 @@
 """The engine's latency tricks must not change results: PCG stop test by watching the mapped mailbox vs draining the stream
 (PSGSDF_PCG_POLL), scalar folds done by the next kernel vs by a kernel of their own (PSGSDF_FOLD_IN_NEXT), albedo update applied by the sweep vs by its own kernel (PSGSDF_FUSE_ALBEDO), launch shape of the
 fused PCG pass (PSGSDF_PCG_ROWS / PSGSDF_PCG_BLOCKS), the distance step as one persistent kernel (assembly + solve + update) vs its parts
-(PSGSDF_PCG_FUSE_APPLY / PSGSDF_PCG_FUSE_ASM / PSGSDF_PCG_PERSIST).  Each variant runs in its own process (the knobs are read at create time)."""
+(PSGSDF_PCG_FUSE_APPLY / PSGSDF_PCG_PERSIST).  Each variant runs in its own process (the knobs are read at create time)."""
 import json
 import os
 import subprocess
@@ -86,23 +86,17 @@ def test_pcg_launch_shape_only_changes_rounding(built):
 @pytest.mark.parametrize("model", ["SH1", "LED"])
 def test_distance_step_fusions_are_bitwise_neutral(built, model):
     """The persistent solve kernel that assembles its own rows (register accumulation in assemble_row's order) and applies the distance update
-    in its epilogue must give the bits of the same kernel with k_apply_dist behind it, with every value through memory instead of the XCD's L2, and
+    in its epilogue must give the bits of the same kernel with k_apply_dist behind it, and
     with the sums fetched after instead of behind the gathers -- energies, iteration counts and the optimised state, through psgsdf_optimize too.
-    The CLASSIC recurrences (round 2's persistent kernel, the same with k_assemble in front, the per-pass kernels that multi-rank fallbacks and
-    512^3 bands run) agree with each other to the bit as well; between the two families -- pipelined recurrences in double vs Eigen's in float --
+    The CLASSIC recurrences (the per-pass kernels that multi-rank fallbacks and 512^3 bands run) give the same bits on XCD-contiguous and on
+    physical row blocks; between the two families -- pipelined recurrences in double vs Eigen's in float --
     only rounding differs: same iteration counts (+-1), energies to 2e-5."""
     ref = run(model, {}, full=True)
-    for env in ({"PSGSDF_PCG_FUSE_APPLY": "0"}, {"PSGSDF_PCG_XCD_LOCAL": "0"}, {"PSGSDF_PCG_PREFETCH": "0"}):
+    for env in ({"PSGSDF_PCG_FUSE_APPLY": "0"}, {"PSGSDF_PCG_PREFETCH": "0"}):
         got = run(model, env, full=True)
         assert got == ref, (env, got, ref)
-    # round 5: the exchanged values carry their own tags in four mantissa bits (2^-48) instead of being ordered behind flags -- same pass counts, the rest to rounding
-    untagged = run(model, {"PSGSDF_PCG_TAGM": "0"}, full=True)
-    assert untagged["cg"] == ref["cg"] and untagged["n2"] == ref["n2"], (untagged["cg"], ref["cg"])
-    assert all(abs(a - b) <= 1e-7 * abs(b) for a, b in zip(untagged["e"] + untagged["e2"], ref["e"] + ref["e2"])), (untagged["e"], ref["e"])
-    assert abs(untagged["dsum"] - ref["dsum"]) <= 1e-7 * ref["dsum"] and abs(untagged["psum"] - ref["psum"]) <= 1e-7 * ref["psum"]
-    classic = run(model, {"PSGSDF_PCG_PIPELINE": "0"}, full=True)
-    for env in ({"PSGSDF_PCG_FUSE_ASM": "0"}, {"PSGSDF_PCG_PERSIST": "0"}, {"PSGSDF_PCG_PIPELINE": "0", "PSGSDF_PCG_XCD_LOCAL": "0"},
-                {"PSGSDF_PCG_PERSIST": "0", "PSGSDF_XCD_MAP": "35"}):      # (round 6: the per-pass kernel's XCD-contiguous row blocks, bit 7 of the map, switched off)
+    classic = run(model, {"PSGSDF_PCG_PERSIST": "0"}, full=True)
+    for env in ({"PSGSDF_PCG_PERSIST": "0", "PSGSDF_XCD_MAP": "35"},):      # (round 6: the per-pass kernel's XCD-contiguous row blocks, bit 7 of the map, switched off)
         got = run(model, env, full=True)
         assert got == classic, (env, got, classic)
     assert all(abs(a - b) <= 1 for a, b in zip(classic["cg"], ref["cg"])) and classic["n2"] == ref["n2"]

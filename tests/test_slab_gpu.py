@@ -70,7 +70,7 @@ def test_native_slab_loop_matches_single_context(built, margins, tmp_path, model
     # "rccl-perpass": the PCG as the multi-rank path runs it (one kernel, one fold and one RCCL all-reduce of 7 doubles per pass) -- a one-rank
     # communicator would otherwise use the persistent single-kernel solve, which needs no exchange
     # "gloo-xr0": the multi-rank PCG of round 2 (per-pass kernels, one all-reduce of 7 doubles and one halo exchange per pass); without it the ranks
-    # run the CROSS-RANK PERSISTENT solve (pcg.hip k_cgf_solve<.., MR>: halo records pushed into the neighbour's band through IPC mappings, rank-level
+    # run the CROSS-RANK PERSISTENT solve (pcg_solve.h k_cgp_solve<.., MR>: halo records pushed into the neighbour's band through IPC mappings, rank-level
     # sums through every rank's mailbox region) -- here between two / three processes sharing the one GPU
     # "gloo-xf0": the per-frame light / pose rows through an all-reduce and the solve kernels (round 3); without it they meet inside the sweeps
     extra = {"PSGSDF_PCG_PERSIST": "0"} if transport == "rccl-perpass" else {"PSGSDF_XR": "0"} if transport == "gloo-xr0" else {"PSGSDF_XF": "0"} if transport == "gloo-xf0" else {"PSGSDF_XS": "0"} if transport == "gloo-xs0" else {"PSGSDF_XH": "0"} if transport == "gloo-xh0" else None      # "gloo-xs0": scalar read-backs staged and all-reduced (round 3) instead of exchanged by the folding thread

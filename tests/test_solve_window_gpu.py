@@ -1,4 +1,4 @@
-"""The windowed instance of the persistent distance solve (PSGSDF_PCG_WINDOW, pcg.hip k_cgp_solve<.., WIN>: every workgroup fetches the band rows its
+"""The windowed instance of the persistent distance solve (PSGSDF_PCG_WINDOW, pcg_solve.h k_cgp_solve<.., WIN>: every workgroup fetches the band rows its
 rows reference once per pass into an LDS window instead of gathering 18 values per row and thread) must give the bits of the gathering instance:
 the same products in the same order.  Every case runs the same scene in two fresh contexts, window on and off, and compares the raw bits of the band
 distances, the CG pass counts and the energies; the tuning record must say which instance the last solve ran -- a band whose windows do not fit falls

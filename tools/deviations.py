@@ -35,7 +35,7 @@ from oracle import oracle  # noqa: E402
 
 CSRC = os.path.join(ROOT, "psgradientsdf_amd", "csrc")
 BITS = {1: "no FMA contraction", 2: "IEEE weights / logf, r / lambda", 4: "bilinear weights and 1/z through double", 8: "observation sums in double", 16: "Jacobian chains in the reference's order"}
-SOLVERS = {"PSGSDF_FRAME_SOLVE": "eigen", "PSGSDF_PCG_PIPELINE": "0", "PSGSDF_PCG_PERSIST": "0"}      # the reference's light / pose solver; the classic per-pass float recurrences
+SOLVERS = {"PSGSDF_FRAME_SOLVE": "eigen", "PSGSDF_PCG_PERSIST": "0"}      # the reference's light / pose solver; the classic per-pass float recurrences
 
 
 def variants():

@@ -10,7 +10,8 @@
 //      PLAIN loads, count records that do not carry the round's value, answer through a flag in the peer's direction;
 //   3. the peer's kernel per round: sc0 sc1 write-through 16-byte stores of the payload, s_waitcnt vmcnt(0), system-scope relaxed store of the
 //      tagged flag, wait for the answer.
-// These are exactly the store / load / fence forms of pcg.hip k_cgf_solve<.., MR>.  It also times a local streaming read of 64 MiB of each kind
+// These are the store / load / fence forms of the 16-byte record hand-off that comm.hip's probe still plays in its even rounds (the persistent
+// solve, pcg_solve.h k_cgp_solve<.., MR>, now hands over self-validating 8-byte values).  It also times a local streaming read of 64 MiB of each kind
 // (is the owner's mapping of fine-grained / uncached memory cached?).  Prints one line per kind: ipc ok?, stale records, timeouts, us per round, GB/s.
 #include <hip/hip_runtime.h>
 #include <stdio.h>

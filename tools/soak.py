@@ -27,21 +27,18 @@ VARIANTS = {
     "default": {},
     "fold0": {"PSGSDF_FOLD_IN_NEXT": "0"},
     "poll0": {"PSGSDF_PCG_POLL": "0"},
-    "persist0": {"PSGSDF_PCG_PERSIST": "0"},     # per-pass kernels: the CLASSIC recurrences (family "classic": bit-identical among themselves, rounding-level apart from the pipelined default)
-    "pipeline0": {"PSGSDF_PCG_PIPELINE": "0"},   # persistent kernel with the classic recurrences (same family as persist0)
-    "tagm0": {"PSGSDF_PCG_TAGM": "0"},           # pipelined solve without the self-validating exchanged values (round 4's hand-off: tags, acquire, drain) -- family "untagged": 2^-48 of the exchanged values apart
+    "persist0": {"PSGSDF_PCG_PERSIST": "0"},     # per-pass kernels: the CLASSIC recurrences (family "classic": rounding-level apart from the pipelined default)
     "prefetch0": {"PSGSDF_PCG_PREFETCH": "0"},   # pipelined solve: sums requested after the last gather batch
     "fmsolve0": {"PSGSDF_FM_SOLVE": "0"},        # light / pose solves as kernels of their own
     "fmsolve2": {"PSGSDF_FM_SOLVE": "2"},        # ... only the LED light vector
     "xcdmap0": {"PSGSDF_XCD_MAP": "0"},          # physical workgroup ids (no XCD-contiguous mapping)
     "xcdmap7": {"PSGSDF_XCD_MAP": "7"},          # ... also for the distance sweep
     "xcdmap99": {"PSGSDF_XCD_MAP": "99"},        # heaviest-first dispatch for every per-observation voxel-major kernel
-    "xcdlocal0": {"PSGSDF_PCG_XCD_LOCAL": "0"},  # persistent solve: every record through memory instead of staying in the XCD's L2 where all its readers are
     "spec0": {"PSGSDF_SPECULATE": "0"},          # every iteration closed before the next one starts (round 2)
     "nocheck": {"PSGSDF_MBOX_CHECK": "0", "PSGSDF_USE_DEV_LIB": "1"},      # read-backs taken on the marker's say-so (round 2): expected to deviate now and then
 }
 KNOB_NAMES = sorted({k for v in VARIANTS.values() for k in v})
-FAMILY = {"persist0": "classic", "pipeline0": "classic", "tagm0": "untagged"}      # which distance-solve recurrences a variant runs (default: pipelined)
+FAMILY = {"persist0": "classic"}      # which distance-solve recurrences a variant runs (default: pipelined)
 
 
 def _hash(a):

@@ -6,9 +6,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from psgradientsdf_amd import capi, synth
 sc = synth.make_scene(N=256, F=12, W=320, H=240, model="SH1")
 out = {}
-for name, env in (("production", {}), ("own_element", {"PSGSDF_PCG_ABLATE": "1"}), ("no_in_plane_columns", {"PSGSDF_PCG_ABLATE": "4"}), ("both", {"PSGSDF_PCG_ABLATE": "5"}), ("untagged", {"PSGSDF_PCG_TAGM": "0"}), ("untagged_no_in_plane", {"PSGSDF_PCG_TAGM": "0", "PSGSDF_PCG_ABLATE": "4"})):
-    for k in ("PSGSDF_PCG_ABLATE", "PSGSDF_PCG_TAGM"):
-        os.environ.pop(k, None)
+for name, env in (("production", {}), ("own_element", {"PSGSDF_PCG_ABLATE": "1"}), ("no_in_plane_columns", {"PSGSDF_PCG_ABLATE": "4"}), ("both", {"PSGSDF_PCG_ABLATE": "5"})):
+    os.environ.pop("PSGSDF_PCG_ABLATE", None)
     os.environ.update(env)
     eng = capi.load_engine(sc, sc.K, capi.default_settings(capi.SH1), 0, dev=True); eng.load_scene(sc); eng.init_albedo(); eng.normalize_weights()
     t = {}
