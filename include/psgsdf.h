@@ -421,7 +421,7 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* ctx, int64_t out[8]);
  * normal operation.  psgsdf_get_tuning reports what was set and what it resolved to.
  *   PSGSDF_PCG_POLL, PSGSDF_SPECULATE, PSGSDF_SPECULATE_MR, PSGSDF_FOLD_IN_NEXT, PSGSDF_FUSE_ALBEDO, PSGSDF_FUSE_PCG_INIT        (0 / 1) host-side scheduling
  *   PSGSDF_PCG_PERSIST (0: the per-pass kernels with the classic float recurrences instead of the persistent pipelined solve), PSGSDF_PCG_WINDOW (0: the single-rank persistent solve gathers its neighbour values per thread instead of reading them from an LDS window; the same bits;
- *   "effective.solve_window" says whether a band's windows fit and what the last solve ran), PSGSDF_PCG_SOLVE_ROWS (rows per workgroup of the persistent solve on one rank; default: as many workgroups as CUs), PSGSDF_PCG_PREFETCH, PSGSDF_PCG_FUSE_APPLY,
+ *   "effective.solve_window" says whether a band's windows fit and what the last solve ran), PSGSDF_PCG_SOLVE_ROWS (rows per workgroup of the persistent solve on one rank; default: as many workgroups as CUs), PSGSDF_PCG_FUSE_APPLY,
  *   PSGSDF_PCG_COL16*, PSGSDF_PCG_ROWS*, PSGSDF_PCG_BLOCKS*                                                                        distance solve
  *   PSGSDF_FRAME_SOLVE (ldlt | eigen: psgsdf_set_frame_solver; the ONE knob that changes results beyond rounding),
  *   PSGSDF_FM_SOLVE, PSGSDF_FM_ROWS*, PSGSDF_IMG_COMPACT, PSGSDF_XCD_MAP, PSGSDF_XCD_STRIPE                                        sweeps

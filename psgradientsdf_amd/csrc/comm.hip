@@ -556,13 +556,6 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
             c->hx_peer_off[sd] = sd == 0 ? sizeof(unsigned) * kHxWords * nlo : 0;
         }
     }
-    // the launch shapes of the neighbours (a function of their own row count and the CU count, the same on every rank): how many of their
-    // workgroups own rows this slab holds as halo = how many tags its cut-side workgroups wait for
-    auto shape_of = [&](int own, int* G, int* per) {
-        const int cap = std::min(c->num_cu, kSolveMaxBlocksHost);
-        int g = std::min(cap, (own + kSolveThreadsHost - 1) / kSolveThreadsHost); g = std::max(8, g / 8 * 8); if (g > cap) g = cap;
-        *G = g; *per = ((own + g - 1) / g + 63) / 64 * 64;
-    };
     XrArgs x{}; x.rank = me; x.n_ranks = R;
     x.need_lo = c->need[0]; x.need_hi = c->need[1]; x.give_lo = c->give[0]; x.give_hi = c->give[1];
     if (ok) {
@@ -572,22 +565,11 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
             const int own_p = (int)info[3 * (me - 1) + 2], need_lo_p = (int)info[3 * (me - 1)];
             // its upper halo rows start at its row1 = need_lo_p + own_p (local band order: lower halo, own rows, upper halo)
             for (int q = 0; q < 2; ++q) { x.lo_base[q] = (float4*)((char*)c->band_peer[0] + (size_t)sl[128 + q]); x.lo_rec[q] = x.lo_base[q] + (need_lo_p + own_p); }
-            int G, per; shape_of(own_p, &G, &per);
-            const int first = std::max(0, own_p - c->need[0]) / per, last = (own_p - 1) / per;      // its workgroups that own its last need_lo(me) rows
-            x.wait_lo = c->need[0] > 0 ? last - first + 1 : 0;
         }
         if (me < R - 1) {
             const double* sl = buf.data() + (size_t)(me + 1) * kSlice;
-            const int own_p = (int)info[3 * (me + 1) + 2];
             for (int q = 0; q < 2; ++q) x.hi_rec[q] = (float4*)((char*)c->band_peer[1] + (size_t)sl[128 + q]);      // its lower halo rows are its first rows
-            int G, per; shape_of(own_p, &G, &per);
-            x.wait_hi = c->need[1] > 0 ? std::min(own_p, c->need[1]) > 0 ? (std::min(own_p, c->need[1]) - 1) / per + 1 : 0 : 0;
         }
-        if (x.wait_lo > kXrPeerTags || x.wait_hi > kXrPeerTags) ok = false;
-        // (this rank's own cut-side workgroups must fit the neighbours' tag slots too: the same formula on their side)
-        int G, per; shape_of(c->row1 - c->row0, &G, &per);
-        if (c->give[0] > 0 && (c->give[0] - 1) / per + 1 > kXrPeerTags) ok = false;
-        if (c->give[1] > 0 && (c->row1 - c->row0 - 1) / per - std::max(0, c->row1 - c->row0 - c->give[1]) / per + 1 > kXrPeerTags) ok = false;
     }
     // agreement: every rank or none.  (Every rank's region was zeroed above, before its handle went out: no word of an earlier band or a raised
     // abort flag survives into the solves of this one.)

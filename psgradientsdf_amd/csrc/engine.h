@@ -144,8 +144,7 @@ struct SweepArgs {
     double* pcg_part; double* pcg_fs;   // fused PCG state (pcg.hip)
     int pcg_asm;              // persistent solve assembles the distance system itself (no k_assemble launch in front of it)
     unsigned pcg_epoch;       // serial number of this context's distance solve (k_cgp_solve: the tag of its exchanged values; the launch sites count it)
-    int pcg_pipe;             // unused, always 0 (it selected among persistent kernels that are gone); the slot stays: every kernel's argument layout depends on it
-    int pcg_xcd_local;        // persistent solve, a bit set despite its name: 2 = the sums of a pass are requested behind the last gather batch (PSGSDF_PCG_PREFETCH), << 3: the timing ablations; bit 0 unused
+    int pcg_ablate;           // persistent solve: the timing ablations of the development library (PSGSDF_PCG_ABLATE; 0 in production)
     int pcg_apply;            // ... and applies the distance update itself (no k_apply_dist behind it): 1 = when finished, 2 = only on Success
     double* pcg_gran; int pcg_gran_n;   // persistent solve: the tagged per-workgroup sums, zeroed by the assembly kernel when non-null
     const int* pcg_win;       // persistent solve, windowed instance (pcg.hip k_solve_windows): per workgroup {first row, length} of its three LDS window ranges; nullptr: off
@@ -173,8 +172,7 @@ struct SweepArgs {
 // word a fast rank wrote before this rank even started its solve -- can neither be mistaken for the current one nor be wiped.
 // Layout of a region, in doubles:
 constexpr int kXrMaxRanks = 32;      // rank-level sums: [2 buffers][8 planes][kXrMaxRanks] tagged granules (plane 7: |b|^2 with the sums of pass 0)
-constexpr int kXrPeerTags = 64;      // [2 sides][3 buffers][kXrPeerTags] words no kernel writes or reads any more (the halo values carry their own tags); the slots stay: the layout of a region is shared by every rank
-constexpr int kXrRankGran = 0, kXrPtag = 2 * 8 * kXrMaxRanks, kXrAbort = kXrPtag + 2 * 3 * kXrPeerTags, kXrDoubles = kXrAbort + 8;
+constexpr int kXrRankGran = 0, kXrAbort = 2 * 8 * kXrMaxRanks, kXrDoubles = kXrAbort + 8;
 // kXrAbort + 0: the persistent solve's abort flag (raised in every rank's region; cleared with the region at the next band).  kXrLate + 0 / 1 / 2: the
 // number of the last frame-row exchange / scalar fold / halo pull of THIS rank whose bounded wait for a peer expired (0: none) -- the NaN such an
 // exchange hands on says "something is wrong", these words say what (lateness signalled out of band, not through the payload alone)
@@ -186,7 +184,6 @@ struct XrArgs {
     float4* lo_rec[2]; float4* hi_rec[2];   // where this slab's boundary records go: first upper-halo row of the lower neighbour / first lower-halo row of the upper one (per record buffer)
     float4* lo_base[2];                     // row 0 of the lower neighbour's record planes (k_cgp_solve stores ONE double per row at the head of a plane: row index counted in doubles)
     int give_lo, give_hi;            // own rows the lower / upper neighbour holds as halo (the first give_lo / last give_hi own rows)
-    int wait_lo, wait_hi;            // workgroups of the lower / upper neighbour next to the cut (xr_setup bounds them by kXrPeerTags; no kernel reads them any more, the fields keep the layout)
     int need_lo, need_hi;            // halo rows this slab gathers from
     unsigned epoch;                  // solve counter of the context (the same on every rank), 14 bits: tags of the cross-rank words are (epoch << 2 | pass tag)
 };
@@ -252,7 +249,7 @@ void launch_cgf_init(const SweepArgs& a, double* fs, double* part, int G, hipStr
 void launch_cgf_pass(const SweepArgs& a, double* fs, double* part, int G, int rows, int k, int kmax, double* mb, hipStream_t s, int ablate = 0);
 void launch_cgf_sum(double* part, int G, int k, double* out, hipStream_t s);
 // the whole solve as one persistent kernel (pcg_solve.h: k_cgp_solve); gran = [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums (planes 0-2; plane 7 of
-// buffer 1: the prologue's flag), zeroed by the kernel in front (assembly kernel / distance sweep)
+// buffer 1: the prologue's flag, which nothing reads -- pcg_solve.h publish_prologue says why it is still written), zeroed by the kernel in front (assembly kernel / distance sweep)
 constexpr int kSolveGranPlanes = 8;
 constexpr int kSolveThreadsHost = 512, kSolveMaxBlocksHost = 256, kSolveMaxRowsHost = 4, kSolveMbSlots = 24;      // {iters, |r|^2, |b|^2, status} + stage timestamps of the timing hook
 int cgf_solve_max_blocks(int rows);      // resident workgroups per CU of the R-rows instance (occupancy query)

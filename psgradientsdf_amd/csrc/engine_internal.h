@@ -97,7 +97,6 @@ struct psgsdf_ctx {
     double* pcg_gran = nullptr;          // persistent solve: [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums
     unsigned pcg_solve_serial = 0;       // distance solves launched on this context (SweepArgs::pcg_epoch)
     int pcg_ablate = 0;                  // PSGSDF_PCG_ABLATE: timing ablations of the persistent solve, bits 1 and 4 (wrong results; tools only)
-    bool pcg_prefetch = true;            // PSGSDF_PCG_PREFETCH=0: pipelined solve: the sums of a pass are only fetched after its gathers (not behind the last gather batch)
     bool pcg_fuse_apply = true;          // PSGSDF_PCG_FUSE_APPLY=0: k_apply_dist behind it
     bool pcg_persist = true;             // PSGSDF_PCG_PERSIST=0: always the per-pass kernels
     bool pcg_window = true;              // PSGSDF_PCG_WINDOW=0: the single-rank pipelined solve gathers per thread instead of reading an LDS window (pcg_solve.h k_cgp_solve<.., WIN>)

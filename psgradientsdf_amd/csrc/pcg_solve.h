@@ -111,10 +111,6 @@ template <bool MR> struct SolveWg {
     // XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs; logical block lb gives XCD x the contiguous blocks [x G/8, (x+1) G/8)
     const int lb = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
     const int own_n = a.row1 - a.row0;
-    // The workgroups whose rows this one gathers from, in band order.  (No reader since the values validate themselves.  Kept: without these two lines the
-    // compiler orders the prologue of the gathering instances differently, and the kernels are to stay as measured: profiles/r08_notes.md)
-    const int wg_first = lb * rows_per_wg;      // (relative to row0)
-    const int nlo = max(0, (wg_first - a.b.reach) / rows_per_wg), nhi = min(G - 1, (wg_first + rows_per_wg - 1 + a.b.reach) / rows_per_wg);
     double* const xr_me = MR ? xr.region[xr.rank] : nullptr;
     const unsigned etag0 = MR ? (xr.epoch & kXrEpochMask) << 2 : 0u;      // cross-rank tags: (epoch << 2 | pass tag)
 
@@ -136,7 +132,9 @@ template <bool MR> struct SolveWg {
     __device__ __forceinline__ bool aborted() const { return __hip_atomic_load(fs + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0; }
     __device__ __forceinline__ bool aborted_by_rank() const { return aborted() || __hip_atomic_load(xr_me + kXrAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0; }
     // Prologue (thread 0, behind the barrier that follows the drain of the workgroup's first stores): 1 + the XCD id into plane 7 of buffer 1.
-    // (Nothing waits for this flag any more -- the exchanged values validate themselves -- but the store is part of the kernel as measured: kept.)
+    // Nothing waits for this flag or reads it.  It stays because the gathering instances measured 0.3-0.4 us per pass slower without it (7.2 against 6.8 us
+    // at the 256^3 band; the windowed instances do not care): the store lies outside the pass loop, what changes is the code the compiler makes of the
+    // loop (profiles/r09_notes.md section 5)
     __device__ __forceinline__ void publish_prologue() const {
         __hip_atomic_store(gran_plane(1, 7) + lb, (double)(1 + my_xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -310,7 +308,6 @@ static_assert(solve_col_segs_match(), "the window segment of a column is its z o
 template <int R, bool MR, bool WIN = false>
 __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, double* fs, double* gran, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, XrArgs xr) {
     __shared__ double red[8 * kSolveThreads / 64];
-    [[maybe_unused]] __shared__ int s_abort;      // (no reader: cleared in the prologue round only.  Kept: the store is part of the kernel as measured)
     // TWO workgroup barriers per pass instead of the five of a kernel that waits for its neighbours' tags (round 6: 7.05 -> 6.5 us per
     // pass).  What is left is one barrier per cross-wavefront sum: in front of stage C's reads of `red` and in front of stage E's reads of `red2`.  The sums
     // of C and E meet in buffers of their own, E's alternating by pass parity -- so neither the barrier between C's reads and E's writes nor the one behind
@@ -323,7 +320,6 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
     __shared__ double red3[MR ? 8 * kSolveThreads / 64 : 1];
     __shared__ int s_ab3[3];
 #define CGP_ABORT s_ab3[(k + 3) % 3]
-    [[maybe_unused]] __shared__ int s_foreign;      // (no reader: see s_abort)
     const Band& b = a.b;
     const SolveWg<MR> wg(a, xr, fs, gran, rows_per_wg);
     const int G = wg.G, tid = wg.tid, lb = wg.lb;
@@ -379,11 +375,11 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         const unsigned want = (unsigned)(k + 1) & 3u;      // tag of the sums published for pass k (k >= 0)
         const int pb = k & 1;                              // the buffer they were published in
         const double* gp = wg.gran_plane(pb, 0);
-        const int abl = (a.pcg_xcd_local >> 3) & 7;      // timing ablations (tools/pcg_variants.py; never set in production): 1 = every gather reads the row's own element, 4 = the 8 in-plane columns are not fetched
+        const int abl = a.pcg_ablate;      // timing ablations (tools/pcg_variants.py; never set in production): 1 = every gather reads the row's own element, 4 = the 8 in-plane columns are not fetched
         solve_keep_columns_packed<R>(cp);
         // ---- A: the neighbours' m_k (k = -1: their u_0) validate themselves: nothing to wait for.  Once per solve: the 'a wait gave up' words
         if (k < 0) {
-            if (tid == 0) { s_abort = 0; s_ab3[0] = 0; s_ab3[1] = 0; s_ab3[2] = 0; s_foreign = 0; }
+            if (tid == 0) { s_ab3[0] = 0; s_ab3[1] = 0; s_ab3[2] = 0; }
             __syncthreads();
         }
         SOLVE_STAMP(1);
@@ -395,7 +391,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = 0.0;
         auto prefetch_sums = [&] {
-            if (k >= 0 && (a.pcg_xcd_local & 2) && tid < G) {
+            if (k >= 0 && tid < G) {
 #pragma unroll
                 for (int q = 0; q < kCgpSums; ++q) v[q] = __hip_atomic_load(gp + (size_t)q * kSolveMaxBlocks + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -519,9 +515,9 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         bool stop = false;
         if (k >= 0) {
             // ---- C: the three sums for pass k of EVERY workgroup (published at the end of pass k - 1: normally all here by now)
-            auto poll3 = [&](const double* base, bool prefetched) {      // this thread's three granules at base[q * kSolveMaxBlocks] until they carry the pass's tag
+            auto poll3 = [&](const double* base) {      // this thread's three granules at base[q * kSolveMaxBlocks] until they carry the pass's tag (v holds what prefetch_sums asked for)
                 int spins = 0;
-                bool ok = prefetched && gran_tag_of(v[0]) == want && gran_tag_of(v[1]) == want && gran_tag_of(v[2]) == want;
+                bool ok = gran_tag_of(v[0]) == want && gran_tag_of(v[1]) == want && gran_tag_of(v[2]) == want;
                 while (!ok) {
                     if (spins) __builtin_amdgcn_s_sleep(1);
                     if (++spins > wg.kLocalSpins || wg.aborted()) { CGP_ABORT = 1; break; }
@@ -530,7 +526,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
                     for (int q = 0; q < kCgpSums; ++q) { v[q] = __hip_atomic_load(base + (size_t)q * kSolveMaxBlocks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && gran_tag_of(v[q]) == want; }
                 }
             };
-            if (tid < G) poll3(gp + tid, (a.pcg_xcd_local & 2) != 0);
+            if (tid < G) poll3(gp + tid);
             { const double v4[4] = {v[0], v[1], v[2], 0.0}; wave_sum4_store<kSolveThreads / 64>(wave_sum4(v4), red, tid >> 6); }      // (three sums: the four-value reduce-scatter, the same bits as wave_sum8's)
             __syncthreads();
             if (CGP_ABORT) { if (tid == 0) wg.raise_abort(); status = 2; break; }

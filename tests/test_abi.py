@@ -45,8 +45,8 @@ def test_dangerous_knobs_are_not_in_the_product_library(built):
         assert hasattr(devlib, n), n
     for k in (b"PSGSDF_FAULT_SOLVE", b"PSGSDF_FAULT_HALO", b"PSGSDF_PCG_ABLATE", b"PSGSDF_MBOX_CHECK"):
         assert prod.count(k) == 1 and dev.count(k) >= 1, k      # (one occurrence: the kDevKnobs name table behind "ignored_dev_only")
-    for k in (b"PSGSDF_PCG_PIPELINE", b"PSGSDF_PCG_FUSE_ASM", b"PSGSDF_PCG_TAGM", b"PSGSDF_PCG_XCD_LOCAL"):
-        assert k not in prod and k not in dev, k      # (retired with the persistent kernels they selected: no build knows them)
+    for k in (b"PSGSDF_PCG_PIPELINE", b"PSGSDF_PCG_FUSE_ASM", b"PSGSDF_PCG_TAGM", b"PSGSDF_PCG_XCD_LOCAL", b"PSGSDF_PCG_PREFETCH"):
+        assert k not in prod and k not in dev, k      # (retired with the persistent kernels and the slower paths they selected: no build knows them)
     assert os.path.getsize(capi.ENGINE_LIB_DEV) > 0
 
 

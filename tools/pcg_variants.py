@@ -1,5 +1,5 @@
 """per-pass time of the persistent distance solve under knob settings: (solve of 48 passes - solve of 16 passes) / 32, median and min over repetitions
-usage: python tools/pcg_variants.py "" "PSGSDF_PCG_PREFETCH=0" "PSGSDF_PCG_WINDOW=0" ...   (each argument: comma-separated KEY=VALUE list; "" = defaults)"""
+usage: python tools/pcg_variants.py "" "PSGSDF_PCG_WINDOW=0" "PSGSDF_PCG_FUSE_APPLY=0" ...   (each argument: comma-separated KEY=VALUE list; "" = defaults)"""
 import os, sys, json
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -28,7 +28,6 @@ VARIANTS = {
     "fold0": {"PSGSDF_FOLD_IN_NEXT": "0"},
     "poll0": {"PSGSDF_PCG_POLL": "0"},
     "persist0": {"PSGSDF_PCG_PERSIST": "0"},     # per-pass kernels: the CLASSIC recurrences (family "classic": rounding-level apart from the pipelined default)
-    "prefetch0": {"PSGSDF_PCG_PREFETCH": "0"},   # pipelined solve: sums requested after the last gather batch
     "fmsolve0": {"PSGSDF_FM_SOLVE": "0"},        # light / pose solves as kernels of their own
     "fmsolve2": {"PSGSDF_FM_SOLVE": "2"},        # ... only the LED light vector
     "xcdmap0": {"PSGSDF_XCD_MAP": "0"},          # physical workgroup ids (no XCD-contiguous mapping)
