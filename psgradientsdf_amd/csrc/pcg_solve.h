@@ -13,7 +13,7 @@ __device__ __forceinline__ float pcg_threshold(float rhsNorm2) { return fmaxf(FL
 //
 // A per-pass launch re-streams the 19 ELL coefficients and 9 index words of every row (152 B/row, 51 MB at the 256^3 band:
 // 9.7 of the pass's 14.3 us at the ~5.3 TB/s the L2-miss path sustains; profiles/r01_notes.md) although the matrix never
-// changes during a solve.  Here every thread assembles the coefficients of its R rows ONCE into LDS, keeps the column deltas
+// changes during a solve.  Here every thread assembles the coefficients of its R rows ONCE into LDS (five 16-byte words per row: SolveCoefs), keeps the column deltas
 // (9 packed words per row) and the row's own vectors in registers, and loops over the passes; per pass it obtains the 18
 // neighbour values of each row (L2-resident), updates its rows and meets the other workgroups at a device-wide all-gather of
 // the per-workgroup sums (k_cgp_solve below says which values and which sums):
@@ -34,8 +34,48 @@ __device__ __forceinline__ float pcg_threshold(float rhsNorm2) { return fmaxf(FL
 // ------------------------------------------------------------------------------------------
 constexpr int kSolveThreads = 512;            // one workgroup of 8 waves per CU: 2 waves per SIMD at <= 256 VGPRs (16 waves at 128 VGPRs spilled: 21 us per pass)
 constexpr int kSolveMaxBlocks = 256;          // one per CU
-constexpr int kSolveMaxRows = 4;              // rows per thread: R x 38 KB of coefficients in the CU's 160 KB of LDS
+constexpr int kSolveMaxRows = 4;              // rows per thread: R x 40 KB of coefficients in the CU's 160 KB of LDS (four rows: 152 KB, SolveCoefs below)
 typedef float v4f_t __attribute__((ext_vector_type(4)));
+// THE COEFFICIENTS OF A ROW SLOT IN LDS (round 10): the 19 floats of a thread's row are FIVE 16-byte words (q = 4 g + c is component c of word g; the
+// twentieth float is an exact 0 that no sum reads), word g of row slot u in a plane of its own: hs4[(u * 5 + g) * kSolveThreads + tid].  A row is
+// fetched with five ds_read_b128 -- lanes read consecutive 16-byte words: no bank conflict -- instead of nineteen ds_read_b32: 60 instead of 114
+// LDS-array cycles per wave and pass at R = 3, and ds_read_b128 reaches its rate at the solve's two waves per SIMD where ds_read_b32 needs about four.
+// The layout belongs to the thread (it writes its words once per solve and nobody else reads them); the readers multiply in the column order they
+// always had.  Four row slots of five words would be the CU's whole 160 KB: at R = 4 (no windowed instance, not tuned) only the four full words of a
+// slot are planes of words, hs4[(u * 4 + g) * kSolveThreads + tid], and the three floats of the fifth stay planes of floats behind them.
+constexpr int kCoefWords = (kNQ + 3) / 4;
+static_assert(kNQ == 19 && kCoefWords == 5, "a row's coefficients are five 16-byte words, the last one padded with one zero");
+template <int R> struct SolveCoefs {
+    static constexpr int kPlanes = R < kSolveMaxRows ? kCoefWords : kCoefWords - 1;      // planes of 16-byte words per row slot
+    static constexpr int kTail = kNQ - 4 * (kCoefWords - 1);                              // R = 4: floats of the fifth word, in planes of floats
+    static constexpr size_t kBytes = sizeof(v4f_t) * R * kPlanes * kSolveThreads + (kPlanes < kCoefWords ? sizeof(float) * R * kTail * kSolveThreads : 0);
+    static __device__ __forceinline__ v4f_t* words(int u, int tid) { return reinterpret_cast<v4f_t*>(psg_dyn_smem) + (size_t)u * kPlanes * kSolveThreads + tid; }
+    static __device__ __forceinline__ float* tail(int u, int tid) { return reinterpret_cast<float*>(reinterpret_cast<v4f_t*>(psg_dyn_smem) + (size_t)R * kPlanes * kSolveThreads) + (size_t)u * kTail * kSolveThreads + tid; }
+    static __device__ __forceinline__ void store(int u, int tid, const float (&hv)[4 * kCoefWords]) {
+        v4f_t* w = words(u, tid);
+#pragma unroll
+        for (int g = 0; g < kPlanes; ++g) { v4f_t t; t[0] = hv[4 * g]; t[1] = hv[4 * g + 1]; t[2] = hv[4 * g + 2]; t[3] = hv[4 * g + 3]; w[g * kSolveThreads] = t; }
+        if constexpr (kPlanes < kCoefWords) {
+#pragma unroll
+            for (int c = 0; c < kTail; ++c) tail(u, tid)[c * kSolveThreads] = hv[4 * kPlanes + c];
+        }
+    }
+    // words [G0, G1) of row slot u into hc
+    template <int G0, int G1> static __device__ __forceinline__ void load(int u, int tid, v4f_t (&hc)[kCoefWords]) {
+        const v4f_t* w = words(u, tid);
+#pragma unroll
+        for (int g = G0; g < G1; ++g) {
+            if (g < kPlanes) hc[g] = w[g * kSolveThreads];
+            else {
+                v4f_t t = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < kTail; ++c) t[c] = tail(u, tid)[c * kSolveThreads];
+                hc[g] = t;
+            }
+        }
+    }
+};
+__device__ __forceinline__ float solve_coef(const v4f_t (&hc)[kCoefWords], int q) { return hc[q >> 2][q & 3]; }
 __device__ __forceinline__ double gran_tag(double v, unsigned tag) { return __longlong_as_double((long long)(((unsigned long long)__double_as_longlong(v) & ~3ull) | tag)); }
 __device__ __forceinline__ unsigned gran_tag_of(double v) { return (unsigned)((unsigned long long)__double_as_longlong(v) & 3ull); }
 // cross-rank words (multi-rank solve): the tag is 16 bits wide, (epoch of the solve << 2 | pass tag) -- 2^-36 of the value, still far below the float the
@@ -173,16 +213,15 @@ template <bool MR> struct SolveWg {
 };
 
 // One row of a thread, assembled straight from the voxel blocks of the distance sweep (no k_assemble, no H in memory): the 19 coefficients (the diagonal
-// damped) into the thread's LDS column hs_slot[q * kSolveThreads], the Jacobi weight and the right-hand side returned
-__device__ __forceinline__ void solve_assemble_row(const SweepArgs& a, int row, float* hs_slot, float& inv, double& rhs) {
+// damped) into the words of the thread's row slot u (SolveCoefs), the Jacobi weight and the right-hand side returned
+template <int R> __device__ __forceinline__ void solve_assemble_row(const SweepArgs& a, int row, int u, int tid, float& inv, double& rhs) {
     double acc[kNQ];
     assemble_row_regs(a, row, acc, rhs);
+    float hv[4 * kCoefWords];
 #pragma unroll
-    for (int q = 0; q < kNQ; ++q) {
-        float hv = (float)acc[q];
-        if (q == 0 && a.damping != 0.0f) hv += a.damping * hv;
-        hs_slot[q * kSolveThreads] = hv;
-    }
+    for (int q = 0; q < 4 * kCoefWords; ++q) hv[q] = q < kNQ ? (float)acc[q] : 0.f;
+    if (a.damping != 0.0f) hv[0] += a.damping * hv[0];
+    SolveCoefs<R>::store(u, tid, hv);
     float dg = (float)acc[0];
     if (a.damping != 0.0f) dg += a.damping * dg;
     inv = dg != 0.f ? 1.0f / dg : 1.0f;
@@ -273,8 +312,9 @@ constexpr int kCgpMaxRows = 4;                // row slots per thread the pipeli
 #define PSG_CGP_DEPTH 2
 #endif
 #ifndef PSG_WIN_BATCH
-#define PSG_WIN_BATCH 9                       // windowed instance: LDS reads of the product in flight per thread
-#endif
+#define PSG_WIN_BATCH 9                       // windowed instance: window reads of the product in flight per thread, a divisor of 18 (round 10, with the row's five coefficient
+#endif                                        // words read up front: 6 and 9 time the same, 5.47 us per pass, at 234 / 241 VGPRs; 18 spills 20 bytes: profiles/r10_notes.md)
+static_assert((kNQ - 1) % PSG_WIN_BATCH == 0, "whole batches");
 #ifndef PSG_WIN_PREFETCH
 #define PSG_WIN_PREFETCH 2                    // windowed instance: the sums are requested 0 = right behind the window's loads, 1 = behind the window's stores, 2 = behind the products of the
 #endif                                        // thread's first row (measured, profiles/r07_notes.md: 6.68 / 5.90 / 5.89 us per pass, 2 930 / 3 003 / 3 044 it/s: the earlier, the more often re-polled)
@@ -295,7 +335,10 @@ __device__ __forceinline__ unsigned m_tag_of(double v) { return (unsigned)((unsi
 // back to back in the dynamic LDS behind the coefficients.  Stage B is then: B1 every FOREIGN slot (everything that is not an own row) is fetched once,
 // coalesced, with the same self-validating loads as the gathers -- all of a thread's loads issued before the first check, ONE trip past the L2 instead
 // of three -- and written into the window; the own rows never travel: stage D (and the prologue) writes the tagged value it publishes into the own
-// range as well; one barrier; B2 the products read the window, columns in the order of the gathers, the same multiply-adds: the same bits.
+// range as well; one barrier; B2 the products read the window, columns in the order of the gathers, the same multiply-adds: the same bits.  Per row: its
+// five coefficient words, then the 18 window values in batches of PSG_WIN_BATCH reads issued back to back with a scheduling barrier between a batch's reads
+// and its multiply-adds -- without it the compiler waits for every single read before it issues the next (one LDS round trip per column: stage B took
+// 3.1 us where it now takes 2.0, profiles/r10_notes.md).
 // ONE window suffices: foreign slots are rewritten in B1 of pass k + 1, behind stage E's barrier of pass k; own slots in stage D of pass k, behind stage
 // C's barrier, and every B2 read of the pass lies in front of that barrier.  The prologue round (k = -1) has no stage C: it gets a barrier of its own
 // between its B2 and its stage D, once per solve.
@@ -330,10 +373,10 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         if (MR && rel < xr.give_lo) store8_sys((double*)xr.lo_base[buf] + lo_row0 + rel, v);
         if (MR && rel >= wg.own_n - xr.give_hi) store8_sys((double*)xr.hi_rec[buf] + (rel - (wg.own_n - xr.give_hi)), v);
     };
-    float* hs = (float*)psg_dyn_smem;
+    using Coefs = SolveCoefs<R>;
     static_assert(!WIN || !MR, "the windowed instance exists for the single-rank kernel only");
     // WIN: the three ranges of this workgroup back to back behind the coefficients; band row i of segment s sits at win[wb<s> + i]
-    double* const win = (double*)(psg_dyn_smem + sizeof(float) * (size_t)R * kNQ * kSolveThreads);
+    double* const win = (double*)(psg_dyn_smem + Coefs::kBytes);
     int wb0 = 0, wb1 = 0, wb2 = 0, woff1 = 0, woff2 = 0, own_s = 0, own_cnt = 0, nforeign = 0;
     if constexpr (WIN) {
         const int* wt = a.pcg_win + 6 * lb;
@@ -347,6 +390,10 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
     }
     const unsigned mepoch = (1u + a.pcg_epoch % 3u) << 2;      // 1 .. 3, never the epoch of the solve before; 0 = memory no solve has written yet (the planes are zeroed when the band is built)
     unsigned cp[R][(kNQ - 1) / 2]; int row[R]; bool live[R];
+    // WIN: a row slot in which no lane of this wavefront has a row (the headline partition: the third slot of wavefronts 5-7) is skipped in stages B2 and
+    // D -- its products and updates were computed on a copy of the last own row and thrown away, its terms of the three sums are not added (as before:
+    // live[u] guards them).  Wave-uniform; a wavefront in which the band or the workgroup's rows end keeps the per-lane guards.
+    bool slot_on[R];
     double x[R], r[R], w[R], z[R], sv[R], pv[R]; float inv[R];      // every vector of the recurrences in double: see "precision" above
     fold_pending<kBlock>(a, red);      // the sums the distance sweep left pending
     // ---- once: assemble the rows of this thread (coefficients -> LDS), r_0 = b, u_0 = M^-1 b out for the neighbours
@@ -354,7 +401,8 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
     for (int u = 0; u < R; ++u) {
         row[u] = wg.own_row(u, live[u]);
         double rhs;
-        solve_assemble_row(a, row[u], hs + (size_t)u * kNQ * kSolveThreads + tid, inv[u], rhs);
+        slot_on[u] = !WIN || __builtin_amdgcn_ballot_w64(live[u]) != 0;
+        solve_assemble_row<R>(a, row[u], u, tid, inv[u], rhs);
         r[u] = live[u] ? (double)(float)rhs : 0.0;      // (b is the float vector the reference solves for)
         x[u] = 0.0; z[u] = 0.0; sv[u] = 0.0; pv[u] = 0.0; w[u] = 0.0;
         if (live[u]) {
@@ -435,20 +483,32 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         // itself, which lies in the in-plane range whatever the column's segment; a row slot without a row reads slot 0 and stores nothing
 #pragma unroll
         for (int u = 0; u < R; ++u) {
-            const float* hrow = hs + (size_t)u * kNQ * kSolveThreads + tid;
+          nres[u] = 0.0;
+          if (slot_on[u]) {
+            v4f_t hc[kCoefWords];
+            Coefs::template load<0, kCoefWords>(u, tid, hc);      // (the row's five words up front: they do not depend on the window)
             const double mine = (double)inv[u] * (k >= 0 ? w[u] : r[u]);      // (the row's own m: what it published)
-            double acc = (double)hrow[0] * mine;
+            double acc = (double)solve_coef(hc, 0) * mine;
             const int self = wb1 + row[u];
 #pragma unroll
-            for (int jj = 0; jj < kNQ - 1; ++jj) {
-                const int pk = (int)cp[u][jj >> 1];
-                const int d = (jj & 1) ? (pk >> 16) : ((pk << 16) >> 16);
-                int idx = solve_col_seg(jj) == 1 ? self + d : (d != 0 ? (solve_col_seg(jj) == 0 ? wb0 : wb2) + row[u] + d : self);
-                if (!live[u]) idx = 0;
-                acc += (double)hrow[(jj + 1) * kSolveThreads] * win[idx];
-                if (jj % PSG_WIN_BATCH == PSG_WIN_BATCH - 1) { asm volatile("" : "+v"(acc)); __builtin_amdgcn_sched_barrier(0); }      // (one batch of LDS reads at a time: all 18 R at once spill)
+            for (int j0 = 0; j0 < kNQ - 1; j0 += PSG_WIN_BATCH) {      // one batch: its window reads issued back to back, then its multiply-adds in column order
+                double wv[PSG_WIN_BATCH];
+#pragma unroll
+                for (int j = 0; j < PSG_WIN_BATCH; ++j) {
+                    const int jj = j0 + j;
+                    const int pk = (int)cp[u][jj >> 1];
+                    const int d = (jj & 1) ? (pk >> 16) : ((pk << 16) >> 16);
+                    int idx = solve_col_seg(jj) == 1 ? self + d : (d != 0 ? (solve_col_seg(jj) == 0 ? wb0 : wb2) + row[u] + d : self);
+                    if (!live[u]) idx = 0;
+                    wv[j] = win[idx];
+                }
+                __builtin_amdgcn_sched_barrier(0);      // (left to itself the compiler waits for every read before it issues the next: 18 LDS round trips per row)
+#pragma unroll
+                for (int j = 0; j < PSG_WIN_BATCH; ++j) acc += (double)solve_coef(hc, j0 + j + 1) * wv[j];
+                asm volatile("" : "+v"(acc)); __builtin_amdgcn_sched_barrier(0);      // (one batch of LDS reads at a time: all 18 R at once spill)
             }
             nres[u] = acc;
+          }
             if (PSG_WIN_PREFETCH == 2 && u == 0) { prefetch_sums(); __builtin_amdgcn_sched_barrier(0); }
         }
         if (k < 0) __syncthreads();      // (no stage C in the prologue round: its B2 reads of the own range end here, stage D rewrites it)
@@ -477,11 +537,12 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         for (int t = 0; t < kCgpDepth && t < 2 * R; ++t) issue(t);
         if (2 * R - 1 - kCgpDepth < 0) { __builtin_amdgcn_sched_barrier(0); prefetch_sums(); __builtin_amdgcn_sched_barrier(0); }
         double acc = 0;
+        v4f_t hc[kCoefWords];      // the row's coefficients: words 0-2 (columns 0-11) with its first batch, words 3-4 with its second
 #pragma unroll
         for (int t = 0; t < 2 * R; ++t) {
             const int u = t >> 1, j0 = (t & 1) * 9;
-            const float* hrow = hs + (size_t)u * kNQ * kSolveThreads + tid;
-            if (!(t & 1)) { const double mine = (double)inv[u] * (k >= 0 ? w[u] : r[u]); acc = (double)hrow[0] * mine; }      // (the row's own m: what it published)
+            if (!(t & 1)) { Coefs::template load<0, 3>(u, tid, hc); const double mine = (double)inv[u] * (k >= 0 ? w[u] : r[u]); acc = (double)solve_coef(hc, 0) * mine; }      // (the row's own m: what it published)
+            else Coefs::template load<3, kCoefWords>(u, tid, hc);
             {      // a value that is not this pass's yet: ask again (the producer is at most one hand-off behind)
                 const unsigned wantm = mepoch | want;
 #pragma unroll
@@ -500,7 +561,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
                 }
             }
 #pragma unroll
-            for (int j = 0; j < 9; ++j) acc += (double)hrow[(j0 + j + 1) * kSolveThreads] * ob[t % kCgpDepth][j];
+            for (int j = 0; j < 9; ++j) acc += (double)solve_coef(hc, j0 + j + 1) * ob[t % kCgpDepth][j];
             asm volatile("" : "+v"(acc));
             if (t & 1) nres[u] = acc;
             __builtin_amdgcn_sched_barrier(0);
@@ -558,6 +619,7 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
         for (int q = 0; q < 8; ++q) s[q] = 0.0;
 #pragma unroll
         for (int u = 0; u < R; ++u) {
+            if (!slot_on[u]) continue;
             double ui = (double)inv[u] * r[u];
             if (k < 0) w[u] = nres[u];
             else {
@@ -613,7 +675,6 @@ __global__ void __launch_bounds__(kSolveThreads, 2) k_cgp_solve(SweepArgs a, dou
 // ---- host side of the persistent solve: every instance takes the same arguments and the same launch shape
 using SolveKernel = void (*)(SweepArgs, double*, double*, int, int, double*, unsigned long long, int, XrArgs);
 static_assert(kCgpMaxRows == kSolveMaxRows && kSolveMaxRows == 4, "solve_with_rows lists the row counts");
-static size_t solve_lds(int rows) { return sizeof(float) * (size_t)rows * kNQ * kSolveThreads; }
 // > 64 KB of dynamic LDS has to be asked for; returns the resident workgroups per CU (0: the instance cannot run)
 static int solve_prepare(SolveKernel kern, size_t lds) {
     int n = 0;
@@ -629,6 +690,7 @@ template <class F> static auto solve_with_rows(int rows, F&& f) {
         default: return f(std::integral_constant<int, 4>{});
     }
 }
+static size_t solve_lds(int rows) { return solve_with_rows(rows, [](auto rc) -> size_t { return SolveCoefs<decltype(rc)::value>::kBytes; }); }      // the coefficients of `rows` row slots
 // the windowed instance of the launch (pcg_window.hip): false = this band's windows do not fit (or the instance cannot be resident): nothing was launched
 bool launch_cgp_solve_window(const SweepArgs& a, double* fs, double* gran, int G, int rows_per_wg, int kmax, double* mb, unsigned long long mb_key, int force_passes, hipStream_t s);
 
