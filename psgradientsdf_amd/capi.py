@@ -99,6 +99,25 @@ class BakeAo(C.Structure):      # psgsdf_bake_ao
                 ("n_dirs", C.c_int32), ("reserved", C.c_int32), ("counts", AoCounts)]
 
 
+class CompareParams(C.Structure):      # psgsdf_compare_params (include/psgsdf_compare.h)
+    _fields_ = [("max_dist", C.c_double), ("tau", C.c_double), ("grid_cell", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class CompareSide(C.Structure):      # psgsdf_compare_side
+    _fields_ = [("n", C.c_int64), ("n_valid", C.c_int64), ("n_matched", C.c_int64), ("n_within_tau", C.c_int64),
+                ("sum_d", C.c_int64), ("sum_d2", C.c_int64), ("sum_signed", C.c_int64), ("hist", C.c_int64 * 16),
+                ("max", C.c_double), ("mean", C.c_double), ("rms", C.c_double), ("mean_signed", C.c_double)]
+
+
+class Compare(C.Structure):      # psgsdf_compare
+    _fields_ = [("xyz", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("rgb", C.POINTER(C.c_uint8)), ("faces", C.POINTER(C.c_int32)),
+                ("n_vertices", C.c_int64), ("n_faces", C.c_int64),
+                ("vertex_dist", C.POINTER(C.c_float)), ("vertex_nearest", C.POINTER(C.c_int32)), ("vertex_side", C.POINTER(C.c_int8)),
+                ("ref_dist", C.POINTER(C.c_float)), ("ref_nearest", C.POINTER(C.c_int32)), ("ref_side", C.POINTER(C.c_int8)),
+                ("to_reference", CompareSide), ("to_reconstruction", CompareSide),
+                ("precision", C.c_double), ("recall", C.c_double), ("fscore", C.c_double)]
+
+
 # psgsdf_mesh_component (include/psgsdf_mesh.h), 88 bytes
 MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_faces", "<i8"), ("n_edges", "<i8"), ("n_boundary_edges", "<i8"),
                                  ("n_nonmanifold_edges", "<i8"), ("area", "<f8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("kept", "<i4"), ("reserved", "<i4")])
@@ -527,6 +546,35 @@ class Api:
         out["mask"] = np.ctypeslib.as_array(b.mask, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint64)
         out["dirs"] = np.ctypeslib.as_array(b.dirs, shape=(b.n_dirs, 3)).copy()
         out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in AoCounts._fields_}
+        return out
+
+    # -- comparison with a reference mesh or cloud (include/psgsdf_compare.h)
+    def compare_reference(self, ref_xyz, ref_faces=None, max_dist=None, tau=None, grid_cell=0.0, min_faces=0, min_area=0.0, keep_largest=0):
+        """Two-sided nearest distances between the welded mesh (with a filter: its kept components, as extract_mesh_components) and a reference
+        (psgsdf_compare_reference): ref_xyz [n, 3] float32 in the mesh's units, ref_faces [f, 3] int32 or None for a cloud.  A pair farther apart
+        than max_dist (None: 8 voxels) is no match; tau (None: 1 voxel) is the threshold of precision and recall; grid_cell sizes the search grid
+        (0: the engine's choice; no result depends on it).  dict of numpy copies: the compared mesh xyz, normals, rgb, faces; vertex_dist [V] float32
+        (inf: unmatched), vertex_nearest [V] int32 (a reference face or point, -1: none), vertex_side [V] int8; ref_dist, ref_nearest (a face of the
+        mesh), ref_side [n] the other way; to_reference and to_reconstruction, dicts of psgsdf_compare_side's fields (hist: [16] int64); precision,
+        recall, fscore.  Single contexts only."""
+        ref_xyz = np.ascontiguousarray(ref_xyz, np.float32).reshape(-1, 3)
+        faces = None if ref_faces is None else np.ascontiguousarray(ref_faces, np.int32).reshape(-1, 3)
+        vs = float(np.float32(self.info().voxel_size))
+        p = CompareParams(float(8 * vs if max_dist is None else max_dist), float(vs if tau is None else tau), float(grid_cell), (C.c_int32 * 2)(0, 0))
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        r = Compare()
+        self._check(self._fn("compare_reference")(self.ctx, C.byref(flt) if flt is not None else None, ref_xyz.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(len(ref_xyz)),
+                                                  faces.ctypes.data_as(C.POINTER(C.c_int32)) if faces is not None and len(faces) else None,
+                                                  C.c_int64(0 if faces is None else len(faces)), C.byref(p), C.byref(r)), "compare_reference")
+        V, F, n = r.n_vertices, r.n_faces, len(ref_xyz)
+        arr = lambda ptr, shape, dt: np.ctypeslib.as_array(ptr, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
+        out = dict(xyz=arr(r.xyz, (V, 3), np.float32), normals=arr(r.normals, (V, 3), np.float32), rgb=arr(r.rgb, (V, 3), np.uint8), faces=arr(r.faces, (F, 3), np.int32),
+                   vertex_dist=arr(r.vertex_dist, (V,), np.float32), vertex_nearest=arr(r.vertex_nearest, (V,), np.int32), vertex_side=arr(r.vertex_side, (V,), np.int8),
+                   ref_dist=arr(r.ref_dist, (n,), np.float32), ref_nearest=arr(r.ref_nearest, (n,), np.int32), ref_side=arr(r.ref_side, (n,), np.int8),
+                   precision=float(r.precision), recall=float(r.recall), fscore=float(r.fscore))
+        for name in ("to_reference", "to_reconstruction"):
+            s = getattr(r, name)
+            out[name] = {k: (np.array(s.hist, np.int64) if k == "hist" else getattr(s, k)) for k, _ in CompareSide._fields_}
         return out
 
     # -- the photometric fit resolved over the surface (include/psgsdf_fit.h)

@@ -37,7 +37,7 @@ static const char* const kKnobs[] = {
     "PSGSDF_PCG_FUSE_APPLY", "PSGSDF_PCG_WINDOW", "PSGSDF_PCG_SOLVE_ROWS", "PSGSDF_PCG_COL16", "PSGSDF_PCG_ROWS", "PSGSDF_PCG_BLOCKS",
     "PSGSDF_FM_SOLVE", "PSGSDF_FRAME_SOLVE", "PSGSDF_FM_ROWS", "PSGSDF_IMG_COMPACT", "PSGSDF_XCD_MAP", "PSGSDF_XCD_STRIPE",
     "PSGSDF_XR", "PSGSDF_XF", "PSGSDF_XS", "PSGSDF_XH", "PSGSDF_XR_MEM", "PSGSDF_XWAIT_LOG2", "PSGSDF_SPECULATE_MR", "PSGSDF_CU_MASK",
-    "PSGSDF_WAIT_TIMEOUT_S", "PSGSDF_DESTROY_TIMEOUT_S", "PSGSDF_SOLVE_DUMP", "PSGSDF_AO_CUT"};
+    "PSGSDF_WAIT_TIMEOUT_S", "PSGSDF_DESTROY_TIMEOUT_S", "PSGSDF_SOLVE_DUMP", "PSGSDF_AO_CUT", "PSGSDF_COMPARE_CHUNK"};
 static const char* const kDevKnobs[] = {"PSGSDF_PCG_ABLATE", "PSGSDF_FAULT_SOLVE", "PSGSDF_FAULT_HALO", "PSGSDF_MBOX_CHECK"};
 const char* psgsdf_last_error(const psgsdf_ctx* c) { return c ? c->err : "null context"; }
 
@@ -51,6 +51,7 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     c->device = device;
     if (const char* e = getenv("PSGSDF_PCG_POLL")) c->pcg_poll = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_AO_CUT")) c->ao_cut = atoi(e) != 0;
+    if (const char* e = getenv("PSGSDF_COMPARE_CHUNK")) c->compare_chunk = std::min(std::max(atoll(e), 1ll), 1ll << 24);
     if (const char* e = getenv("PSGSDF_SPECULATE")) c->speculate = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_FOLD_IN_NEXT")) c->fold_in_next = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_FUSE_ALBEDO")) c->fuse_albedo = atoi(e) != 0;

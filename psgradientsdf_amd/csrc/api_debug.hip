@@ -280,11 +280,11 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
     char buf[1024];
     snprintf(buf, sizeof(buf), "\"pcg_poll\": %d, \"speculate\": %d, \"speculate_mr\": %d, \"fold_in_next\": %d, \"fuse_albedo\": %d, \"fuse_pcg_init\": %d, \"pcg_persist\": %d, "
              "\"pcg_fuse_apply\": %d, \"fm_solve\": %d, \"fm_solve_led\": %d, \"frame_solve\": \"%s\", \"img_compact\": %d, \"xcd_map\": %d, "
-             "\"xr\": %d, \"xf\": %d, \"xs\": %d, \"xh\": %d, \"xr_mem_kind\": %d, \"xwait_log2\": %d, \"cu_mask\": [%d, %d], \"mbox_check\": %d, \"pcg_ablate\": %d, \"fault_solve\": %d, \"fault_halo\": %lld, \"ao_cut\": %d",
+             "\"xr\": %d, \"xf\": %d, \"xs\": %d, \"xh\": %d, \"xr_mem_kind\": %d, \"xwait_log2\": %d, \"cu_mask\": [%d, %d], \"mbox_check\": %d, \"pcg_ablate\": %d, \"fault_solve\": %d, \"fault_halo\": %lld, \"ao_cut\": %d, \"compare_chunk\": %lld",
              (int)c->pcg_poll, (int)c->speculate, (int)c->speculate_mr, (int)c->fold_in_next, (int)c->fuse_albedo, (int)c->fuse_pcg_init, (int)c->pcg_persist,
              (int)c->pcg_fuse_apply, (int)c->fm_solve, (int)c->fm_solve_led, c->frame_solve == 1 ? "eigen" : "ldlt", (int)c->img_compact, c->xcd_map,
              (int)c->xr_enable, (int)c->xf_enable, (int)c->xs_enable, (int)c->xh_enable, c->xr_mem_kind, (int)lround(log2((double)c->xwait_spins)), c->cu_mask_lo, c->cu_mask_hi,
-             (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut);
+             (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut, c->compare_chunk);
     o += buf;
     {   // the LDS window of the single-rank persistent solve: the knob, what this band's partition needs and may hold, and what the last solve ran.
         // "fallback" names why a context with the knob on gathers per thread all the same -- never silently
@@ -298,6 +298,9 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
         o += buf;
     }
     o += "}";
+    // the search of the last psgsdf_compare_reference: queries and candidate pairs evaluated, [to_reference, to_reconstruction] (tools/time_compare.py)
+    snprintf(buf, sizeof(buf), ", \"last_compare\": {\"queries\": [%lld, %lld], \"pairs\": [%lld, %lld]}", c->cmp_queries[0], c->cmp_queries[1], c->cmp_pairs[0], c->cmp_pairs[1]);
+    o += buf;
     if (c->n_ranks > 1) {      // the hand-off probe as THIS rank saw it, per memory kind tried (comm.hip xr_probe): a first multi-GPU run reads its pairs here
         snprintf(buf, sizeof(buf), ", \"xr_probe\": {\"rank\": %d, \"n_ranks\": %d, \"kind_chosen\": %d, \"stale_mappings\": %lld, \"fine_grained\": {\"tried\": %lld, \"stale_records_from_lower\": %lld, \"expired_waits_lower\": %lld, \"expired_waits_upper\": %lld}, "
                  "\"uncached\": {\"tried\": %lld, \"stale_records_from_lower\": %lld, \"expired_waits_lower\": %lld, \"expired_waits_upper\": %lld}}",

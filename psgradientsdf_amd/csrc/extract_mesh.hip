@@ -3,7 +3,8 @@
 // clustering (mesh_lod.hip; "Level of detail"); and the C ABI of include/psgsdf_fit.h: the photometric fit per band row and per vertex of the welded
 // mesh (fit.hip; "Photometric fit per voxel and vertex"); and the C ABI of include/psgsdf_bake.h: detail maps of the level-of-detail mesh (bake.hip;
 // "Baked detail maps"); and the C ABI of include/psgsdf_occlusion.h: ambient occlusion at the caller's points and as a map of the bake
-// (occlusion.hip; "Ambient occlusion").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
+// (occlusion.hip; "Ambient occlusion"); and the C ABI of include/psgsdf_compare.h: distances to a reference mesh or cloud (compare.hip;
+// "Comparison with a reference").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
 // welded mesh -> vertex fit -- that hand each other device arrays whose kernels may still be in flight.  The CALL owns all device memory of its
 // stages in one DevMem, which waits for the stream and frees when the call returns, whichever way it returns: a stage allocates from it and never frees.
 // The frame arithmetic (extract_internal.h crop_frame) runs on the host and its results are compared bit for bit: no FMA contraction here either.
@@ -13,9 +14,11 @@
 #include "../../include/psgsdf_fit.h"
 #include "../../include/psgsdf_bake.h"
 #include "../../include/psgsdf_occlusion.h"
+#include "../../include/psgsdf_compare.h"
 #include "mesh_lod.h"
 #include "bake.h"
 #include "occlusion.h"
+#include "compare.h"
 
 using namespace psge;
 
@@ -545,5 +548,162 @@ extern "C" int psgsdf_bake_lod_ao(psgsdf_ctx* c, const psgsdf_mesh_filter* filte
         if (int rc = ao_run(c, mem, me, *params, D, a, true, XO_BAKE_AO_MASK, XO_BAKE_AO_OCCLUSION, &out->mask, &out->occlusion, &out->counts)) { *out = psgsdf_bake_ao{}; return rc; }
     }
     out->dirs = D;
+    return PSGSDF_OK;
+}
+
+// ---- comparison with a reference mesh or cloud (include/psgsdf_compare.h; kernels: compare.hip): the welded mesh (or its kept components) stays on
+// the device, the reference is uploaded once, and each direction is a grid build over its targets, the search, and the integer reductions.
+namespace {
+struct CmpBox { double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}; bool any = false; };
+// the bounding box of the finite points
+CmpBox cmp_bbox(const float* xyz, size_t n) {
+    CmpBox b;
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = xyz + 3 * i;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;
+        for (int k = 0; k < 3; ++k) { b.lo[k] = std::min(b.lo[k], (double)p[k]); b.hi[k] = std::max(b.hi[k], (double)p[k]); }
+        b.any = true;
+    }
+    return b;
+}
+struct CmpOut { XoSlot s_dist, s_nearest, s_side; const float** dist; const int32_t** nearest; const int8_t** side; };
+// one direction: a.t_*, a.nt, a.q_xyz, a.nq and the parameters are set; the grid over the box [lo, hi] (none if !box), the search, the
+// statistics; the per-query arrays in their pinned slots (the stream has been waited for)
+int compare_direction(psgsdf_ctx* c, DevMem& mem, const char* me, psg::CompareArgs a, const CmpBox& box, double cell, int dir, const CmpOut& o, psgsdf_compare_side* S) {
+    *S = psgsdf_compare_side{};
+    S->n = a.nq;
+    c->cmp_queries[dir] = a.nq; c->cmp_pairs[dir] = 0;
+    if (a.nq == 0) return PSGSDF_OK;
+    const size_t nq = (size_t)a.nq;
+    if (!mem.get(&a.d, nq) || !mem.get(&a.dist, nq) || !mem.get(&a.nearest, nq) || !mem.get(&a.side, nq) || !mem.get(&a.pairs, nq) || !mem.get(&a.stats, (size_t)psg::kCmpStats)
+        || !mem.get(&a.total, 1)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld queries)", me, a.nq);
+    if (hipMemsetAsync(a.stats, 0, sizeof(unsigned long long) * psg::kCmpStats, c->stream) != hipSuccess || hipMemsetAsync(a.total, 0, sizeof(unsigned long long), c->stream) != hipSuccess)
+        return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
+    psg::CompareGrid& g = a.g;
+    g = psg::CompareGrid{};
+    if (a.nt > 0 && box.any) {
+        // the cells: edge `cell`, doubled until the grid fits kCompareMaxCells (acceleration only: no result depends on it)
+        // and the lower corner snapped down to a whole number of cells, so that the walls are the multiples of the edge
+        double h = cell, nd[3], lo[3];
+        for (;;) {
+            double cells = 1.0;
+            for (int k = 0; k < 3; ++k) { lo[k] = floor(box.lo[k] / h) * h; nd[k] = std::max(1.0, ceil((box.hi[k] - lo[k]) / h)); cells *= nd[k]; }
+            if (cells <= (double)psg::kCompareMaxCells) break;
+            h *= 2.0;
+        }
+        g.h = h; g.cells = 1;
+        for (int k = 0; k < 3; ++k) { g.lo[k] = lo[k]; g.n[k] = (int)nd[k]; g.cells *= g.n[k]; }
+        int* sums = nullptr;
+        if (!mem.get(&g.start, (size_t)g.cells + 1) || !mem.get(&g.cursor, (size_t)g.cells) || !mem.get(&sums, (size_t)((g.cells + 1 + psg::kTile - 1) / psg::kTile + 1)))
+            return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld grid cells)", me, g.cells);
+        if (hipMemsetAsync(g.start, 0, sizeof(int) * ((size_t)g.cells + 1), c->stream) != hipSuccess || hipMemsetAsync(g.cursor, 0, sizeof(int) * (size_t)g.cells, c->stream) != hipSuccess)
+            return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
+        hipError_t e = hipSuccess;
+        unsigned long long total = 0;
+        timed(c, "compare_total", [&] { e = psg::launch_compare_total(a, c->stream); });
+        if (e != hipSuccess || hipMemcpyAsync(&total, a.total, sizeof(total), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail(c, PSGSDF_ERR_DEVICE, "%s: the grid's size", me);
+        if (total > (unsigned long long)INT32_MAX)
+            return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: the search grid would need %llu entries for %d targets (cells of %g): tessellate it", me, total, a.nt, h);
+        timed(c, "compare_count", [&] { e = psg::launch_compare_count(a, c->stream); });
+        if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
+        int tot = 0;
+        if (int rc = scan_counts(c, g.start, g.cells + 1, sums, &tot)) return rc;      // counts -> the cells' first entries; start[cells] = the total
+        if ((unsigned long long)tot != total) return fail(c, PSGSDF_ERR_DEVICE, "%s: the grid's counts (%d) and its total (%llu) differ", me, tot, total);
+        if (!mem.get(&g.entries, (size_t)tot)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d grid entries)", me, tot);
+        timed(c, "compare_fill", [&] { e = psg::launch_compare_fill(a, c->stream); });
+        if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
+    }
+    hipError_t e = hipSuccess;
+    timed(c, dir ? "compare_query_rec" : "compare_query_ref", [&] { e = psg::launch_compare_query(a, c->compare_chunk, c->stream); });
+    if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld queries: %s", me, a.nq, hipGetErrorString(e));
+    timed(c, "compare_stats", [&] { e = psg::launch_compare_stats(a, c->stream); });
+    if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
+    unsigned long long st[psg::kCmpStats] = {};
+    if (hipMemcpyAsync(st, a.stats, sizeof(st), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the statistics", me);
+    if (int rc = download(c, me, {{o.s_dist, a.dist, sizeof(float) * nq, o.dist}, {o.s_nearest, a.nearest, sizeof(int) * nq, o.nearest}, {o.s_side, a.side, nq, o.side}})) return rc;
+    S->n_valid = (int64_t)st[psg::CS_VALID]; S->n_matched = (int64_t)st[psg::CS_MATCHED]; S->n_within_tau = (int64_t)st[psg::CS_TAU];
+    S->sum_d = (int64_t)st[psg::CS_SUM_D]; S->sum_d2 = (int64_t)st[psg::CS_SUM_D2]; S->sum_signed = (int64_t)st[psg::CS_SIGNED];
+    for (int b = 0; b < 16; ++b) S->hist[b] = (int64_t)st[psg::CS_HIST + b];
+    memcpy(&S->max, &st[psg::CS_MAX], sizeof(double));
+    if (S->n_matched > 0) {
+        const double m = (double)S->n_matched, unit = 1048576.0;
+        S->mean = a.vs * ((double)S->sum_d / unit) / m;
+        S->rms = a.vs * sqrt(((double)S->sum_d2 / unit) / m);
+        S->mean_signed = a.vs * ((double)S->sum_signed / unit) / m;
+    }
+    c->cmp_pairs[dir] = (long long)st[psg::CS_PAIRS];
+    return PSGSDF_OK;
+}
+}  // namespace
+
+extern "C" int psgsdf_compare_reference(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, const float* ref_xyz, int64_t n_ref, const int32_t* ref_faces, int64_t n_ref_faces,
+                                        const psgsdf_compare_params* params, psgsdf_compare* out) {
+    const char* me = "compare_reference";
+    if (!params || !out || (n_ref > 0 && !ref_xyz)) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    // (before anything collective and before any device work: no rank waits for another)
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): a slab holds only its own share of the mesh", me, c->rank, c->n_ranks);
+    if (n_ref < 0 || n_ref > (int64_t)INT32_MAX || n_ref_faces < 0 || (n_ref_faces > 0 && !ref_faces))
+        return fail(c, PSGSDF_ERR_ARG, "%s: %lld reference points, %lld faces%s", me, (long long)n_ref, (long long)n_ref_faces, n_ref_faces > 0 && !ref_faces ? " (null)" : "");
+    const psgsdf_compare_params& P = *params;
+    if (!(P.max_dist > 0.0) || std::isinf(P.max_dist) || !(P.tau > 0.0) || !(P.tau <= P.max_dist) || !(P.grid_cell >= 0.0) || std::isinf(P.grid_cell) || P.reserved[0] != 0 || P.reserved[1] != 0)
+        return fail(c, PSGSDF_ERR_ARG, "%s: max_dist %g, tau %g, grid_cell %g, reserved %d %d (finite, 0 < tau <= max_dist, grid_cell >= 0, reserved 0)", me, P.max_dist, P.tau, P.grid_cell, P.reserved[0], P.reserved[1]);
+    if (c && c->have_volume && P.max_dist > 64.0 * (double)c->grid.vs) return fail(c, PSGSDF_ERR_ARG, "%s: max_dist %g is more than 64 voxels of %g", me, P.max_dist, (double)c->grid.vs);
+    for (int64_t i = 0; i < 3 * n_ref_faces; ++i)
+        if (ref_faces[i] < 0 || (int64_t)ref_faces[i] >= n_ref) return fail(c, PSGSDF_ERR_ARG, "%s: face %lld has the index %d (%lld reference points)", me, (long long)(i / 3), ref_faces[i], (long long)n_ref);
+    if (filter && bad_filter(*filter)) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
+    if (n_ref_faces > (int64_t)INT32_MAX) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: %lld reference faces", me, (long long)n_ref_faces);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *out = psgsdf_compare{};
+    auto bail = [&](int rc) { *out = psgsdf_compare{}; return rc; };
+    const double vs = (double)c->grid.vs;
+    DevMem mem(c);
+    // the compared mesh, on the device and in the slots of the call it mirrors
+    MeshView mv;
+    if (!filter) {
+        WMeshDev m;
+        if (int rc = wmesh_device(c, mem, &m)) return bail(rc);
+        mv = m;
+    } else {
+        MCompDev d;
+        if (int rc = mcomp_device(c, mem, me, *filter, &d)) return bail(rc);
+        if (d.nc != 0 && d.nv > 0 && d.nf > 0) mv = d;      // (else: an empty mesh, or a filter that drops everything)
+    }
+    const size_t nv = (size_t)mv.nv, nf = (size_t)mv.nf;
+    psgsdf_compare r{};
+    if (int rc = download(c, me, {{XO_IMESH_XYZ, mv.xyz, sizeof(float) * 3 * nv, &r.xyz}, {XO_IMESH_NORMALS, mv.nrm, sizeof(float) * 3 * nv, &r.normals}, {XO_IMESH_RGB, mv.rgb, 3 * nv, &r.rgb},
+                                  {XO_IMESH_FACES, mv.faces, sizeof(int) * 3 * nf, &r.faces}})) return bail(rc);
+    r.n_vertices = (int64_t)nv; r.n_faces = (int64_t)nf;
+    // the reference, uploaded once
+    float* d_rxyz = nullptr; int* d_rfaces = nullptr;
+    if ((n_ref > 0 && !mem.get(&d_rxyz, 3 * (size_t)n_ref)) || (n_ref_faces > 0 && !mem.get(&d_rfaces, 3 * (size_t)n_ref_faces)))
+        return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld reference points, %lld faces)", me, (long long)n_ref, (long long)n_ref_faces));
+    if ((n_ref > 0 && hipMemcpyAsync(d_rxyz, ref_xyz, sizeof(float) * 3 * (size_t)n_ref, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        || (n_ref_faces > 0 && hipMemcpyAsync(d_rfaces, ref_faces, sizeof(int) * 3 * (size_t)n_ref_faces, hipMemcpyHostToDevice, c->stream) != hipSuccess))
+        return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: upload", me));
+    // one box for both grids: a matching pair has its query in the queries' box and its closest point within max_dist of it and in the targets'
+    // box, so both lie in the intersection of the two boxes inflated by max_dist (taken a little larger: rounding never drops a pair at the rim)
+    const double cell = P.grid_cell > 0.0 ? P.grid_cell : 2.0 * vs;
+    const CmpBox bm = cmp_bbox(r.xyz, nv), br = cmp_bbox(ref_xyz, (size_t)n_ref);
+    CmpBox box; box.any = bm.any && br.any;
+    const double grow = P.max_dist * (1.0 + 1e-6) + 1e-6 * cell;
+    for (int k = 0; k < 3 && box.any; ++k) {
+        box.lo[k] = std::max(bm.lo[k], br.lo[k]) - grow; box.hi[k] = std::min(bm.hi[k], br.hi[k]) + grow;
+        if (!(box.lo[k] <= box.hi[k])) box.any = false;      // the two are farther apart than 2 max_dist: nothing matches
+    }
+    psg::CompareArgs a{};
+    a.max_dist = P.max_dist; a.tau = P.tau; a.vs = vs;
+    // the mesh's vertices against the reference
+    a.q_xyz = mv.xyz; a.nq = (long long)nv;
+    a.t_xyz = d_rxyz; a.t_faces = d_rfaces; a.nt = (int)(n_ref_faces > 0 ? n_ref_faces : n_ref);
+    if (int rc = compare_direction(c, mem, me, a, box, cell, 0, CmpOut{XO_CMP_VDIST, XO_CMP_VNEAREST, XO_CMP_VSIDE, &r.vertex_dist, &r.vertex_nearest, &r.vertex_side}, &r.to_reference)) return bail(rc);
+    // the reference's points against the mesh's faces
+    a.q_xyz = d_rxyz; a.nq = (long long)n_ref;
+    a.t_xyz = mv.xyz; a.t_faces = mv.faces; a.nt = (int)nf;
+    if (int rc = compare_direction(c, mem, me, a, box, cell, 1, CmpOut{XO_CMP_RDIST, XO_CMP_RNEAREST, XO_CMP_RSIDE, &r.ref_dist, &r.ref_nearest, &r.ref_side}, &r.to_reconstruction)) return bail(rc);
+    if (r.to_reference.n_valid > 0) r.precision = (double)r.to_reference.n_within_tau / (double)r.to_reference.n_valid;
+    if (r.to_reconstruction.n_valid > 0) r.recall = (double)r.to_reconstruction.n_within_tau / (double)r.to_reconstruction.n_valid;
+    if (r.precision + r.recall > 0.0) r.fscore = 2.0 * r.precision * r.recall / (r.precision + r.recall);
+    *out = r;
     return PSGSDF_OK;
 }

@@ -30,6 +30,7 @@
 #include <fstream>
 #include <iostream>
 #include <memory>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -39,6 +40,7 @@
 #include "../../include/psgsdf_fit.h"
 #include "../../include/psgsdf_bake.h"
 #include "../../include/psgsdf_occlusion.h"
+#include "../../include/psgsdf_compare.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 #include "obj_writer.hpp"
@@ -114,6 +116,12 @@ inline int& mesh_bake_ao_dirs() { static int v = 0; return v; }
 // voxelPS --mesh-fit: next to every <name>_mesh.ply a <name>_mesh_fit.ply, the welded mesh with the photometric fit of every vertex (psgsdf_extract_mesh_fit): how many
 // keyframes saw it, the rms residual and the mean robust loss; single process only
 inline bool& mesh_fit() { static bool v = false; return v; }
+// voxelPS --compare-ply FILE [--compare-tau T] [--compare-max D]: next to every <name>_mesh.ply a <name>_compare.txt (both directions' counts, mean / rms /
+// max / signed mean, histogram, precision / recall / F) and a <name>_mesh_compare.ply (the welded mesh -- the filtered one, if a filter flag is given --
+// with every vertex's distance to the reference and the side it lies on): psgsdf_compare_reference against the mesh or cloud read from FILE, whose
+// coordinates are those of <name>_mesh_indexed.ply (the mesh's units: that writer adds no offset); T and D in voxels; single process only
+struct CompareRef { bool on = false; std::string file; std::vector<float> xyz; std::vector<int32_t> faces; double tau_voxels = 1.0, max_voxels = 8.0; };
+inline CompareRef& compare_ref() { static CompareRef r; return r; }
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
 inline bool& skip_sync_back() { static bool v = false; return v; }      // voxelPS --host-writers: round 4's path (dense download, host marching cubes, iostream): the cross-check
@@ -266,6 +274,125 @@ inline bool write_mesh_fit_ply(const std::string& file, const float* xyz, const 
     for (size_t i = 0; i < nv; ++i, p += kPlyFitVertexBytes) { memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes); memcpy(p + 27, rms + i, 4); memcpy(p + 31, loss + i, 4); memcpy(p + 35, n_obs + i, 4); }
     bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
     return fclose(f) == 0 && ok;
+}
+// the welded mesh with its distance to a reference (include/psgsdf_compare.h): the format of _mesh_indexed.ply with two more vertex properties behind
+// the colours -- float distance (inf: no match within max_dist), char side (-1 inside, +1 outside, 0 on the reference, a cloud, or no match) -- 32 B per
+// vertex, and `extra` header lines.  `voxelPS --compare-ply`.
+constexpr size_t kPlyCompareVertexBytes = kPlyVertexBytes + 5;
+inline bool write_mesh_compare_ply(const std::string& file, const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv, const int32_t* faces, size_t nf,
+                                   const float origin[3], float vs, const float* dist, const int8_t* side, const std::string& extra = std::string()) {
+    FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
+    const std::string h = mesh_indexed_header(nv, nf, origin, vs, extra, "property float distance\nproperty char side\n");
+    const std::string base = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    std::string v(nv * kPlyCompareVertexBytes, '\0'); char* p = &v[0];
+    for (size_t i = 0; i < nv; ++i, p += kPlyCompareVertexBytes) { memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes); memcpy(p + 27, dist + i, 4); memcpy(p + 31, side + i, 1); }
+    bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
+    return fclose(f) == 0 && ok;
+}
+// A reference mesh or cloud from a PLY: `element vertex` with float x y z (other scalar properties are skipped by their declared sizes) and an optional
+// `element face` with a `vertex_indices` (or `vertex_index`) list of three per face; binary little-endian, as this project's own writers produce, or
+// ASCII.  Elements behind the faces are not read; an element in front of them must have scalar properties only.  false + why: anything else.
+inline bool read_reference_ply(const std::string& file, std::vector<float>& xyz, std::vector<int32_t>& faces, std::string& why) {
+    std::ifstream in(file, std::ios::binary);
+    if (!in) { why = "cannot open " + file; return false; }
+    auto type_size = [](const std::string& t) { return t == "char" || t == "uchar" || t == "int8" || t == "uint8" ? 1 : t == "short" || t == "ushort" || t == "int16" || t == "uint16" ? 2
+                                                     : t == "int" || t == "uint" || t == "float" || t == "int32" || t == "uint32" || t == "float32" ? 4 : t == "double" || t == "float64" ? 8 : 0; };
+    struct Prop { std::string name, type, count_type; bool list = false; };
+    struct Elem { std::string name; long long n = 0; std::vector<Prop> props; };
+    std::vector<Elem> elems;
+    std::string line; int format = -1;      // 0 ascii, 1 binary little-endian
+    if (!std::getline(in, line) || line.compare(0, 3, "ply") != 0) { why = file + " is not a PLY file"; return false; }
+    bool ended = false;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        std::istringstream s(line); std::string w; s >> w;
+        if (w == "end_header") { ended = true; break; }
+        if (w == "format") { std::string f; s >> f; format = f == "ascii" ? 0 : f == "binary_little_endian" ? 1 : -1; }
+        else if (w == "element") { Elem e; s >> e.name >> e.n; if (!s || e.n < 0) { why = file + ": bad element line"; return false; } elems.push_back(e); }
+        else if (w == "property") {
+            if (elems.empty()) { why = file + ": a property before any element"; return false; }
+            Prop p; s >> p.type;
+            if (p.type == "list") { p.list = true; s >> p.count_type >> p.type; }
+            s >> p.name;
+            if (!s || !type_size(p.type) || (p.list && !type_size(p.count_type))) { why = file + ": bad property line '" + line + "'"; return false; }
+            elems.back().props.push_back(p);
+        }
+    }
+    if (!ended || format < 0) { why = file + ": no end_header, or a format other than ascii and binary_little_endian"; return false; }
+    auto is_float = [](const std::string& t) { return t == "float" || t == "float32"; };
+    auto is_signed_int = [](const std::string& t) { return t == "char" || t == "short" || t == "int" || t == "int8" || t == "int16" || t == "int32"; };
+    auto read_int = [&](const std::string& t, long long& v) -> bool {      // one integer of type t: binary, or the next ASCII token
+        if (format == 0) { double d; if (!(in >> d)) return false; v = (long long)d; return true; }
+        unsigned char b[8] = {}; const int n = type_size(t);
+        if (!in.read((char*)b, n)) return false;
+        unsigned long long u = 0; for (int k = n - 1; k >= 0; --k) u = (u << 8) | b[k];
+        v = is_signed_int(t) && n < 8 && (u >> (8 * n - 1)) ? (long long)u - (1ll << (8 * n)) : (long long)u;
+        return true;
+    };
+    bool got_vertices = false;
+    xyz.clear(); faces.clear();
+    for (const Elem& e : elems) {
+        if (e.name == "vertex") {
+            int off[3] = {-1, -1, -1}, col[3] = {-1, -1, -1}, stride = 0, k = 0;
+            for (const Prop& p : e.props) {
+                if (p.list) { why = file + ": a list property in the vertex element"; return false; }
+                for (int a = 0; a < 3; ++a) if (p.name == std::string(1, "xyz"[a])) { if (!is_float(p.type)) { why = file + ": " + p.name + " is not a float"; return false; } off[a] = stride; col[a] = k; }
+                stride += type_size(p.type); ++k;
+            }
+            if (off[0] < 0 || off[1] < 0 || off[2] < 0) { why = file + ": the vertex element has no float x y z"; return false; }
+            if (e.n > (long long)INT32_MAX) { why = file + ": too many vertices"; return false; }
+            xyz.resize(3 * (size_t)e.n);
+            if (format == 1) {
+                std::vector<char> rec((size_t)stride);
+                for (long long i = 0; i < e.n; ++i) {
+                    if (!in.read(rec.data(), stride)) { why = file + ": the vertex records end early"; return false; }
+                    for (int a = 0; a < 3; ++a) memcpy(&xyz[3 * (size_t)i + a], rec.data() + off[a], 4);
+                }
+            } else {
+                for (long long i = 0; i < e.n; ++i)
+                    for (int c = 0; c < k; ++c) {
+                        std::string tok;
+                        if (!(in >> tok)) { why = file + ": the vertex lines end early"; return false; }
+                        for (int a = 0; a < 3; ++a) if (col[a] == c) {
+                            char* end = nullptr; const float v = strtof(tok.c_str(), &end);
+                            if (end == tok.c_str() || *end) { why = file + ": '" + tok + "' is not a number"; return false; }
+                            xyz[3 * (size_t)i + a] = v;
+                        }
+                    }
+            }
+            got_vertices = true;
+        } else if (e.name == "face") {
+            if (!got_vertices) { why = file + ": the face element comes before the vertices"; return false; }
+            bool has = false;
+            for (const Prop& p : e.props) has = has || (p.list && (p.name == "vertex_indices" || p.name == "vertex_index"));
+            if (!has) { why = file + ": the face element has no vertex_indices list"; return false; }
+            faces.reserve(3 * (size_t)e.n);
+            for (long long q = 0; q < e.n; ++q)
+                for (const Prop& p : e.props) {
+                    long long cnt = 1, v = 0;
+                    if (p.list && !read_int(p.count_type, cnt)) { why = file + ": the face records end early"; return false; }
+                    const bool idx = p.list && (p.name == "vertex_indices" || p.name == "vertex_index");
+                    if (idx && cnt != 3) { why = file + ": a face with " + std::to_string(cnt) + " corners (triangles only)"; return false; }
+                    for (long long j = 0; j < cnt; ++j) {
+                        if (is_float(p.type) || p.type == "double" || p.type == "float64") {      // (never an index: skipped)
+                            if (format == 0) { double d; if (!(in >> d)) { why = file + ": the face records end early"; return false; } }
+                            else { char b[8]; if (!in.read(b, type_size(p.type))) { why = file + ": the face records end early"; return false; } }
+                            continue;
+                        }
+                        if (!read_int(p.type, v)) { why = file + ": the face records end early"; return false; }
+                        if (idx) { if (v < 0 || v >= (long long)(xyz.size() / 3)) { why = file + ": a face index outside the vertices"; return false; } faces.push_back((int32_t)v); }
+                    }
+                }
+            return true;      // (what follows the faces is not read)
+        } else {      // another element in front: skipped by its declared sizes
+            long long bytes = 0, cols = 0;
+            for (const Prop& p : e.props) { if (p.list) { why = file + ": a list property in element " + e.name; return false; } bytes += type_size(p.type); ++cols; }
+            if (format == 1) in.seekg(bytes * e.n, std::ios::cur);
+            else for (long long i = 0; i < e.n * cols; ++i) { std::string tok; if (!(in >> tok)) { why = file + ": element " + e.name + " ends early"; return false; } }
+        }
+    }
+    if (!got_vertices) { why = file + ": no vertex element"; return false; }
+    return true;
 }
 // save_pointcloud / extract_pc (OptimizerAux.cpp:456-511, VolumetricGradSdf.cpp:320-376): x y z nx ny nz r g b
 inline bool write_pointcloud_ply(const std::string& file, const float* pn, const int32_t* col, size_t n) {
@@ -446,6 +573,7 @@ struct VolumetricGradSdf {
         if (ctx && clean_mesh() && !device_mesh_clean(ctx, filename)) std::cout << "couldn't save the cleaned mesh of " << filename << std::endl;
         if (ctx && mesh_lod_voxels() > 0 && !device_mesh_lod(ctx, filename)) std::cout << "couldn't save the level-of-detail mesh of " << filename << std::endl;
         if (ctx && mesh_fit() && !device_mesh_fit(ctx, filename)) std::cout << "couldn't save the mesh with its fit of " << filename << std::endl;
+        if (ctx && compare_ref().on && !device_mesh_compare(ctx, filename)) std::cout << "couldn't save the comparison of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
     }
@@ -600,6 +728,54 @@ struct VolumetricGradSdf {
             if (!write_mesh_fit_ply(base + "_mesh_fit.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, fr->data(), fl->data(), fn->data())) {
                 std::cout << "couldn't save the mesh with its fit " << base << std::endl; DumpQueue::get().report_failure();
             }
+        });
+        return true;
+    }
+    // <name>_mesh.ply -> <name>_compare.txt + <name>_mesh_compare.ply (write_mesh_compare_ply): the welded mesh (with a filter flag: its kept components)
+    // against the reference of --compare-ply.  The text file, one record per line, every length in voxels and in metres:
+    //   reference FILE points N faces F / voxel_size VS max_dist_voxels D tau_voxels T
+    //   per direction (to_reference, to_reconstruction) three lines: the counts; mean, rms, max and signed mean; the histogram's 16 bins
+    //   precision P recall R fscore F
+    static bool device_mesh_compare(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: comparison with the reference (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string base = mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                 ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file;
+        const CompareRef& ref = compare_ref();
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        const double vsd = (double)info.voxel_size;
+        psgsdf_compare_params p{}; p.max_dist = ref.max_voxels * vsd; p.tau = ref.tau_voxels * vsd;
+        psgsdf_compare r{};
+        const int64_t n_ref = (int64_t)(ref.xyz.size() / 3), n_ref_faces = (int64_t)(ref.faces.size() / 3);
+        if (psgsdf_compare_reference(ctx, clean_mesh() ? &mesh_filter() : nullptr, ref.xyz.data(), n_ref, ref.faces.data(), n_ref_faces, &p, &r) != 0) return false;
+        char line[1200]; std::string txt;
+        snprintf(line, sizeof line, "reference %s points %lld faces %lld\nvoxel_size %.9g max_dist_voxels %.17g tau_voxels %.17g\n", ref.file.c_str(), (long long)n_ref, (long long)n_ref_faces, vsd, ref.max_voxels, ref.tau_voxels);
+        txt += line;
+        const psgsdf_compare_side* sides[2] = {&r.to_reference, &r.to_reconstruction};
+        for (int d = 0; d < 2; ++d) {
+            const psgsdf_compare_side& s = *sides[d]; const char* name = d ? "to_reconstruction" : "to_reference";
+            snprintf(line, sizeof line, "%s n %lld n_valid %lld n_matched %lld n_within_tau %lld\n"
+                     "%s mean_voxels %.17g mean %.17g rms_voxels %.17g rms %.17g max_voxels %.17g max %.17g mean_signed_voxels %.17g mean_signed %.17g\n%s hist", name, (long long)s.n, (long long)s.n_valid,
+                     (long long)s.n_matched, (long long)s.n_within_tau, name, s.mean / vsd, s.mean, s.rms / vsd, s.rms, s.max / vsd, s.max, s.mean_signed / vsd, s.mean_signed, name);
+            txt += line;
+            for (int b = 0; b < 16; ++b) txt += " " + std::to_string((long long)s.hist[b]);
+            txt += "\n";
+        }
+        snprintf(line, sizeof line, "precision %.17g recall %.17g fscore %.17g\n", r.precision, r.recall, r.fscore);
+        txt += line;
+        snprintf(line, sizeof line, "comment compare precision %.9g recall %.9g fscore %.9g tau %.9g max_dist %.9g\n", r.precision, r.recall, r.fscore, p.tau, p.max_dist);
+        const std::string extra = line;
+        const int64_t nv = r.n_vertices, nf = r.n_faces;
+        auto vx = std::make_shared<std::vector<float>>(r.xyz, r.xyz + 3 * nv), vnr = std::make_shared<std::vector<float>>(r.normals, r.normals + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(r.rgb, r.rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(r.faces, r.faces + 3 * nf);
+        auto vd = std::make_shared<std::vector<float>>(r.vertex_dist, r.vertex_dist + nv); auto vsd8 = std::make_shared<std::vector<int8_t>>(r.vertex_side, r.vertex_side + nv);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            FILE* f = fopen((base + "_compare.txt").c_str(), "wb");
+            bool ok = f && fwrite(txt.data(), 1, txt.size(), f) == txt.size();
+            if (f && fclose(f) != 0) ok = false;
+            if (nf > 0) ok = write_mesh_compare_ply(base + "_mesh_compare.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, vd->data(), vsd8->data(), extra) && ok;
+            if (!ok) { std::cout << "couldn't save the comparison " << base << std::endl; DumpQueue::get().report_failure(); }
         });
         return true;
     }
@@ -1001,6 +1177,7 @@ public:
         if (clean_mesh() && !VolumetricGradSdf::device_mesh_clean(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the cleaned mesh " << save_path_ << filename << std::endl;
         if (mesh_lod_voxels() > 0 && !VolumetricGradSdf::device_mesh_lod(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the level-of-detail mesh " << save_path_ << filename << std::endl;
         if (mesh_fit() && !VolumetricGradSdf::device_mesh_fit(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the mesh with its fit " << save_path_ << filename << std::endl;
+        if (compare_ref().on && !VolumetricGradSdf::device_mesh_compare(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the comparison " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");
             if (!ok) std::cout << "couldn't save mesh " << save_path_ << filename << std::endl;

@@ -130,6 +130,23 @@ static int selftest_ply_fit(const char* path) {
     return psgsdf_host::write_mesh_fit_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, rms, loss, n_obs) ? 0 : 1;
 }
 
+// `--selftest-ply-compare out.ply`: the same octahedron through the writer of `--compare-ply` (two more vertex properties, one more header line;
+// tests/test_compare_cpu.py parses it back) and back through the reader of `--compare-ply`, which has to skip what it does not want by the
+// declared sizes: 0 iff the positions and faces it returns are the ones written
+static int selftest_ply_compare(const char* path) {
+    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
+    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
+    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
+    const float origin[3] = {-0.25f, 0.5f, 1.0f};
+    const float dist[6] = {0.125f, 0.03125f, 0.0f, INFINITY, 0.0625f, 0.5f};
+    const int8_t side[6] = {1, -1, 0, 0, -1, 1};
+    if (!psgsdf_host::write_mesh_compare_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, dist, side, "comment compare selftest\n")) return 1;
+    std::vector<float> rx; std::vector<int32_t> rf; std::string why;
+    if (!psgsdf_host::read_reference_ply(path, rx, rf, why)) { std::cerr << why << std::endl; return 1; }
+    return rx.size() == 18 && rf.size() == 24 && memcmp(rx.data(), xyz, sizeof xyz) == 0 && memcmp(rf.data(), faces, sizeof faces) == 0 ? 0 : 1;
+}
+
 // `--selftest-obj-bake out.obj`: the same octahedron with made-up texture coordinates (dyadic, so that 1 - v is exact) through the writer of
 // `--mesh-bake` -- out.obj, out.mtl -- and three normals through the normal map's byte rule into out_normal.png (tests/test_bake_cpu.py parses them back)
 static int selftest_obj_bake(const char* path) {
@@ -253,12 +270,15 @@ int main(int argc, char* argv[]) {
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-fit") return selftest_ply_fit(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-obj-bake") return selftest_obj_bake(argv[2]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-compare") return selftest_ply_compare(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
     std::string configfile, timing_file;      // --timing <file.json>: wall-clock per stage (no reference counterpart; the reference's outputs are unchanged)
     std::string filter_flag;                  // the last of --mesh-min-faces / --mesh-keep-largest given
     bool lod_flag = false, lod_ok = true;     // --mesh-lod S given / S is a number > 0
     bool bake_flag = false, bake_ok = true;   // --mesh-bake R given / R is a whole number >= 1
     bool ao_flag = false, ao_ok = true;       // --mesh-bake-ao K given / K is 8, 16, 32 or 64
+    std::string cmp_file, cmp_bad;            // --compare-ply FILE given / the --compare-* flag whose number is bad
+    bool cmp_tau_flag = false, cmp_max_flag = false;
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
@@ -271,6 +291,11 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-bake" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); bake_ok = end != argv[i] && *end == 0 && v >= 1 && v <= 16383; mesh_bake_res() = bake_ok ? (int)v : 0; bake_flag = true; }      // with --mesh-lod: <name>_mesh_lod.obj / .mtl / _albedo.png / _normal.png next to every <name>_mesh_lod.ply: the reconstruction's albedo and normals baked onto the coarse mesh, R texels along a triangle's edge (include/psgsdf_bake.h)
         else if (a == "--mesh-bake-ao" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); ao_ok = end != argv[i] && *end == 0 && (v == 8 || v == 16 || v == 32 || v == 64); mesh_bake_ao_dirs() = ao_ok ? (int)v : 0; ao_flag = true; }      // with --mesh-bake: <name>_mesh_lod_ao.png and a map_Ka line in the .mtl: ambient occlusion of the reconstructed surface, K rays per texel (include/psgsdf_occlusion.h)
         else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
+        else if (a == "--compare-ply" && i + 1 < argc) cmp_file = argv[++i];      // <name>_compare.txt and <name>_mesh_compare.ply next to every <name>_mesh.ply: distances between the welded mesh and the mesh or cloud in FILE, precision / recall / F (include/psgsdf_compare.h)
+        else if ((a == "--compare-tau" || a == "--compare-max") && i + 1 < argc) {      // the threshold of precision / recall and the matching radius, in voxels (defaults 1 and 8)
+            char* end = nullptr; const double v = strtod(argv[++i], &end);
+            if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0) || v > 64) cmp_bad = a;
+            (a == "--compare-tau" ? compare_ref().tau_voxels : compare_ref().max_voxels) = v; (a == "--compare-tau" ? cmp_tau_flag : cmp_max_flag) = true; }
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
@@ -290,6 +315,15 @@ int main(int argc, char* argv[]) {
     if ((want_ranks > 1 || multi_rank()) && bake_flag) { std::cerr << "--mesh-bake needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && lod_flag) { std::cerr << "--mesh-lod needs a single process: clusters are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && mesh_fit()) { std::cerr << "--mesh-fit needs a single process: the fit is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if (!cmp_bad.empty()) { std::cerr << cmp_bad << ": a number of voxels, 0 < tau <= max <= 64" << std::endl; return 1; }
+    if ((cmp_tau_flag || cmp_max_flag) && cmp_file.empty()) { std::cerr << "--compare-tau / --compare-max need --compare-ply FILE: the reference to compare with" << std::endl; return 1; }
+    if (!cmp_file.empty()) {
+        if (want_ranks > 1 || multi_rank()) { std::cerr << "--compare-ply needs a single process: the welded mesh is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+        if (compare_ref().tau_voxels > compare_ref().max_voxels) { std::cerr << (cmp_tau_flag ? "--compare-tau" : "--compare-max") << ": tau " << compare_ref().tau_voxels << " is more than the matching radius " << compare_ref().max_voxels << std::endl; return 1; }
+        std::string why;
+        if (!read_reference_ply(cmp_file, compare_ref().xyz, compare_ref().faces, why)) { std::cerr << "--compare-ply: " << why << std::endl; return 1; }
+        compare_ref().file = cmp_file; compare_ref().on = true;
+    }
     if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
     if (want_ranks > 1 && !multi_rank()) return launch_ranks(want_ranks, transport == "sockets", argc, argv);
     static std::ofstream null_out;
