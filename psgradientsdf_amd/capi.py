@@ -118,6 +118,27 @@ class Compare(C.Structure):      # psgsdf_compare
                 ("precision", C.c_double), ("recall", C.c_double), ("fscore", C.c_double)]
 
 
+class AlignParams(C.Structure):      # psgsdf_align_params (include/psgsdf_align.h)
+    _fields_ = [("init", C.c_double * 16), ("max_dist", C.c_double), ("min_dist", C.c_double), ("shrink", C.c_double), ("eps_rot", C.c_double), ("eps_trans", C.c_double),
+                ("grid_cell", C.c_double), ("directions", C.c_int32), ("max_iters", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class AlignIter(C.Structure):      # psgsdf_align_iter
+    _fields_ = [("radius", C.c_double), ("rms", C.c_double), ("n_pairs", C.c_int64 * 2), ("min_pivot", C.c_double), ("step", C.c_double * 6)]
+
+    def as_dict(self):
+        return dict(radius=self.radius, rms=self.rms, n_pairs=[int(self.n_pairs[0]), int(self.n_pairs[1])], min_pivot=self.min_pivot, step=np.array(self.step, np.float64))
+
+
+ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_DEGENERATE, ALIGN_TOO_FEW = 0, 1, 2, 3
+
+
+class Align(C.Structure):      # psgsdf_align
+    _fields_ = [("transform", C.c_double * 16), ("centre", C.c_double * 3), ("status", C.c_int32), ("n_iters", C.c_int32), ("iters", AlignIter * 64), ("system0", C.c_double * 28),
+                ("final", AlignIter), ("aligned_xyz", C.POINTER(C.c_float)), ("n_ref", C.c_int64),
+                ("xyz", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("rgb", C.POINTER(C.c_uint8)), ("faces", C.POINTER(C.c_int32)), ("n_vertices", C.c_int64), ("n_faces", C.c_int64)]
+
+
 # psgsdf_mesh_component (include/psgsdf_mesh.h), 88 bytes
 MESH_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_faces", "<i8"), ("n_edges", "<i8"), ("n_boundary_edges", "<i8"),
                                  ("n_nonmanifold_edges", "<i8"), ("area", "<f8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("kept", "<i4"), ("reserved", "<i4")])
@@ -576,6 +597,36 @@ class Api:
             s = getattr(r, name)
             out[name] = {k: (np.array(s.hist, np.int64) if k == "hist" else getattr(s, k)) for k, _ in CompareSide._fields_}
         return out
+
+    # -- rigid alignment of a reference to the welded mesh (include/psgsdf_align.h)
+    def align_reference(self, ref_xyz, ref_faces=None, init=None, max_dist=None, min_dist=None, shrink=1.0, directions=3, max_iters=30, eps_rot=1e-5, eps_trans=None, grid_cell=0.0,
+                        min_faces=0, min_area=0.0, keep_largest=0):
+        """Point-to-plane ICP of a reference onto the welded mesh (with a filter: its kept components) on the device (psgsdf_align_reference):
+        ref_xyz [n, 3] float32, ref_faces [f, 3] int32 or None for a cloud; init a rigid 4x4 taking reference units to mesh units (None: identity).
+        The matching radius of iteration k is max(min_dist, max_dist shrink^k) (None: 8 voxels and 1 voxel); directions 1: reference points ->
+        mesh faces, 2: mesh vertices -> reference, 3: both; the loop stops after a step with |omega| <= eps_rot and |v| <= eps_trans (None: 1e-3
+        voxels) or after max_iters steps.  dict of numpy copies: transform [4, 4] float64, centre [3], status (ALIGN_*), n_iters, iters (a list of
+        dicts: radius, rms, n_pairs, min_pivot, step [6]; after TOO_FEW / DEGENERATE one more entry, the state that refused), system0 [28],
+        final (a dict like iters'), aligned_xyz [n, 3] float32 (the reference under transform) and the compared mesh xyz, normals, rgb, faces.
+        Single contexts only."""
+        ref_xyz = np.ascontiguousarray(ref_xyz, np.float32).reshape(-1, 3)
+        faces = None if ref_faces is None else np.ascontiguousarray(ref_faces, np.int32).reshape(-1, 3)
+        vs = float(np.float32(self.info().voxel_size))
+        T = np.eye(4) if init is None else np.ascontiguousarray(init, np.float64).reshape(4, 4)
+        p = AlignParams((C.c_double * 16)(*T.ravel()), float(8 * vs if max_dist is None else max_dist), float(vs if min_dist is None else min_dist), float(shrink), float(eps_rot),
+                        float(1e-3 * vs if eps_trans is None else eps_trans), float(grid_cell), int(directions), int(max_iters), (C.c_int32 * 2)(0, 0))
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        r = Align()
+        self._check(self._fn("align_reference")(self.ctx, C.byref(flt) if flt is not None else None, ref_xyz.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(len(ref_xyz)),
+                                                faces.ctypes.data_as(C.POINTER(C.c_int32)) if faces is not None and len(faces) else None,
+                                                C.c_int64(0 if faces is None else len(faces)), C.byref(p), C.byref(r)), "align_reference")
+        V, F, n = r.n_vertices, r.n_faces, len(ref_xyz)
+        arr = lambda ptr, shape, dt: np.ctypeslib.as_array(ptr, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
+        shown = r.n_iters + (1 if r.status in (ALIGN_DEGENERATE, ALIGN_TOO_FEW) and r.n_iters < 64 and p.max_iters > 0 else 0)
+        return dict(transform=np.array(r.transform, np.float64).reshape(4, 4), centre=np.array(r.centre, np.float64), status=int(r.status), n_iters=int(r.n_iters),
+                    iters=[r.iters[k].as_dict() for k in range(shown)], system0=np.array(r.system0, np.float64), final=r.final.as_dict(),
+                    aligned_xyz=arr(r.aligned_xyz, (n, 3), np.float32), xyz=arr(r.xyz, (V, 3), np.float32), normals=arr(r.normals, (V, 3), np.float32),
+                    rgb=arr(r.rgb, (V, 3), np.uint8), faces=arr(r.faces, (F, 3), np.int32))
 
     # -- the photometric fit resolved over the surface (include/psgsdf_fit.h)
     def band_fit(self):

@@ -301,6 +301,10 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
     // the search of the last psgsdf_compare_reference: queries and candidate pairs evaluated, [to_reference, to_reconstruction] (tools/time_compare.py)
     snprintf(buf, sizeof(buf), ", \"last_compare\": {\"queries\": [%lld, %lld], \"pairs\": [%lld, %lld]}", c->cmp_queries[0], c->cmp_queries[1], c->cmp_pairs[0], c->cmp_pairs[1]);
     o += buf;
+    // the last psgsdf_align_reference: steps, evaluations, and over all evaluations the queries searched and candidate pairs evaluated, [direction 1, direction 2] (tools/time_align.py)
+    snprintf(buf, sizeof(buf), ", \"last_align\": {\"iterations\": %lld, \"evaluations\": %lld, \"queries\": [%lld, %lld], \"pairs\": [%lld, %lld]}", c->aln_iters, c->aln_evals, c->aln_queries[0], c->aln_queries[1],
+             c->aln_pairs[0], c->aln_pairs[1]);
+    o += buf;
     if (c->n_ranks > 1) {      // the hand-off probe as THIS rank saw it, per memory kind tried (comm.hip xr_probe): a first multi-GPU run reads its pairs here
         snprintf(buf, sizeof(buf), ", \"xr_probe\": {\"rank\": %d, \"n_ranks\": %d, \"kind_chosen\": %d, \"stale_mappings\": %lld, \"fine_grained\": {\"tried\": %lld, \"stale_records_from_lower\": %lld, \"expired_waits_lower\": %lld, \"expired_waits_upper\": %lld}, "
                  "\"uncached\": {\"tried\": %lld, \"stale_records_from_lower\": %lld, \"expired_waits_lower\": %lld, \"expired_waits_upper\": %lld}}",

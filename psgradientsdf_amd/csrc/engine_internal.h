@@ -6,7 +6,7 @@
 //   api_debug.hip     measurement and test hooks               api_render.hip     the C ABI of include/psgsdf_render.h
 //   extract.hip       mesh, point clouds, SDF block on the device (kernels and calls); extract_mesh.hip: the welded mesh, its components and
 //                     its level of detail (include/psgsdf_mesh.h), the photometric fit per band row and vertex (include/psgsdf_fit.h), the baked maps
-//                     (include/psgsdf_bake.h), ambient occlusion (include/psgsdf_occlusion.h) and the comparison with a reference (include/psgsdf_compare.h); what the two share: extract_internal.h
+//                     (include/psgsdf_bake.h), ambient occlusion (include/psgsdf_occlusion.h) the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h); what the two share: extract_internal.h
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"
@@ -46,6 +46,7 @@ enum XoSlot {
     XO_AO_DIRS, XO_AO_MASK, XO_AO_OCCLUSION,                         // psgsdf_occlusion_points (the table also of psgsdf_bake_lod_ao)
     XO_BAKE_AO_MASK, XO_BAKE_AO_OCCLUSION,                           // psgsdf_bake_lod_ao (everything else: psgsdf_bake_lod's slots)
     XO_CMP_VDIST, XO_CMP_VNEAREST, XO_CMP_VSIDE, XO_CMP_RDIST, XO_CMP_RNEAREST, XO_CMP_RSIDE,   // psgsdf_compare_reference (its mesh: XO_IMESH_*; with a filter also XO_COMPONENTS)
+    XO_ALN_XYZ,                                                      // psgsdf_align_reference: the moved reference points (its mesh: XO_IMESH_*; with a filter also XO_COMPONENTS)
     XO_COUNT
 };
 }  // namespace psge
@@ -204,6 +205,7 @@ struct psgsdf_ctx {
     bool ao_cut = true;                  // PSGSDF_AO_CUT=0: the rays of include/psgsdf_occlusion.h walk on past their radius (what the cut buys: tools/time_mesh.py; the same bits)
     long long compare_chunk = 1ll << 24; // PSGSDF_COMPARE_CHUNK: queries per launch of include/psgsdf_compare.h's search (1 .. 2^24; the same bits)
     long long cmp_pairs[2] = {0, 0}, cmp_queries[2] = {0, 0};   // the last psgsdf_compare_reference: candidate pairs evaluated and queries, per direction (psgsdf_get_tuning "last_compare"; tools/time_compare.py)
+    long long aln_evals = 0, aln_iters = 0, aln_pairs[2] = {0, 0}, aln_queries[2] = {0, 0};   // the last psgsdf_align_reference: evaluations, steps, and per direction the queries searched and candidate pairs evaluated over all evaluations (psgsdf_get_tuning "last_align"; tools/time_align.py)
     bool pcg_poll = true;                // PCG stop test by watching the mapped mailbox (PSGSDF_PCG_POLL=0: drain the stream instead)
     int need[2] = {0, 0}; int* d_need = nullptr;   // halo rows needed below row0 / from row1 up
     bool own_stream = true;

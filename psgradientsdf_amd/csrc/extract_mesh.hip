@@ -4,7 +4,7 @@
 // mesh (fit.hip; "Photometric fit per voxel and vertex"); and the C ABI of include/psgsdf_bake.h: detail maps of the level-of-detail mesh (bake.hip;
 // "Baked detail maps"); and the C ABI of include/psgsdf_occlusion.h: ambient occlusion at the caller's points and as a map of the bake
 // (occlusion.hip; "Ambient occlusion"); and the C ABI of include/psgsdf_compare.h: distances to a reference mesh or cloud (compare.hip;
-// "Comparison with a reference").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
+// "Comparison with a reference") and of include/psgsdf_align.h: its rigid alignment to the mesh (align.hip; "Alignment of a reference").  Each call is a chain of stages -- welded mesh -> components -> clusters, or band fit ->
 // welded mesh -> vertex fit -- that hand each other device arrays whose kernels may still be in flight.  The CALL owns all device memory of its
 // stages in one DevMem, which waits for the stream and frees when the call returns, whichever way it returns: a stage allocates from it and never frees.
 // The frame arithmetic (extract_internal.h crop_frame) runs on the host and its results are compared bit for bit: no FMA contraction here either.
@@ -15,10 +15,12 @@
 #include "../../include/psgsdf_bake.h"
 #include "../../include/psgsdf_occlusion.h"
 #include "../../include/psgsdf_compare.h"
+#include "../../include/psgsdf_align.h"
 #include "mesh_lod.h"
 #include "bake.h"
 #include "occlusion.h"
 #include "compare.h"
+#include "align.h"
 
 using namespace psge;
 
@@ -567,6 +569,52 @@ CmpBox cmp_bbox(const float* xyz, size_t n) {
     return b;
 }
 struct CmpOut { XoSlot s_dist, s_nearest, s_side; const float** dist; const int32_t** nearest; const int8_t** side; };
+// the uniform grid over a.t_* (a.nt targets) and the box [lo, hi] into a.g (none if !box.any or without a target); waits for the stream once (the
+// grid's size).  Shared by psgsdf_compare_reference and psgsdf_align_reference.
+int compare_grid(psgsdf_ctx* c, DevMem& mem, const char* me, psg::CompareArgs& a, const CmpBox& box, double cell) {
+    psg::CompareGrid& g = a.g;
+    g = psg::CompareGrid{};
+    if (!(a.nt > 0 && box.any)) return PSGSDF_OK;
+    if (!mem.get(&a.total, 1)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory", me);
+    if (hipMemsetAsync(a.total, 0, sizeof(unsigned long long), c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
+    // the cells: edge `cell`, doubled until the grid fits kCompareMaxCells (acceleration only: no result depends on it)
+    // and the lower corner snapped down to a whole number of cells, so that the walls are the multiples of the edge
+    double h = cell, nd[3], lo[3];
+    for (;;) {
+        double cells = 1.0;
+        for (int k = 0; k < 3; ++k) { lo[k] = floor(box.lo[k] / h) * h; nd[k] = std::max(1.0, ceil((box.hi[k] - lo[k]) / h)); cells *= nd[k]; }
+        if (cells <= (double)psg::kCompareMaxCells) break;
+        h *= 2.0;
+    }
+    g.h = h; g.cells = 1;
+    for (int k = 0; k < 3; ++k) { g.lo[k] = lo[k]; g.n[k] = (int)nd[k]; g.cells *= g.n[k]; }
+    int* sums = nullptr;
+    if (!mem.get(&g.start, (size_t)g.cells + 1) || !mem.get(&g.cursor, (size_t)g.cells) || !mem.get(&sums, (size_t)((g.cells + 1 + psg::kTile - 1) / psg::kTile + 1)))
+        return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld grid cells)", me, g.cells);
+    if (hipMemsetAsync(g.start, 0, sizeof(int) * ((size_t)g.cells + 1), c->stream) != hipSuccess || hipMemsetAsync(g.cursor, 0, sizeof(int) * (size_t)g.cells, c->stream) != hipSuccess)
+        return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
+    hipError_t e = hipSuccess;
+    unsigned long long total = 0;
+    timed(c, "compare_total", [&] { e = psg::launch_compare_total(a, c->stream); });
+    if (e != hipSuccess || hipMemcpyAsync(&total, a.total, sizeof(total), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(c, PSGSDF_ERR_DEVICE, "%s: the grid's size", me);
+    if (total > (unsigned long long)INT32_MAX)
+        return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: the search grid would need %llu entries for %d targets (cells of %g): tessellate it", me, total, a.nt, h);
+    timed(c, "compare_count", [&] { e = psg::launch_compare_count(a, c->stream); });
+    if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
+    int tot = 0;
+    if (int rc = scan_counts(c, g.start, g.cells + 1, sums, &tot)) return rc;      // counts -> the cells' first entries; start[cells] = the total
+    if ((unsigned long long)tot != total) return fail(c, PSGSDF_ERR_DEVICE, "%s: the grid's counts (%d) and its total (%llu) differ", me, tot, total);
+    if (!mem.get(&g.entries, (size_t)tot)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d grid entries)", me, tot);
+    timed(c, "compare_fill", [&] { e = psg::launch_compare_fill(a, c->stream); });
+    if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
+    return PSGSDF_OK;
+}
+// the per-query arrays the search writes
+bool compare_query_arrays(DevMem& mem, psg::CompareArgs& a) {
+    const size_t nq = (size_t)a.nq;
+    return mem.get(&a.d, nq) && mem.get(&a.dist, nq) && mem.get(&a.nearest, nq) && mem.get(&a.side, nq) && mem.get(&a.pairs, nq);
+}
 // one direction: a.t_*, a.nt, a.q_xyz, a.nq and the parameters are set; the grid over the box [lo, hi] (none if !box), the search, the
 // statistics; the per-query arrays in their pinned slots (the stream has been waited for)
 int compare_direction(psgsdf_ctx* c, DevMem& mem, const char* me, psg::CompareArgs a, const CmpBox& box, double cell, int dir, const CmpOut& o, psgsdf_compare_side* S) {
@@ -575,45 +623,9 @@ int compare_direction(psgsdf_ctx* c, DevMem& mem, const char* me, psg::CompareAr
     c->cmp_queries[dir] = a.nq; c->cmp_pairs[dir] = 0;
     if (a.nq == 0) return PSGSDF_OK;
     const size_t nq = (size_t)a.nq;
-    if (!mem.get(&a.d, nq) || !mem.get(&a.dist, nq) || !mem.get(&a.nearest, nq) || !mem.get(&a.side, nq) || !mem.get(&a.pairs, nq) || !mem.get(&a.stats, (size_t)psg::kCmpStats)
-        || !mem.get(&a.total, 1)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld queries)", me, a.nq);
-    if (hipMemsetAsync(a.stats, 0, sizeof(unsigned long long) * psg::kCmpStats, c->stream) != hipSuccess || hipMemsetAsync(a.total, 0, sizeof(unsigned long long), c->stream) != hipSuccess)
-        return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
-    psg::CompareGrid& g = a.g;
-    g = psg::CompareGrid{};
-    if (a.nt > 0 && box.any) {
-        // the cells: edge `cell`, doubled until the grid fits kCompareMaxCells (acceleration only: no result depends on it)
-        // and the lower corner snapped down to a whole number of cells, so that the walls are the multiples of the edge
-        double h = cell, nd[3], lo[3];
-        for (;;) {
-            double cells = 1.0;
-            for (int k = 0; k < 3; ++k) { lo[k] = floor(box.lo[k] / h) * h; nd[k] = std::max(1.0, ceil((box.hi[k] - lo[k]) / h)); cells *= nd[k]; }
-            if (cells <= (double)psg::kCompareMaxCells) break;
-            h *= 2.0;
-        }
-        g.h = h; g.cells = 1;
-        for (int k = 0; k < 3; ++k) { g.lo[k] = lo[k]; g.n[k] = (int)nd[k]; g.cells *= g.n[k]; }
-        int* sums = nullptr;
-        if (!mem.get(&g.start, (size_t)g.cells + 1) || !mem.get(&g.cursor, (size_t)g.cells) || !mem.get(&sums, (size_t)((g.cells + 1 + psg::kTile - 1) / psg::kTile + 1)))
-            return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld grid cells)", me, g.cells);
-        if (hipMemsetAsync(g.start, 0, sizeof(int) * ((size_t)g.cells + 1), c->stream) != hipSuccess || hipMemsetAsync(g.cursor, 0, sizeof(int) * (size_t)g.cells, c->stream) != hipSuccess)
-            return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
-        hipError_t e = hipSuccess;
-        unsigned long long total = 0;
-        timed(c, "compare_total", [&] { e = psg::launch_compare_total(a, c->stream); });
-        if (e != hipSuccess || hipMemcpyAsync(&total, a.total, sizeof(total), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-            return fail(c, PSGSDF_ERR_DEVICE, "%s: the grid's size", me);
-        if (total > (unsigned long long)INT32_MAX)
-            return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: the search grid would need %llu entries for %d targets (cells of %g): tessellate it", me, total, a.nt, h);
-        timed(c, "compare_count", [&] { e = psg::launch_compare_count(a, c->stream); });
-        if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
-        int tot = 0;
-        if (int rc = scan_counts(c, g.start, g.cells + 1, sums, &tot)) return rc;      // counts -> the cells' first entries; start[cells] = the total
-        if ((unsigned long long)tot != total) return fail(c, PSGSDF_ERR_DEVICE, "%s: the grid's counts (%d) and its total (%llu) differ", me, tot, total);
-        if (!mem.get(&g.entries, (size_t)tot)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%d grid entries)", me, tot);
-        timed(c, "compare_fill", [&] { e = psg::launch_compare_fill(a, c->stream); });
-        if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
-    }
+    if (!compare_query_arrays(mem, a) || !mem.get(&a.stats, (size_t)psg::kCmpStats)) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld queries)", me, a.nq);
+    if (hipMemsetAsync(a.stats, 0, sizeof(unsigned long long) * psg::kCmpStats, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
+    if (int rc = compare_grid(c, mem, me, a, box, cell)) return rc;
     hipError_t e = hipSuccess;
     timed(c, dir ? "compare_query_rec" : "compare_query_ref", [&] { e = psg::launch_compare_query(a, c->compare_chunk, c->stream); });
     if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld queries: %s", me, a.nq, hipGetErrorString(e));
@@ -704,6 +716,216 @@ extern "C" int psgsdf_compare_reference(psgsdf_ctx* c, const psgsdf_mesh_filter*
     if (r.to_reference.n_valid > 0) r.precision = (double)r.to_reference.n_within_tau / (double)r.to_reference.n_valid;
     if (r.to_reconstruction.n_valid > 0) r.recall = (double)r.to_reconstruction.n_within_tau / (double)r.to_reconstruction.n_valid;
     if (r.precision + r.recall > 0.0) r.fscore = 2.0 * r.precision * r.recall / (r.precision + r.recall);
+    *out = r;
+    return PSGSDF_OK;
+}
+
+// ---- alignment of a reference to the compared mesh (include/psgsdf_align.h; kernels: align.hip and compare.hip's search): the two grids are built
+// once, every evaluation moves the points, searches, reduces the rows to one 6x6 system on the device and brings 32 doubles to the host, which
+// solves and composes in double.
+namespace {
+// the step of the header: 0 and xi, or 1 (a pivot <= 1e-6: degenerate); *min_pivot the smallest pivot met
+int align_solve(const double* sys, double* min_pivot, double* xi) {
+    double A[6][6], S[6][6], L[6][6] = {}, s[6], b[6], z[6], w[6];
+    for (int i = 0, k = 0; i < 6; ++i) for (int j = i; j < 6; ++j, ++k) A[i][j] = A[j][i] = sys[psg::AL_A + k];
+    *min_pivot = 0.0;
+    for (int i = 0; i < 6; ++i) { if (!(A[i][i] > 0.0)) return 1; s[i] = sqrt(A[i][i]); }
+    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) S[i][j] = A[i][j] / (s[i] * s[j]);
+    double mp = INFINITY;
+    for (int j = 0; j < 6; ++j) {
+        double d = S[j][j];
+        for (int k = 0; k < j; ++k) d = d - L[j][k] * L[j][k];
+        if (!(d >= mp)) mp = d;
+        *min_pivot = mp;
+        if (!(d > 1e-6)) return 1;
+        L[j][j] = sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double v = S[i][j];
+            for (int k = 0; k < j; ++k) v = v - L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    for (int i = 0; i < 6; ++i) b[i] = -(sys[psg::AL_G + i] / s[i]);
+    for (int i = 0; i < 6; ++i) { double v = b[i]; for (int k = 0; k < i; ++k) v = v - L[i][k] * z[k]; z[i] = v / L[i][i]; }
+    for (int i = 5; i >= 0; --i) { double v = z[i]; for (int k = i + 1; k < 6; ++k) v = v - L[k][i] * w[k]; w[i] = v / L[i][i]; }
+    for (int i = 0; i < 6; ++i) xi[i] = w[i] / s[i];
+    return 0;
+}
+inline double aln_dot(const double* u, const double* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
+// T <- Delta o T with Delta(x) = c + Exp(omega)(x - c) + v; T is 3x4 row-major
+void align_compose(double* T, const double* om, const double* v, const double* c) {
+    const double th2 = aln_dot(om, om), th = sqrt(th2);
+    double a, b;
+    if (th < 1e-8) { a = 1.0 - th2 / 6.0; b = 0.5 - th2 / 24.0; } else { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
+    const double K[3][3] = {{0.0, -om[2], om[1]}, {om[2], 0.0, -om[0]}, {-om[1], om[0], 0.0}};
+    double E[3][3], N[12];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) E[i][j] = ((i == j ? 1.0 : 0.0) + a * K[i][j]) + b * (om[i] * om[j] - (i == j ? th2 : 0.0));
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) N[4 * i + j] = (E[i][0] * T[j] + E[i][1] * T[4 + j]) + E[i][2] * T[8 + j];
+        const double t[3] = {T[3], T[7], T[11]};
+        N[4 * i + 3] = aln_dot(E[i], t) + ((c[i] - aln_dot(E[i], c)) + v[i]);
+    }
+    memcpy(T, N, sizeof(N));
+}
+}  // namespace
+
+extern "C" int psgsdf_align_reference(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, const float* ref_xyz, int64_t n_ref, const int32_t* ref_faces, int64_t n_ref_faces,
+                                      const psgsdf_align_params* params, psgsdf_align* out) {
+    const char* me = "align_reference";
+    if (!params || !out || (n_ref > 0 && !ref_xyz)) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    // (before anything collective and before any device work: no rank waits for another)
+    if (c && c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): a slab holds only its own share of the mesh", me, c->rank, c->n_ranks);
+    if (n_ref < 0 || n_ref > (int64_t)INT32_MAX || n_ref_faces < 0 || (n_ref_faces > 0 && !ref_faces))
+        return fail(c, PSGSDF_ERR_ARG, "%s: %lld reference points, %lld faces%s", me, (long long)n_ref, (long long)n_ref_faces, n_ref_faces > 0 && !ref_faces ? " (null)" : "");
+    const psgsdf_align_params& P = *params;
+    {   // init: finite, last row 0 0 0 1, R^T R = I to 1e-6
+        bool rigid = P.init[12] == 0.0 && P.init[13] == 0.0 && P.init[14] == 0.0 && P.init[15] == 1.0;
+        for (int i = 0; i < 12; ++i) rigid = rigid && std::isfinite(P.init[i]);
+        for (int i = 0; i < 3 && rigid; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const double g = (P.init[i] * P.init[j] + P.init[4 + i] * P.init[4 + j]) + P.init[8 + i] * P.init[8 + j];
+                rigid = rigid && fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-6;
+            }
+        if (!rigid) return fail(c, PSGSDF_ERR_ARG, "%s: init is not a rigid transform (finite, last row 0 0 0 1, R^T R = I to 1e-6)", me);
+    }
+    if (!(P.max_dist > 0.0) || std::isinf(P.max_dist) || !(P.min_dist > 0.0) || !(P.min_dist <= P.max_dist) || !(P.shrink > 0.0) || !(P.shrink <= 1.0) || !(P.eps_rot >= 0.0) || std::isinf(P.eps_rot)
+        || !(P.eps_trans >= 0.0) || std::isinf(P.eps_trans) || !(P.grid_cell >= 0.0) || std::isinf(P.grid_cell) || P.directions < 1 || P.directions > 3 || P.max_iters < 0 || P.max_iters > 64
+        || P.reserved[0] != 0 || P.reserved[1] != 0)
+        return fail(c, PSGSDF_ERR_ARG, "%s: max_dist %g, min_dist %g, shrink %g, eps_rot %g, eps_trans %g, grid_cell %g, directions %d, max_iters %d, reserved %d %d (finite, 0 < min_dist <= max_dist, 0 < shrink <= 1, "
+                    "eps >= 0, grid_cell >= 0, directions 1 .. 3, max_iters 0 .. 64, reserved 0)", me, P.max_dist, P.min_dist, P.shrink, P.eps_rot, P.eps_trans, P.grid_cell, P.directions, P.max_iters, P.reserved[0], P.reserved[1]);
+    if (c && c->have_volume && P.max_dist > 64.0 * (double)c->grid.vs) return fail(c, PSGSDF_ERR_ARG, "%s: max_dist %g is more than 64 voxels of %g", me, P.max_dist, (double)c->grid.vs);
+    for (int64_t i = 0; i < 3 * n_ref_faces; ++i)
+        if (ref_faces[i] < 0 || (int64_t)ref_faces[i] >= n_ref) return fail(c, PSGSDF_ERR_ARG, "%s: face %lld has the index %d (%lld reference points)", me, (long long)(i / 3), ref_faces[i], (long long)n_ref);
+    if (filter && bad_filter(*filter)) return fail(c, PSGSDF_ERR_ARG, "%s: min_area is NaN or keep_largest < 0", me);
+    if (n_ref_faces > (int64_t)INT32_MAX) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: %lld reference faces", me, (long long)n_ref_faces);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *out = psgsdf_align{};
+    auto bail = [&](int rc) { *out = psgsdf_align{}; return rc; };
+    const double vs = (double)c->grid.vs;
+    c->aln_evals = c->aln_iters = 0; c->aln_pairs[0] = c->aln_pairs[1] = c->aln_queries[0] = c->aln_queries[1] = 0;
+    DevMem mem(c);
+    // the compared mesh, on the device and in the slots of the call it mirrors
+    MeshView mv;
+    if (!filter) {
+        WMeshDev m;
+        if (int rc = wmesh_device(c, mem, &m)) return bail(rc);
+        mv = m;
+    } else {
+        MCompDev d;
+        if (int rc = mcomp_device(c, mem, me, *filter, &d)) return bail(rc);
+        if (d.nc != 0 && d.nv > 0 && d.nf > 0) mv = d;      // (else: an empty mesh, or a filter that drops everything)
+    }
+    const size_t nv = (size_t)mv.nv, nf = (size_t)mv.nf;
+    psgsdf_align r{};
+    if (int rc = download(c, me, {{XO_IMESH_XYZ, mv.xyz, sizeof(float) * 3 * nv, &r.xyz}, {XO_IMESH_NORMALS, mv.nrm, sizeof(float) * 3 * nv, &r.normals}, {XO_IMESH_RGB, mv.rgb, 3 * nv, &r.rgb},
+                                  {XO_IMESH_FACES, mv.faces, sizeof(int) * 3 * nf, &r.faces}})) return bail(rc);
+    r.n_vertices = (int64_t)nv; r.n_faces = (int64_t)nf; r.n_ref = n_ref;
+    memcpy(r.transform, P.init, sizeof(r.transform));
+    // the reference, uploaded once; the moved points of both directions
+    const bool dir1 = (P.directions & 1) != 0, dir2 = (P.directions & 2) != 0;
+    float *d_rxyz = nullptr, *d_mref = nullptr, *d_mvert = nullptr; int* d_rfaces = nullptr;
+    if ((n_ref > 0 && !(mem.get(&d_rxyz, 3 * (size_t)n_ref) && mem.get(&d_mref, 3 * (size_t)n_ref))) || (n_ref_faces > 0 && !mem.get(&d_rfaces, 3 * (size_t)n_ref_faces))
+        || (dir2 && nv > 0 && !mem.get(&d_mvert, 3 * nv)))
+        return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld reference points, %lld faces)", me, (long long)n_ref, (long long)n_ref_faces));
+    if ((n_ref > 0 && hipMemcpyAsync(d_rxyz, ref_xyz, sizeof(float) * 3 * (size_t)n_ref, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        || (n_ref_faces > 0 && hipMemcpyAsync(d_rfaces, ref_faces, sizeof(int) * 3 * (size_t)n_ref_faces, hipMemcpyHostToDevice, c->stream) != hipSuccess))
+        return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: upload", me));
+    // each grid covers its targets' box inflated by max_dist (a little more: rounding never drops a pair at the rim): the radius only shrinks, and
+    // the search clamps or skips a query outside the box
+    const double cell = P.grid_cell > 0.0 ? P.grid_cell : 2.0 * vs;
+    const double grow = P.max_dist * (1.0 + 1e-6) + 1e-6 * cell;
+    CmpBox bm = cmp_bbox(r.xyz, nv), br = cmp_bbox(ref_xyz, (size_t)n_ref);
+    double ctr[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < 3 && bm.any; ++k) ctr[k] = (bm.lo[k] + bm.hi[k]) / 2.0;
+    memcpy(r.centre, ctr, sizeof(ctr));
+    for (int k = 0; k < 3; ++k) { bm.lo[k] -= grow; bm.hi[k] += grow; br.lo[k] -= grow; br.hi[k] += grow; }
+    psg::AlignRowArgs R1{}, R2{};
+    int nb1 = 0, nb2 = 0;
+    double* d_sys = nullptr;
+    if (!mem.get(&d_sys, (size_t)psg::kAlignSys)) return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory", me));
+    if (dir1 && n_ref > 0) {      // the moved reference points against the mesh's faces
+        psg::CompareArgs& a = R1.s;
+        a.vs = vs; a.tau = P.max_dist; a.max_dist = P.max_dist;
+        a.q_xyz = d_mref; a.nq = (long long)n_ref; a.t_xyz = mv.xyz; a.t_faces = mv.faces; a.nt = (int)nf;
+        nb1 = (int)psg::align_row_blocks(a.nq);
+        if (!compare_query_arrays(mem, a) || !mem.get(&R1.partial, (size_t)nb1 * psg::kAlignRow)) return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld queries)", me, a.nq));
+        if (int rc = compare_grid(c, mem, me, a, bm, cell)) return bail(rc);
+    }
+    if (dir2 && nv > 0) {         // the mesh's vertices, moved into the reference's units, against the reference's targets
+        psg::CompareArgs& a = R2.s;
+        a.vs = vs; a.tau = P.max_dist; a.max_dist = P.max_dist;
+        a.q_xyz = d_mvert; a.nq = (long long)nv; a.t_xyz = d_rxyz; a.t_faces = d_rfaces; a.nt = (int)(n_ref_faces > 0 ? n_ref_faces : n_ref);
+        nb2 = (int)psg::align_row_blocks(a.nq);
+        if (!compare_query_arrays(mem, a) || !mem.get(&R2.partial, (size_t)nb2 * psg::kAlignRow)) return bail(fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld queries)", me, a.nq));
+        if (int rc = compare_grid(c, mem, me, a, br, cell)) return bail(rc);
+    }
+    for (psg::AlignRowArgs* R : {&R1, &R2}) { memcpy(R->c, ctr, sizeof(ctr)); R->vs = vs; R->v_xyz = mv.xyz; R->v_nrm = mv.nrm; }
+    double T[12];
+    memcpy(T, P.init, sizeof(T));
+    // one evaluation at T with the radius: 32 doubles and one wait
+    auto evaluate = [&](double radius, double* sys) -> int {
+        double Ti[12];
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) Ti[4 * i + j] = T[4 * j + i];
+            Ti[4 * i + 3] = -((T[i] * T[3] + T[4 + i] * T[7]) + T[8 + i] * T[11]);
+        }
+        hipError_t e = hipSuccess;
+        psg::AlignMoveArgs m{};
+        memcpy(m.M, T, sizeof(T)); m.src = d_rxyz; m.dst = d_mref; m.n = (long long)n_ref;
+        timed(c, "align_move", [&] { e = psg::launch_align_move(m, c->stream); });
+        if (e == hipSuccess && nb2 > 0) {
+            memcpy(m.M, Ti, sizeof(Ti)); m.src = mv.xyz; m.dst = d_mvert; m.n = (long long)nv;
+            timed(c, "align_move", [&] { e = psg::launch_align_move(m, c->stream); });
+        }
+        if (e == hipSuccess && nb1 > 0) {
+            R1.s.max_dist = radius;
+            timed(c, "align_query_1", [&] { e = psg::launch_compare_query(R1.s, c->compare_chunk, c->stream); });
+            if (e == hipSuccess) timed(c, "align_rows_1", [&] { e = psg::launch_align_rows(R1, 1, c->stream); });
+        }
+        if (e == hipSuccess && nb2 > 0) {
+            R2.s.max_dist = radius; memcpy(R2.T, T, sizeof(T));
+            timed(c, "align_query_2", [&] { e = psg::launch_compare_query(R2.s, c->compare_chunk, c->stream); });
+            if (e == hipSuccess) timed(c, "align_rows_2", [&] { e = psg::launch_align_rows(R2, 2, c->stream); });
+        }
+        if (e == hipSuccess) timed(c, "align_fold", [&] { e = psg::launch_align_fold(R1.partial, nb1, R2.partial, nb2, d_sys, c->stream); });
+        if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
+        if (hipMemcpyAsync(sys, d_sys, sizeof(double) * psg::kAlignSys, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the system", me);
+        c->aln_evals += 1;
+        c->aln_queries[0] += nb1 > 0 ? R1.s.nq : 0; c->aln_queries[1] += nb2 > 0 ? R2.s.nq : 0;
+        c->aln_pairs[0] += (long long)sys[psg::AS_PAIRS]; c->aln_pairs[1] += (long long)sys[psg::AS_PAIRS + 1];
+        return PSGSDF_OK;
+    };
+    r.status = PSGSDF_ALIGN_MAX_ITERS;
+    bool last = P.max_iters == 0;
+    double pw = 1.0;
+    for (int k = 0;; ++k) {
+        const double radius = std::max(P.min_dist, P.max_dist * pw);
+        double sys[psg::kAlignSys];
+        if (int rc = evaluate(radius, sys)) return bail(rc);
+        if (k == 0) memcpy(r.system0, sys, sizeof(r.system0));
+        psgsdf_align_iter it{};
+        const double n = sys[psg::AS_N] + sys[psg::AS_N + 1];
+        it.radius = radius; it.rms = n > 0.0 ? vs * sqrt(sys[psg::AL_E] / n) : 0.0;
+        it.n_pairs[0] = (int64_t)sys[psg::AS_N]; it.n_pairs[1] = (int64_t)sys[psg::AS_N + 1];
+        r.final = it;
+        if (last) { if (r.n_iters == 0 && n < 6.0) r.status = PSGSDF_ALIGN_TOO_FEW; break; }
+        if (n < 6.0) { r.status = PSGSDF_ALIGN_TOO_FEW; r.iters[k] = it; break; }
+        double xi[6];
+        const int deg = align_solve(sys, &it.min_pivot, xi);
+        if (deg) { r.status = PSGSDF_ALIGN_DEGENERATE; r.iters[k] = it; break; }
+        const double v[3] = {xi[3] * vs, xi[4] * vs, xi[5] * vs};
+        for (int i = 0; i < 3; ++i) { it.step[i] = xi[i]; it.step[3 + i] = v[i]; }
+        r.iters[k] = it; r.n_iters = k + 1;
+        align_compose(T, xi, v, ctr);
+        memcpy(r.transform, T, sizeof(T));
+        const bool conv = sqrt(aln_dot(xi, xi)) <= P.eps_rot && sqrt(aln_dot(v, v)) <= P.eps_trans;
+        if (conv) r.status = PSGSDF_ALIGN_CONVERGED;
+        last = conv || k + 1 == P.max_iters;
+        pw *= P.shrink;
+    }
+    c->aln_iters = r.n_iters;
+    if (int rc = download(c, me, {{XO_ALN_XYZ, d_mref, sizeof(float) * 3 * (size_t)n_ref, &r.aligned_xyz}})) return bail(rc);
     *out = r;
     return PSGSDF_OK;
 }

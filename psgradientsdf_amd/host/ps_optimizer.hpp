@@ -41,6 +41,7 @@
 #include "../../include/psgsdf_bake.h"
 #include "../../include/psgsdf_occlusion.h"
 #include "../../include/psgsdf_compare.h"
+#include "../../include/psgsdf_align.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 #include "obj_writer.hpp"
@@ -120,7 +121,10 @@ inline bool& mesh_fit() { static bool v = false; return v; }
 // max / signed mean, histogram, precision / recall / F) and a <name>_mesh_compare.ply (the welded mesh -- the filtered one, if a filter flag is given --
 // with every vertex's distance to the reference and the side it lies on): psgsdf_compare_reference against the mesh or cloud read from FILE, whose
 // coordinates are those of <name>_mesh_indexed.ply (the mesh's units: that writer adds no offset); T and D in voxels; single process only
-struct CompareRef { bool on = false; std::string file; std::vector<float> xyz; std::vector<int32_t> faces; double tau_voxels = 1.0, max_voxels = 8.0; };
+// --compare-align [--compare-align-iters K]: before each comparison the reference is aligned to that dump's mesh from the identity (psgsdf_align_reference:
+// both directions, the filter flags applied, the radius of --compare-max, at most K = 30 steps), the comparison runs on the aligned points, and a
+// <name>_align.txt is written next to <name>_compare.txt: the status word, one line per iteration, the final evaluation, the 4x4 transform with %.17g
+struct CompareRef { bool on = false; std::string file; std::vector<float> xyz; std::vector<int32_t> faces; double tau_voxels = 1.0, max_voxels = 8.0; bool align = false; int align_iters = 30; };
 inline CompareRef& compare_ref() { static CompareRef r; return r; }
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
@@ -747,7 +751,38 @@ struct VolumetricGradSdf {
         psgsdf_compare_params p{}; p.max_dist = ref.max_voxels * vsd; p.tau = ref.tau_voxels * vsd;
         psgsdf_compare r{};
         const int64_t n_ref = (int64_t)(ref.xyz.size() / 3), n_ref_faces = (int64_t)(ref.faces.size() / 3);
-        if (psgsdf_compare_reference(ctx, clean_mesh() ? &mesh_filter() : nullptr, ref.xyz.data(), n_ref, ref.faces.data(), n_ref_faces, &p, &r) != 0) return false;
+        const float* ref_xyz = ref.xyz.data();
+        std::vector<float> aligned;      // --compare-align: the reference under the transform found for THIS dump (a copy: the engine's array lives until the next extraction call)
+        if (ref.align) {
+            auto al = std::make_unique<psgsdf_align>();
+            psgsdf_align_params ap{};
+            for (int i = 0; i < 4; ++i) ap.init[5 * i] = 1.0;
+            ap.max_dist = p.max_dist; ap.min_dist = std::min(vsd, p.max_dist); ap.shrink = 1.0; ap.eps_rot = 1e-5; ap.eps_trans = 1e-3 * vsd; ap.directions = 3; ap.max_iters = ref.align_iters;
+            if (psgsdf_align_reference(ctx, clean_mesh() ? &mesh_filter() : nullptr, ref.xyz.data(), n_ref, ref.faces.data(), n_ref_faces, &ap, al.get()) != 0) return false;
+            aligned.assign(al->aligned_xyz, al->aligned_xyz + 3 * n_ref);
+            ref_xyz = aligned.data();
+            static const char* const words[4] = {"converged", "max_iters", "degenerate", "too_few"};
+            char ln[1200]; std::string at;
+            snprintf(ln, sizeof ln, "status %s iterations %d\nreference %s points %lld faces %lld\nvoxel_size %.9g max_dist_voxels %.17g max_iters %d\n", words[al->status & 3], (int)al->n_iters, ref.file.c_str(),
+                     (long long)n_ref, (long long)n_ref_faces, vsd, ref.max_voxels, ref.align_iters);
+            at += ln;
+            for (int k = 0; k < al->n_iters; ++k) {
+                const psgsdf_align_iter& it = al->iters[k];
+                snprintf(ln, sizeof ln, "iter %d radius_voxels %.17g rms_voxels %.17g pairs %lld %lld min_pivot %.17g step %.17g %.17g %.17g %.17g %.17g %.17g\n", k, it.radius / vsd, it.rms / vsd, (long long)it.n_pairs[0],
+                         (long long)it.n_pairs[1], it.min_pivot, it.step[0], it.step[1], it.step[2], it.step[3], it.step[4], it.step[5]);
+                at += ln;
+            }
+            snprintf(ln, sizeof ln, "final radius_voxels %.17g rms_voxels %.17g pairs %lld %lld\ntransform\n", al->final.radius / vsd, al->final.rms / vsd, (long long)al->final.n_pairs[0], (long long)al->final.n_pairs[1]);
+            at += ln;
+            for (int i = 0; i < 4; ++i) { snprintf(ln, sizeof ln, "%.17g %.17g %.17g %.17g\n", al->transform[4 * i], al->transform[4 * i + 1], al->transform[4 * i + 2], al->transform[4 * i + 3]); at += ln; }
+            DumpQueue::get().push([=] {
+                FILE* f = fopen((base + "_align.txt").c_str(), "wb");
+                bool ok = f && fwrite(at.data(), 1, at.size(), f) == at.size();
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) { std::cout << "couldn't save the alignment " << base << std::endl; DumpQueue::get().report_failure(); }
+            });
+        }
+        if (psgsdf_compare_reference(ctx, clean_mesh() ? &mesh_filter() : nullptr, ref_xyz, n_ref, ref.faces.data(), n_ref_faces, &p, &r) != 0) return false;
         char line[1200]; std::string txt;
         snprintf(line, sizeof line, "reference %s points %lld faces %lld\nvoxel_size %.9g max_dist_voxels %.17g tau_voxels %.17g\n", ref.file.c_str(), (long long)n_ref, (long long)n_ref_faces, vsd, ref.max_voxels, ref.tau_voxels);
         txt += line;

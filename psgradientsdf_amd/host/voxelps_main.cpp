@@ -278,7 +278,7 @@ int main(int argc, char* argv[]) {
     bool bake_flag = false, bake_ok = true;   // --mesh-bake R given / R is a whole number >= 1
     bool ao_flag = false, ao_ok = true;       // --mesh-bake-ao K given / K is 8, 16, 32 or 64
     std::string cmp_file, cmp_bad;            // --compare-ply FILE given / the --compare-* flag whose number is bad
-    bool cmp_tau_flag = false, cmp_max_flag = false;
+    bool cmp_tau_flag = false, cmp_max_flag = false, cmp_iters_flag = false, cmp_bad_iters = false;
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
@@ -296,6 +296,8 @@ int main(int argc, char* argv[]) {
             char* end = nullptr; const double v = strtod(argv[++i], &end);
             if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0) || v > 64) cmp_bad = a;
             (a == "--compare-tau" ? compare_ref().tau_voxels : compare_ref().max_voxels) = v; (a == "--compare-tau" ? cmp_tau_flag : cmp_max_flag) = true; }
+        else if (a == "--compare-align") compare_ref().align = true;      // with --compare-ply: the reference is first aligned to every dump's mesh by ICP on the device (include/psgsdf_align.h); <name>_align.txt next to <name>_compare.txt
+        else if (a == "--compare-align-iters" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); if (end == argv[i] || *end || v < 0 || v > 64) cmp_bad_iters = true; compare_ref().align_iters = (int)v; cmp_iters_flag = true; }
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
@@ -317,6 +319,10 @@ int main(int argc, char* argv[]) {
     if ((want_ranks > 1 || multi_rank()) && mesh_fit()) { std::cerr << "--mesh-fit needs a single process: the fit is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (!cmp_bad.empty()) { std::cerr << cmp_bad << ": a number of voxels, 0 < tau <= max <= 64" << std::endl; return 1; }
     if ((cmp_tau_flag || cmp_max_flag) && cmp_file.empty()) { std::cerr << "--compare-tau / --compare-max need --compare-ply FILE: the reference to compare with" << std::endl; return 1; }
+    if (cmp_bad_iters) { std::cerr << "--compare-align-iters: a whole number of steps, 0 .. 64" << std::endl; return 1; }
+    if (cmp_iters_flag && !compare_ref().align) { std::cerr << "--compare-align-iters needs --compare-align" << std::endl; return 1; }
+    if (compare_ref().align && cmp_file.empty()) { std::cerr << "--compare-align needs --compare-ply FILE: the reference to align" << std::endl; return 1; }
+    if (compare_ref().align && (want_ranks > 1 || multi_rank())) { std::cerr << "--compare-align needs a single process: the welded mesh is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (!cmp_file.empty()) {
         if (want_ranks > 1 || multi_rank()) { std::cerr << "--compare-ply needs a single process: the welded mesh is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
         if (compare_ref().tau_voxels > compare_ref().max_voxels) { std::cerr << (cmp_tau_flag ? "--compare-tau" : "--compare-max") << ": tau " << compare_ref().tau_voxels << " is more than the matching radius " << compare_ref().max_voxels << std::endl; return 1; }
