@@ -99,6 +99,43 @@ class BakeAo(C.Structure):      # psgsdf_bake_ao
                 ("n_dirs", C.c_int32), ("reserved", C.c_int32), ("counts", AoCounts)]
 
 
+class Light(C.Structure):      # psgsdf_light (include/psgsdf_relight.h)
+    _fields_ = [("kind", C.c_int32), ("n_sh", C.c_int32), ("sh", C.c_float * 9), ("vec", C.c_float * 3), ("colour", C.c_float * 3), ("ambient", C.c_float * 3),
+                ("spread", C.c_float), ("n_shadow", C.c_int32)]
+
+
+class RelightParams(C.Structure):      # psgsdf_relight_params
+    _fields_ = [("bias", C.c_double), ("reach", C.c_double), ("n_lights", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RelightCounts(C.Structure):      # psgsdf_relight_counts
+    _fields_ = [("n_hits", C.c_int64), ("n_lit", C.c_int64), ("n_rays", C.c_int64), ("n_occluded", C.c_int64), ("n_buried", C.c_int64)]
+
+
+LIGHT_KINDS = {"sh": 0, "directional": 1, "point": 2}
+
+
+def make_light(d):
+    """a psgsdf_light of a dict: kind ("sh", "directional", "point"), sh (4 or 9 coefficients), vec, colour (default 1, 1, 1), ambient (default 0),
+    spread (default 0), samples (the shadow rays K; default 1, an SH light has none)"""
+    L = Light()
+    kind = d["kind"]
+    L.kind = LIGHT_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if L.kind == 0:
+        sh = [float(x) for x in np.asarray(d["sh"], np.float32).reshape(-1)]
+        if len(sh) > 9:
+            raise ValueError("relight: an SH light has 4 or 9 coefficients")
+        L.n_sh = len(sh)
+        L.sh[:len(sh)] = sh
+    else:
+        L.vec[:] = [float(x) for x in np.asarray(d["vec"], np.float32).reshape(3)]
+    L.colour[:] = [float(x) for x in np.broadcast_to(np.asarray(d.get("colour", 1.0), np.float32), (3,))]
+    L.ambient[:] = [float(x) for x in np.broadcast_to(np.asarray(d.get("ambient", 0.0), np.float32), (3,))]
+    L.spread = float(d.get("spread", 0.0))
+    L.n_shadow = int(d.get("samples", 0 if L.kind == 0 else 1))
+    return L
+
+
 class CompareParams(C.Structure):      # psgsdf_compare_params (include/psgsdf_compare.h)
     _fields_ = [("max_dist", C.c_double), ("tau", C.c_double), ("grid_cell", C.c_double), ("reserved", C.c_int32 * 2)]
 
@@ -413,28 +450,31 @@ class Api:
         return dict(dist=dist, grad=grad, weight=weight, rgb=rgb, vis=vis)
 
     # -- view rendering (include/psgsdf_render.h)
-    def render(self, frame=None, pose=None, K=None, size=None, channels=None, light_frame=0):
-        """frame: a keyframe view; otherwise a caller's camera: pose (4x4 or 16 camera->world), K (3x3 or [fx, fy, cx, cy]), size (W, H),
-        shaded with the light of keyframe light_frame.  channels: R_* bits (default: every plane the view has).  Returns {plane name: array [ch, H, W] (voxel: int32 [H, W], depth / shading: [H, W])}
-        plus "stats" (RenderStats.as_dict).  On a context attached to a rank: a collective call (every rank the same view), every rank gets the whole view."""
+    def _view(self, what, frame, pose, K, size, light_frame=0):
+        """(psgsdf_view, W, H) of a keyframe, or of a caller's camera (pose, K, size)"""
         v = View()
         if frame is not None:
             v.frame = int(frame)
             w_, h_ = C.c_int32(), C.c_int32()
             self._check(self._fn("render_size")(self.ctx, C.byref(v), C.byref(w_), C.byref(h_)), "render_size")
-            W, H = w_.value, h_.value
-            channels = R_ALL if channels is None else channels
-        else:
-            if pose is None or K is None or size is None:
-                raise ValueError("render: a keyframe or (pose, K, size)")
-            channels = (R_ALL & ~R_RESIDUAL) if channels is None else channels
-            v.frame = -1
-            v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
-            k = np.asarray(K, np.float64).reshape(-1)
-            v.fx, v.fy, v.cx, v.cy = (k[0], k[4], k[2], k[5]) if k.size == 9 else tuple(k[:4])
-            v.width, v.height = int(size[0]), int(size[1])
-            v.light_frame = int(light_frame)
-            W, H = v.width, v.height
+            return v, w_.value, h_.value
+        if pose is None or K is None or size is None:
+            raise ValueError(f"{what}: a keyframe or (pose, K, size)")
+        v.frame = -1
+        v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
+        k = np.asarray(K, np.float64).reshape(-1)
+        v.fx, v.fy, v.cx, v.cy = (k[0], k[4], k[2], k[5]) if k.size == 9 else tuple(k[:4])
+        v.width, v.height = int(size[0]), int(size[1])
+        v.light_frame = int(light_frame)
+        return v, v.width, v.height
+
+    def render(self, frame=None, pose=None, K=None, size=None, channels=None, light_frame=0):
+        """frame: a keyframe view; otherwise a caller's camera: pose (4x4 or 16 camera->world), K (3x3 or [fx, fy, cx, cy]), size (W, H),
+        shaded with the light of keyframe light_frame.  channels: R_* bits (default: every plane the view has).  Returns {plane name: array [ch, H, W] (voxel: int32 [H, W], depth / shading: [H, W])}
+        plus "stats" (RenderStats.as_dict).  On a context attached to a rank: a collective call (every rank the same view), every rank gets the whole view."""
+        v, W, H = self._view("render", frame, pose, K, size, light_frame)
+        if channels is None:
+            channels = R_ALL if frame is not None else (R_ALL & ~R_RESIDUAL)
         nch = sum(n for _, bit, n in _R_PLANES if channels & bit)
         out = np.zeros((max(nch, 1), H, W), np.float32)
         st = RenderStats()
@@ -446,6 +486,26 @@ class Api:
                 res[name] = a.view(np.int32)[0].copy() if name == "voxel" else (a[0].copy() if n == 1 else a.copy())
                 q += n
         res["stats"] = st.as_dict()
+        return res
+
+    # -- relighting (include/psgsdf_relight.h)
+    def relight(self, lights, frame=None, pose=None, K=None, size=None, bias=None, reach=None, geometry=False):
+        """One view (a keyframe, or a caller's camera: pose, K, size as for render) under up to 64 lights of the caller's, with the shadows the
+        reconstruction casts on itself (psgsdf_relight).  lights: a list of dicts (make_light: kind "sh" / "directional" / "point", sh, vec, colour,
+        ambient, spread, samples).  bias: the shadow rays' lift off the surface (None: 1 voxel); reach: how far a ray occludes (None or 0: no limit).
+        dict of rendered [L, 3, H, W], visibility [L, H, W], counts (per light: n_hits, n_lit, n_rays, n_occluded, n_buried) and, with geometry,
+        depth, normal, albedo and voxel as render returns them.  Single contexts only."""
+        v, W, H = self._view("relight", frame, pose, K, size)
+        arr = (Light * max(len(lights), 1))(*[make_light(d) for d in lights])
+        vs = float(np.float32(self.info().voxel_size))
+        p = RelightParams(float(vs if bias is None else bias), float(0.0 if reach is None else reach), len(lights), 0)
+        out = np.zeros((max(len(lights), 1), 4, H, W), np.float32)
+        geo = np.zeros((8, H, W), np.float32) if geometry else None
+        cnt = (RelightCounts * max(len(lights), 1))()
+        self._check(self._fn("relight")(self.ctx, C.byref(v), arr, C.byref(p), out.ctypes.data_as(C.c_void_p), geo.ctypes.data_as(C.c_void_p) if geometry else None, cnt), "relight")
+        res = dict(rendered=out[:, :3].copy(), visibility=out[:, 3].copy(), counts=[{k: int(getattr(cnt[l], k)) for k, _ in RelightCounts._fields_} for l in range(len(lights))])
+        if geometry:
+            res.update(depth=geo[0].copy(), normal=geo[1:4].copy(), albedo=geo[4:7].copy(), voxel=geo[7].view(np.int32).copy())
         return res
 
     def render_report(self):

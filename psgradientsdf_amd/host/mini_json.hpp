@@ -1,5 +1,6 @@
 // mini_json.hpp — the subset of JSON the voxelPS config files use (one flat object of string / number / bool values,
 // config/*.json).  Replaces nlohmann::json in ConfigLoader.h:16-170 (not available in this build environment).
+// JsonNode, below, reads a whole value with nested objects and arrays: the light file of `voxelPS --relight`.
 #pragma once
 #include <cctype>
 #include <cstdlib>
@@ -7,6 +8,7 @@
 #include <map>
 #include <sstream>
 #include <string>
+#include <vector>
 
 namespace psgsdf_host {
 
@@ -69,6 +71,56 @@ public:
             os << (++k < kv_.size() ? ",\n" : "\n");
         }
         os << "}";
+    }
+};
+
+// A whole JSON value with nested objects and arrays (the light file of `voxelPS --relight`; the config files stay flat and go through JsonObject).
+struct JsonNode {
+    enum Kind { OBJECT, ARRAY, STRING, NUMBER, BOOL, NUL } kind = NUL;
+    std::string s; double n = 0; bool b = false;
+    std::vector<std::string> keys;      // OBJECT: the key of every item
+    std::vector<JsonNode> items;        // OBJECT, ARRAY
+    const JsonNode* get(const std::string& k) const { for (size_t i = 0; i < keys.size(); ++i) if (keys[i] == k) return &items[i]; return nullptr; }
+    // the whole text is one value (true), or malformed (false)
+    bool parse(const std::string& t) { size_t i = 0; if (!value(t, i, 0)) return false; ws(t, i); return i == t.size(); }
+    bool load(const std::string& path) { std::ifstream f(path); if (!f.is_open()) return false; std::stringstream ss; ss << f.rdbuf(); return parse(ss.str()); }
+private:
+    static void ws(const std::string& t, size_t& i) { while (i < t.size() && std::isspace((unsigned char)t[i])) ++i; }
+    static bool string(const std::string& t, size_t& i, std::string& out) {
+        if (i >= t.size() || t[i] != '"') return false;
+        ++i; out.clear();
+        while (i < t.size() && t[i] != '"') {
+            if (t[i] == '\\' && i + 1 < t.size()) { char c = t[++i]; out += c == 'n' ? '\n' : c == 't' ? '\t' : c; }
+            else out += t[i];
+            ++i;
+        }
+        if (i >= t.size()) return false;
+        ++i; return true;
+    }
+    bool value(const std::string& t, size_t& i, int depth) {
+        ws(t, i);
+        if (i >= t.size() || depth > 32) return false;
+        if (t[i] == '{' || t[i] == '[') {
+            const bool obj = t[i] == '{'; const char close = obj ? '}' : ']';
+            kind = obj ? OBJECT : ARRAY; ++i; ws(t, i);
+            if (i < t.size() && t[i] == close) { ++i; return true; }
+            while (true) {
+                if (obj) { std::string k; ws(t, i); if (!string(t, i, k)) return false; ws(t, i); if (i >= t.size() || t[i] != ':') return false; ++i; keys.push_back(k); }
+                items.emplace_back();
+                if (!items.back().value(t, i, depth + 1)) return false;
+                ws(t, i);
+                if (i < t.size() && t[i] == ',') { ++i; continue; }
+                if (i < t.size() && t[i] == close) { ++i; return true; }
+                return false;
+            }
+        }
+        if (t[i] == '"') { kind = STRING; return string(t, i, s); }
+        if (!t.compare(i, 4, "true")) { kind = BOOL; b = true; i += 4; return true; }
+        if (!t.compare(i, 5, "false")) { kind = BOOL; b = false; i += 5; return true; }
+        if (!t.compare(i, 4, "null")) { kind = NUL; i += 4; return true; }
+        char* end = nullptr; n = std::strtod(t.c_str() + i, &end);
+        if (end == t.c_str() + i) return false;
+        kind = NUMBER; i = end - t.c_str(); return true;
     }
 };
 

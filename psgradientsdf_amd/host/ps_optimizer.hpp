@@ -36,6 +36,7 @@
 
 #include "../../include/psgsdf.h"
 #include "../../include/psgsdf_render.h"
+#include "../../include/psgsdf_relight.h"
 #include "../../include/psgsdf_mesh.h"
 #include "../../include/psgsdf_fit.h"
 #include "../../include/psgsdf_bake.h"
@@ -126,6 +127,9 @@ inline bool& mesh_fit() { static bool v = false; return v; }
 // <name>_align.txt is written next to <name>_compare.txt: the status word, one line per iteration, the final evaluation, the 4x4 transform with %.17g
 struct CompareRef { bool on = false; std::string file; std::vector<float> xyz; std::vector<int32_t> faces; double tau_voxels = 1.0, max_voxels = 8.0; bool align = false; int align_iters = 30; };
 inline CompareRef& compare_ref() { static CompareRef r; return r; }
+// `voxelPS --relight FILE`: the lights of the file (include/psgsdf_relight.h), bias and reach in voxels
+struct RelightSpec { bool on = false; double bias_voxels = 1.0, reach_voxels = 0.0; std::vector<psgsdf_light> lights; };
+inline RelightSpec& relight_spec() { static RelightSpec r; return r; }
 // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
 // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
 inline bool& skip_sync_back() { static bool v = false; return v; }      // voxelPS --host-writers: round 4's path (dense download, host marching cubes, iostream): the cross-check
@@ -1043,6 +1047,48 @@ public:
             snprintf(line, sizeof(line), "%s %lld %lld %.6g %.4f %.6g\n", name.c_str(), (long long)rows[f].n_hits, (long long)rows[f].n_hits_off_band, std::sqrt(mse),
                      mse > 0 ? 10.0 * std::log10(1.0 / mse) : 0.0, rows[f].robust);
             rep << line;
+        }
+        return ok;
+    }
+
+    // `--relight FILE`: every keyframe's view under every light of the file, with cast shadows (psgsdf_relight): relight/<keyframe>_light<NN>.png
+    // (the rendered plane through the 8-bit colour rule), relight/<keyframe>_light<NN>_visibility.png (grey) and one line of counts per keyframe
+    // and light in relight_report.txt.  Single process only (refused while parsing otherwise).
+    bool relightKeyframes(const std::string& prefix, const RelightSpec& spec) {
+        if (!ctx_) return false;
+        const int F = (int)num_frames_, L = (int)spec.lights.size();
+        const std::string dir = prefix + "relight/";
+        ::mkdir(dir.c_str(), 0755);
+        std::ofstream rep(prefix + "relight_report.txt");
+        rep << "# keyframe light kind samples hits lit rays occluded buried\n";
+        psgsdf_view v0{}; int32_t W = 0, H = 0;
+        if (int rc = psgsdf_render_size(ctx_, &v0, &W, &H)) return fail("psgsdf_render_size", rc);
+        psgsdf_info info{}; psgsdf_get_info(ctx_, &info);
+        psgsdf_relight_params par{};
+        par.bias = spec.bias_voxels * (double)info.voxel_size; par.reach = spec.reach_voxels * (double)info.voxel_size; par.n_lights = L;
+        const size_t HW = (size_t)W * H;
+        std::vector<float> planes((size_t)L * 4 * HW);
+        std::vector<psgsdf_relight_counts> counts(L);
+        std::vector<uint8_t> px(3 * HW);
+        bool ok = rep.is_open();
+        static const char* kinds[3] = {"sh", "directional", "point"};
+        for (int f = 0; f < F; ++f) {
+            const std::string name = f < (int)key_stamps_.size() ? key_stamps_[f] : std::to_string(f);
+            psgsdf_view v{}; v.frame = f;
+            if (int rc = psgsdf_relight(ctx_, &v, spec.lights.data(), &par, planes.data(), nullptr, counts.data())) return fail("psgsdf_relight", rc);
+            for (int l = 0; l < L; ++l) {
+                const float* p = planes.data() + (size_t)l * 4 * HW;
+                char tag[32]; snprintf(tag, sizeof(tag), "_light%02d", l);
+                for (size_t i = 0; i < HW; ++i) for (int c = 0; c < 3; ++c) px[3 * i + c] = psgsdf_host::unit_to_u8(p[c * HW + i]);
+                ok &= psgsdf_host::write_png(dir + name + tag + ".png", W, H, 3, px.data());
+                for (size_t i = 0; i < HW; ++i) px[i] = psgsdf_host::unit_to_u8(p[3 * HW + i]);
+                ok &= psgsdf_host::write_png(dir + name + tag + "_visibility.png", W, H, 1, px.data());
+                const psgsdf_relight_counts& k = counts[l];
+                char line[256];
+                snprintf(line, sizeof(line), "%s %d %s %d %lld %lld %lld %lld %lld\n", name.c_str(), l, kinds[spec.lights[l].kind], (int)spec.lights[l].n_shadow, (long long)k.n_hits,
+                         (long long)k.n_lit, (long long)k.n_rays, (long long)k.n_occluded, (long long)k.n_buried);
+                rep << line;
+            }
         }
         return ok;
     }

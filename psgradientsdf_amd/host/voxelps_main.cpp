@@ -202,6 +202,60 @@ static int selftest_fmt(long n) {
     return bad ? 1 : 0;
 }
 
+// `--relight FILE`: {"bias_voxels": 1, "reach_voxels": 0, "lights": [{"kind": "sh" | "directional" | "point", "sh": [..], "vec": [..], "colour": [..],
+// "ambient": [..], "spread": s, "samples": K}, ...]} into the lights of include/psgsdf_relight.h (defaults: colour 1, ambient 0, spread 0, one
+// shadow ray).  false: why says what is wrong with the file.
+static bool read_relight_file(const std::string& path, RelightSpec& spec, std::string& why) {
+    JsonNode root;
+    { std::ifstream f(path); if (!f.is_open()) { why = "cannot read " + path; return false; } }
+    if (!root.load(path) || root.kind != JsonNode::OBJECT) { why = path + " is not a JSON object"; return false; }
+    auto number = [&](const JsonNode* n, double& out) { if (!n) return true; if (n->kind != JsonNode::NUMBER || !std::isfinite(n->n)) return false; out = n->n; return true; };
+    if (!number(root.get("bias_voxels"), spec.bias_voxels) || !(spec.bias_voxels > 0)) { why = "bias_voxels: a number > 0"; return false; }
+    if (!number(root.get("reach_voxels"), spec.reach_voxels) || !(spec.reach_voxels >= 0)) { why = "reach_voxels: a number >= 0 (0: no limit)"; return false; }
+    const JsonNode* lights = root.get("lights");
+    if (!lights || lights->kind != JsonNode::ARRAY || lights->items.empty()) { why = "lights: a list of at least one light"; return false; }
+    if (lights->items.size() > PSGSDF_RELIGHT_MAX_LIGHTS) { why = "lights: " + std::to_string(lights->items.size()) + " lights, at most 64"; return false; }
+    for (size_t l = 0; l < lights->items.size(); ++l) {
+        const JsonNode& n = lights->items[l];
+        const std::string at = "light " + std::to_string(l) + ": ";
+        if (n.kind != JsonNode::OBJECT) { why = at + "not an object"; return false; }
+        psgsdf_light L{};
+        const JsonNode* kind = n.get("kind");
+        const std::string k = kind && kind->kind == JsonNode::STRING ? kind->s : "";
+        if (k == "sh") L.kind = PSGSDF_LIGHT_SH; else if (k == "directional") L.kind = PSGSDF_LIGHT_DIRECTIONAL; else if (k == "point") L.kind = PSGSDF_LIGHT_POINT;
+        else { why = at + "kind: sh, directional or point"; return false; }
+        // a list of `lo` to `hi` finite numbers into out; its length (0: the key is missing and `need` is false), -1: malformed
+        auto floats = [&](const char* key, float* out, int lo, int hi, bool need) {
+            const JsonNode* a = n.get(key);
+            if (!a) return need ? -1 : 0;
+            if (a->kind != JsonNode::ARRAY || (int)a->items.size() < lo || (int)a->items.size() > hi) return -1;
+            for (size_t i = 0; i < a->items.size(); ++i) { if (a->items[i].kind != JsonNode::NUMBER || !std::isfinite(a->items[i].n)) return -1; out[i] = (float)a->items[i].n; }
+            return (int)a->items.size();
+        };
+        L.colour[0] = L.colour[1] = L.colour[2] = 1.f;
+        if (floats("colour", L.colour, 3, 3, false) < 0 || floats("ambient", L.ambient, 3, 3, false) < 0) { why = at + "colour / ambient: three numbers"; return false; }
+        for (int c = 0; c < 3; ++c) if (L.colour[c] < 0.f || L.ambient[c] < 0.f) { why = at + "colour / ambient: >= 0"; return false; }
+        double spread = 0.0, samples = L.kind == PSGSDF_LIGHT_SH ? 0.0 : 1.0;
+        if (!number(n.get("spread"), spread) || spread < 0) { why = at + "spread: a number >= 0"; return false; }
+        if (!number(n.get("samples"), samples)) { why = at + "samples: a number"; return false; }
+        L.spread = (float)spread;
+        if (L.kind == PSGSDF_LIGHT_SH) {
+            const int ns = floats("sh", L.sh, 4, 9, true);
+            if (ns != 4 && ns != 9) { why = at + "sh: 4 or 9 coefficients"; return false; }
+            L.n_sh = ns;
+            if (samples != 0.0 || spread != 0.0) { why = at + "an sh light has no samples and no spread"; return false; }
+        } else {
+            if (floats("vec", L.vec, 3, 3, true) < 0) { why = at + "vec: three numbers"; return false; }
+            if (L.kind == PSGSDF_LIGHT_DIRECTIONAL && L.vec[0] == 0.f && L.vec[1] == 0.f && L.vec[2] == 0.f) { why = at + "vec: a direction of length zero"; return false; }
+            if (samples != 1 && samples != 8 && samples != 16 && samples != 32 && samples != 64) { why = at + "samples: 1, 8, 16, 32 or 64"; return false; }
+            if (spread > 0 && samples < 8) { why = at + "a spread > 0 needs at least 8 samples"; return false; }
+            L.n_shadow = (int)samples;
+        }
+        spec.lights.push_back(L);
+    }
+    return true;
+}
+
 // `voxelPS --config_file <cfg> --gpus N [--transport rccl|sockets]`: this process only starts the N ranks (itself, once per GPU) and waits for them.
 // rccl (default): rank r runs on device r, the ranks meet in ncclCommInitRank over the id made here.  sockets: the engine's node-local transport over one
 // socket pair per pair of ranks (psgsdf_comm_init_sockets) -- a node without a working RCCL, or ranks that share a device: VOXELPS_SHARE_GPU=1 puts
@@ -279,11 +333,13 @@ int main(int argc, char* argv[]) {
     bool ao_flag = false, ao_ok = true;       // --mesh-bake-ao K given / K is 8, 16, 32 or 64
     std::string cmp_file, cmp_bad;            // --compare-ply FILE given / the --compare-* flag whose number is bad
     bool cmp_tau_flag = false, cmp_max_flag = false, cmp_iters_flag = false, cmp_bad_iters = false;
+    std::string relight_file;                 // --relight FILE: every keyframe under the lights of FILE (relight/*.png, relight_report.txt; include/psgsdf_relight.h)
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
         else if (a == "--host-writers") host_writers() = true;
         else if (a == "--render-keyframes") render_keyframes = true;
+        else if (a == "--relight" && i + 1 < argc) relight_file = argv[++i];
         else if (a == "--indexed-mesh") indexed_mesh() = true;      // a <name>_mesh_indexed.ply (welded, normals, binary; include/psgsdf_mesh.h) next to every <name>_mesh.ply
         else if (a == "--mesh-min-faces" && i + 1 < argc) { mesh_filter().min_faces = atoll(argv[++i]); clean_mesh() = true; filter_flag = a; }      // <name>_mesh_clean.ply + <name>_mesh_components.txt next to every <name>_mesh.ply:
         else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
@@ -329,6 +385,12 @@ int main(int argc, char* argv[]) {
         std::string why;
         if (!read_reference_ply(cmp_file, compare_ref().xyz, compare_ref().faces, why)) { std::cerr << "--compare-ply: " << why << std::endl; return 1; }
         compare_ref().file = cmp_file; compare_ref().on = true;
+    }
+    if (!relight_file.empty()) {
+        if (want_ranks > 1 || multi_rank()) { std::cerr << "--relight needs a single process: a slab holds only its own planes of the volume the shadow rays cross (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
+        std::string why;
+        if (!read_relight_file(relight_file, relight_spec(), why)) { std::cerr << "--relight: " << why << std::endl; return 1; }
+        relight_spec().on = true;
     }
     if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
     if (want_ranks > 1 && !multi_rank()) return launch_ranks(want_ranks, transport == "sockets", argc, argv);
@@ -476,6 +538,7 @@ int main(int argc, char* argv[]) {
     vOpt->init();
     vOpt->alternatingOptimize(light, albedo, distance, pose);
     if (render_keyframes && !vOpt->renderKeyframes(output)) { std::cerr << "--render-keyframes: rendering failed" << std::endl; return 1; }   // (collective on a multi-rank run)
+    if (relight_spec().on && !vOpt->relightKeyframes(output, relight_spec())) { std::cerr << "--relight: relighting failed" << std::endl; return 1; }
     DumpQueue::get().drain();
     const int write_failures = DumpQueue::get().failures();      // (a rank whose piece of a shared output file could not be written: the file has a hole where it belongs)
     if (write_failures) std::cerr << "rank " << rank_info().rank << ": " << write_failures << " output file piece(s) could not be written" << std::endl;
