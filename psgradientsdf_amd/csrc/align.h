@@ -1,5 +1,5 @@
 // align.h -- the launchers of align.hip (psgsdf_align_reference: include/psgsdf_align.h; DESIGN.md "Alignment of a reference"), called from
-// extract_mesh.hip.  The search between a move and its rows is compare.hip's k_cmp_query (launch_compare_query), unchanged.
+// extract_compare.hip.  The search between a move and its rows is compare.hip's k_cmp_query (launch_compare_query), unchanged.
 #pragma once
 #include "compare.h"
 

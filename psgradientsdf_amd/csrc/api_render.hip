@@ -254,8 +254,7 @@ int psgsdf_relight(psgsdf_ctx* c, const psgsdf_view* v, const psgsdf_light* ligh
                    psgsdf_relight_counts* per_light) {
     const char* me = "relight";
     if (!c || !v || !lights || !p || !out_host) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
-    // (before anything collective and before any device work: no rank waits for another)
-    if (c->n_ranks > 1) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): a slab holds only its own planes of the volume", me, c->rank, c->n_ranks);
+    if (int rc = single_rank_only(c, me, "a slab holds only its own planes of the volume")) return rc;
     if (!c->inited || !c->have_frames) return fail(c, PSGSDF_ERR_STATE, "%s: init first", me);
     if (!(p->bias > 0.0) || std::isinf(p->bias) || !(p->reach >= 0.0) || std::isinf(p->reach)) return fail(c, PSGSDF_ERR_ARG, "%s: the bias must be a finite length > 0, the reach one >= 0", me);
     if (p->n_lights < 1 || p->n_lights > PSGSDF_RELIGHT_MAX_LIGHTS || p->reserved != 0) return fail(c, PSGSDF_ERR_ARG, "%s: n_lights %d, reserved %d (1 to 64 lights; reserved 0)", me, p->n_lights, p->reserved);

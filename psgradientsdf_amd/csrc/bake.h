@@ -1,4 +1,4 @@
-// bake.h -- the launcher of bake.hip (psgsdf_bake_lod, include/psgsdf_bake.h; DESIGN.md "Baked detail maps"), called from extract_mesh.hip, and the
+// bake.h -- the launcher of bake.hip (psgsdf_bake_lod, include/psgsdf_bake.h; DESIGN.md "Baked detail maps"), called from extract_bake.hip, and the
 // texel's sample as a device function.
 #pragma once
 #include "engine.h"

@@ -1,5 +1,5 @@
 // compare.h -- the launchers of compare.hip (psgsdf_compare_reference: include/psgsdf_compare.h; DESIGN.md "Comparison with a reference"), called
-// from extract_mesh.hip.
+// from extract_compare.hip.
 #pragma once
 #include "engine.h"
 

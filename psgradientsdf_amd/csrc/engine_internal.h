@@ -4,9 +4,11 @@
 //   api.hip           the C ABI of include/psgsdf.h (volume, keyframes, init, steps, downloads)
 //   api_frontend.hip  frame fusion, FALS normals, depth tracker        api_multi_gpu.hip  the z-slab phase API
 //   api_debug.hip     measurement and test hooks               api_render.hip     the C ABI of include/psgsdf_render.h
-//   extract.hip       mesh, point clouds, SDF block on the device (kernels and calls); extract_mesh.hip: the welded mesh, its components and
-//                     its level of detail (include/psgsdf_mesh.h), the photometric fit per band row and vertex (include/psgsdf_fit.h), the baked maps
-//                     (include/psgsdf_bake.h), ambient occlusion (include/psgsdf_occlusion.h) the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h); what the two share: extract_internal.h
+//   extract.hip       mesh, point clouds, SDF block on the device (kernels and calls); what it shares with the four below: extract_internal.h
+//   extract_mesh.hip  the welded mesh, its components and its level of detail (include/psgsdf_mesh.h), the photometric fit per band row and
+//                     vertex (include/psgsdf_fit.h); the stages the next two go on from: mesh_stages.h
+//   extract_bake.hip  the baked maps (include/psgsdf_bake.h) and ambient occlusion (include/psgsdf_occlusion.h)
+//   extract_compare.hip  the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h)
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"

@@ -254,7 +254,7 @@ int host_out(psgsdf_ctx* c, XoSlot slot, size_t bytes, void** p) {
     *p = c->xo_host[slot];
     return 0;
 }
-int download(psgsdf_ctx* c, const char* me, std::initializer_list<XoCopy> list) {
+int download(psgsdf_ctx* c, const char* me, const std::vector<XoCopy>& list) {
     void* h[XO_COUNT] = {}; bool any = false, ok = true;
     for (const XoCopy& e : list) if (e.bytes) { any = true; if (int rc = host_out(c, e.slot, e.bytes, &h[e.slot])) return rc; }
     if (!any) return 0;

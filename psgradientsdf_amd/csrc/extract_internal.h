@@ -1,8 +1,9 @@
-// extract_internal.h -- what the extraction calls of extract.hip (mesh, point clouds, SDF block; it defines the functions below) and of
-// extract_mesh.hip (welded mesh, components, level of detail) share on the host.
+// extract_internal.h -- what the extraction calls of extract.hip (mesh, point clouds, SDF block; it defines the functions below), of the mesh
+// calls' files (extract_mesh.hip, extract_bake.hip, extract_compare.hip; their stages: mesh_stages.h) and of api_render.hip share on the host.
 #pragma once
 #include "engine_internal.h"
 #include <initializer_list>
+#include <vector>
 
 namespace psg {
 constexpr int kTile = 1024;      // elements per workgroup of the count scan
@@ -16,6 +17,12 @@ int host_out(psgsdf_ctx* c, XoSlot slot, size_t bytes, void** p);
 int crop_box_dev(psgsdf_ctx* c, int lo[3], int hi[3], bool* any);
 // state checks of every extraction call, pending work flushed, the band's state scattered into the dense arrays
 int extract_ready(psgsdf_ctx* c, const char* what);
+// the calls that are not collective refuse a multi-rank context, `why` behind the colon.  A call checks this before anything collective and before
+// any device work: every rank that calls leaves at once, and none waits for a rank that never called
+inline int single_rank_only(psgsdf_ctx* c, const char* me, const char* why) {
+    if (!c || c->n_ranks <= 1) return PSGSDF_OK;
+    return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: not on a context attached to a rank (rank %d of %d): %s", me, c->rank, c->n_ranks, why);
+}
 
 // api_render.hip: the renderer's prepare path for a single-rank call -- dense planes, band state and grid into `a`, the occupied-brick map and its box
 // built into `m` (k_render_bricks on the stream)
@@ -28,7 +35,7 @@ struct XoCopy {
 };
 // the results of call `me` to the host: pinned slots, copies behind whatever is in flight on the stream, ONE wait; the caller's pointers are
 // written only if all of it worked
-int download(psgsdf_ctx* c, const char* me, std::initializer_list<XoCopy> list);
+int download(psgsdf_ctx* c, const char* me, const std::vector<XoCopy>& list);
 
 // the frame of the crop box [lo, hi] both meshes are built in (McGrid / WMeshGrid): the dense planes, the box, the voxel size and origin of
 // MarchingCubes as write_mesh sets them up (host/ps_optimizer.hpp, operation for operation: the meshes are compared bit for bit) and this

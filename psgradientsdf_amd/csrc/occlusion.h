@@ -1,5 +1,5 @@
 // occlusion.h -- the launchers of occlusion.hip (psgsdf_occlusion_points, psgsdf_bake_lod_ao: include/psgsdf_occlusion.h; DESIGN.md "Ambient
-// occlusion"), called from extract_mesh.hip.
+// occlusion"), called from extract_bake.hip.
 #pragma once
 #include "engine.h"
 

@@ -8,20 +8,20 @@ import functools
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import _align_ref as aref
 import _compare_ref as cref
+from _refused_ranks import refused_ranks
 from psgradientsdf_amd import capi
 from test_align_cpu import AXIS, displacement, motion, sphere_cloud
 from test_bake_gpu import scene_engine
 from test_compare_gpu import cloud600, icospheres, pieces, plane_cloud, plane_engine      # noqa: F401 (fixtures)
 from test_mesh_components_cpu import pieces_volume
 from test_mesh_components_gpu import upload, vs_of
-from test_mesh_indexed_gpu import EXE, NCU, _socket_mesh, voxelps_config
+from test_mesh_indexed_gpu import EXE, voxelps_config
 
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
@@ -261,27 +261,7 @@ def test_leaves_everything_else_alone(pieces):
 def test_ranks_are_refused_before_any_exchange(built, tmp_path):
     """on a context attached to a rank: PSGSDF_ERR_UNSUPPORTED at once -- only rank 1 calls, so a collective refusal would hang -- and the
     context goes on working (the collective psgsdf_extract_mesh_indexed afterwards)"""
-    world, timeout = 2, 150
-    sp = str(tmp_path / "spec.json"); json.dump({"N": 40, "F": 4, "callers": [1], "timeout": timeout - 20}, open(sp, "w"))
-    mesh = _socket_mesh(world)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MESH_CU_MASKS=",".join(f"{r * NCU // world}:{(r + 1) * NCU // world}" for r in range(world)))
-    outs = [str(tmp_path / f"rank{r}.json") for r in range(world)]
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_align_ranks_worker.py")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), sp, outs[r]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(env, MESH_FDS=",".join(str(f) for f in mesh[r])), pass_fds=[f for f in mesh[r] if f >= 0]) for r in range(world)]
-    for row in mesh:
-        for f in row:
-            if f >= 0:
-                os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    res = [json.load(open(o)) for o in outs]
+    res = refused_ranks(tmp_path, "align")
     assert res[0]["errors"] == [] and len(res[1]["errors"]) == 3
     for e in res[1]["errors"]:
         assert "rc=-3" in e and "rank 1 of 2" in e and "align_reference" in e, e

@@ -16,16 +16,16 @@ import filecmp
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import _fit_ref as fref
+from _refused_ranks import refused_ranks
 from psgradientsdf_amd import capi, synth
 from test_fit_cpu import assert_header_matches_columns, header_fit_numbers, read_ply_fit
 from test_mesh_indexed_cpu import read_ply_indexed
-from test_mesh_indexed_gpu import EXE, NCU, _socket_mesh, ulps, voxelps_config
+from test_mesh_indexed_gpu import EXE, ulps, voxelps_config
 
 pytestmark = pytest.mark.gpu
 ROW_TOL = {"SH1": (4 * 8.826e-05, 4 * 7.120e-05), "SH2": (4 * 2.185e-05, 4 * 1.540e-05), "LED": (4 * 3.216e-05, 4 * 2.580e-05)}      # (loss, sum_r2): four times the measured deviations above
@@ -256,27 +256,7 @@ def test_errors_and_the_empty_mesh(built):
 def test_ranks_are_refused_before_any_exchange(built, tmp_path):
     """on a context attached to a rank: PSGSDF_ERR_UNSUPPORTED at once -- only rank 1 calls, so a collective refusal would hang -- and the
     context goes on working (the collective psgsdf_extract_mesh_indexed afterwards)"""
-    world, timeout = 2, 150
-    sp = str(tmp_path / "spec.json"); json.dump({"N": 32, "F": 3, "callers": [1], "timeout": timeout - 20}, open(sp, "w"))
-    mesh = _socket_mesh(world)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MESH_CU_MASKS=",".join(f"{r * NCU // world}:{(r + 1) * NCU // world}" for r in range(world)))
-    outs = [str(tmp_path / f"rank{r}.json") for r in range(world)]
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_fit_ranks_worker.py")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), sp, outs[r]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(env, MESH_FDS=",".join(str(f) for f in mesh[r])), pass_fds=[f for f in mesh[r] if f >= 0]) for r in range(world)]
-    for row in mesh:
-        for f in row:
-            if f >= 0:
-                os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    res = [json.load(open(o)) for o in outs]
+    res = refused_ranks(tmp_path, "fit", N=32, F=3)
     assert res[0]["errors"] == [] and len(res[1]["errors"]) == 2
     for e in res[1]["errors"]:
         assert "rc=-3" in e and "rank 1 of 2" in e, e

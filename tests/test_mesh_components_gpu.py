@@ -4,7 +4,6 @@ import filecmp
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,9 +11,10 @@ from scipy.sparse.csgraph import connected_components  # noqa: F401  (the yardst
 
 import _mesh_components_ref as cref
 import _mesh_ref as ref
+from _refused_ranks import refused_ranks
 from psgradientsdf_amd import capi, synth
 from test_mesh_components_cpu import pieces_volume
-from test_mesh_indexed_gpu import EXE, GOLD, NCU, _socket_mesh, analytic_engine, synth_engine, voxelps_config
+from test_mesh_indexed_gpu import EXE, GOLD, analytic_engine, synth_engine, voxelps_config
 
 pytestmark = pytest.mark.gpu
 FILTERS = (dict(min_faces=100), dict(min_area=50.0), dict(keep_largest=2), dict(keep_largest=1, min_faces=6000))      # min_area in units of vs^2
@@ -165,27 +165,7 @@ def test_reproducible_leaves_the_full_mesh_alone_empty_and_state_error(built):
 def test_ranks_are_refused_before_any_exchange(built, tmp_path):
     """on a context attached to a rank: PSGSDF_ERR_UNSUPPORTED at once -- only rank 1 calls, so a collective refusal would hang -- and the
     context goes on working (the collective psgsdf_extract_mesh_indexed afterwards)"""
-    world, timeout = 2, 150
-    sp = str(tmp_path / "spec.json"); json.dump({"N": 40, "F": 4, "callers": [1], "timeout": timeout - 20}, open(sp, "w"))
-    mesh = _socket_mesh(world)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MESH_CU_MASKS=",".join(f"{r * NCU // world}:{(r + 1) * NCU // world}" for r in range(world)))
-    outs = [str(tmp_path / f"rank{r}.json") for r in range(world)]
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_mesh_components_ranks_worker.py")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), sp, outs[r]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(env, MESH_FDS=",".join(str(f) for f in mesh[r])), pass_fds=[f for f in mesh[r] if f >= 0]) for r in range(world)]
-    for row in mesh:
-        for f in row:
-            if f >= 0:
-                os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    res = [json.load(open(o)) for o in outs]
+    res = refused_ranks(tmp_path, "mesh_components")
     assert res[0]["errors"] == [] and len(res[1]["errors"]) == 2
     for e in res[1]["errors"]:
         assert "rc=-3" in e and "rank 1 of 2" in e, e
