@@ -99,6 +99,22 @@ class BakeAo(C.Structure):      # psgsdf_bake_ao
                 ("n_dirs", C.c_int32), ("reserved", C.c_int32), ("counts", AoCounts)]
 
 
+class PhotoParams(C.Structure):      # psgsdf_photo_params (include/psgsdf_photo.h)
+    _fields_ = [("bias", C.c_double), ("cos_min", C.c_double), ("shade_min", C.c_double), ("want_status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PhotoCounts(C.Structure):      # psgsdf_photo_counts
+    _fields_ = [(k, C.c_int64) for k in ("n_samples", "n_pairs", "n_used", "n_outside", "n_grazing", "n_occluded", "n_buried", "n_dark", "n_texels_solved")]
+
+
+class BakePhoto(C.Structure):      # psgsdf_bake_photo
+    _fields_ = [("bake", Bake), ("photo", C.POINTER(C.c_float)), ("photo_rgb", C.POINTER(C.c_uint8)), ("n_obs", C.POINTER(C.c_int32)), ("status", C.POINTER(C.c_uint8)),
+                ("n_frames", C.c_int32), ("reserved", C.c_int32), ("counts", PhotoCounts)]
+
+
+PHOTO_USED, PHOTO_OUTSIDE, PHOTO_GRAZING, PHOTO_OCCLUDED, PHOTO_DARK, PHOTO_NO_SAMPLE = 0, 1, 2, 3, 4, 255
+
+
 class Light(C.Structure):      # psgsdf_light (include/psgsdf_relight.h)
     _fields_ = [("kind", C.c_int32), ("n_sh", C.c_int32), ("sh", C.c_float * 9), ("vec", C.c_float * 3), ("colour", C.c_float * 3), ("ambient", C.c_float * 3),
                 ("spread", C.c_float), ("n_shadow", C.c_int32)]
@@ -627,6 +643,29 @@ class Api:
         out["mask"] = np.ctypeslib.as_array(b.mask, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint64)
         out["dirs"] = np.ctypeslib.as_array(b.dirs, shape=(b.n_dirs, 3)).copy()
         out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in AoCounts._fields_}
+        return out
+
+    # -- the albedo texture solved from the keyframes (include/psgsdf_photo.h)
+    def bake_lod_photo(self, cell, res, reach=None, bias=None, cos_min=0.2, shade_min=0.05, status=False, min_faces=0, min_area=0.0, keep_largest=0):
+        """bake_lod's dict for the same arguments (bit for bit) plus the albedo of every texel solved from the keyframes that see it
+        (psgsdf_bake_lod_photo): photo [H, W, 3] float32 (unclamped), photo_rgb [H, W, 3] uint8, n_obs [H, W] int32 (keyframes used), status
+        [n_frames, H, W] uint8 (PHOTO_USED, _OUTSIDE, _GRAZING, _OCCLUDED, _DARK, _NO_SAMPLE) or None unless `status`, and counts, a dict of
+        n_samples, n_pairs, n_used, n_outside, n_grazing, n_occluded, n_buried, n_dark, n_texels_solved.  A keyframe counts for a texel if the
+        texel projects into it, its normal makes a cosine > cos_min with the direction to the camera, the ray towards the camera (lifted off the
+        surface by `bias`; None: 1 voxel) is free, and the model's shading is >= shade_min.  After init; single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        vs = float(np.float32(self.info().voxel_size))
+        b, p = BakePhoto(), PhotoParams(float(vs if bias is None else bias), float(cos_min), float(shade_min), 1 if status else 0, 0)
+        self._check(self._fn("bake_lod_photo")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
+                                               C.c_double(float(cell if reach is None else reach)), C.byref(p), C.byref(b)), "bake_lod_photo")
+        out = self._bake_dict(b.bake)
+        W, H, F = b.bake.width, b.bake.height, b.n_frames
+        arr = lambda ptr, shape, dt: np.ctypeslib.as_array(ptr, shape=shape).copy() if W * H else np.zeros(shape, dt)
+        out["photo"] = arr(b.photo, (H, W, 3), np.float32)
+        out["photo_rgb"] = arr(b.photo_rgb, (H, W, 3), np.uint8)
+        out["n_obs"] = arr(b.n_obs, (H, W), np.int32)
+        out["status"] = arr(b.status, (F, H, W), np.uint8) if status else None
+        out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in PhotoCounts._fields_}
         return out
 
     # -- comparison with a reference mesh or cloud (include/psgsdf_compare.h)

@@ -7,7 +7,8 @@
 //   extract.hip       mesh, point clouds, SDF block on the device (kernels and calls); what it shares with the four below: extract_internal.h
 //   extract_mesh.hip  the welded mesh, its components and its level of detail (include/psgsdf_mesh.h), the photometric fit per band row and
 //                     vertex (include/psgsdf_fit.h); the stages the next two go on from: mesh_stages.h
-//   extract_bake.hip  the baked maps (include/psgsdf_bake.h) and ambient occlusion (include/psgsdf_occlusion.h)
+//   extract_bake.hip  the baked maps (include/psgsdf_bake.h), ambient occlusion (include/psgsdf_occlusion.h) and the albedo texture solved from the
+//                     keyframes (include/psgsdf_photo.h)
 //   extract_compare.hip  the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h)
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
@@ -47,6 +48,7 @@ enum XoSlot {
     XO_BAKE_UV, XO_BAKE_ALBEDO, XO_BAKE_NORMAL, XO_BAKE_DISPLACEMENT, XO_BAKE_VOXEL, XO_BAKE_FACE,   // psgsdf_bake_lod (its mesh: XO_IMESH_*, XO_LOD_VERTEX_MAP)
     XO_AO_DIRS, XO_AO_MASK, XO_AO_OCCLUSION,                         // psgsdf_occlusion_points (the table also of psgsdf_bake_lod_ao)
     XO_BAKE_AO_MASK, XO_BAKE_AO_OCCLUSION,                           // psgsdf_bake_lod_ao (everything else: psgsdf_bake_lod's slots)
+    XO_PHOTO, XO_PHOTO_RGB, XO_PHOTO_NOBS, XO_PHOTO_STATUS,                // psgsdf_bake_lod_photo (everything else: psgsdf_bake_lod's slots)
     XO_CMP_VDIST, XO_CMP_VNEAREST, XO_CMP_VSIDE, XO_CMP_RDIST, XO_CMP_RNEAREST, XO_CMP_RSIDE,   // psgsdf_compare_reference (its mesh: XO_IMESH_*; with a filter also XO_COMPONENTS)
     XO_ALN_XYZ,                                                      // psgsdf_align_reference: the moved reference points (its mesh: XO_IMESH_*; with a filter also XO_COMPONENTS)
     XO_COUNT

@@ -1,19 +1,22 @@
 // extract_bake.hip -- the C ABI of include/psgsdf_bake.h: detail maps of the level-of-detail mesh (kernel: bake.hip; DESIGN.md "Baked detail maps"),
-// and of include/psgsdf_occlusion.h: ambient occlusion at the caller's points and as a map of the bake (occlusion.hip; "Ambient occlusion").
+// of include/psgsdf_occlusion.h: ambient occlusion at the caller's points and as a map of the bake (occlusion.hip; "Ambient occlusion"),
+// and of include/psgsdf_photo.h: the bake's albedo solved again from the keyframes, per texel (photo.hip; "Photometric albedo texture").
 // The texture coordinates and the direction table are computed on the host and compared bit for bit: no FMA contraction.
 #pragma clang fp contract(off)
 #include "mesh_stages.h"
 #include "../../include/psgsdf_bake.h"
 #include "../../include/psgsdf_occlusion.h"
+#include "../../include/psgsdf_photo.h"
 #include "bake.h"
 #include "occlusion.h"
+#include "photo.h"
 
 using namespace psge;
 
 // ---- the bake (kernel: bake.hip k_bake).  The clusters' device arrays are the kernel's mesh (lod_from_device hands them out: nothing is uploaded
 // again), the brick map comes from the renderer's prepare path.
 namespace {
-// what psgsdf_bake_lod and psgsdf_bake_lod_ao check first
+// what psgsdf_bake_lod, psgsdf_bake_lod_ao and psgsdf_bake_lod_photo check first
 int bake_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach) {
     if (int rc = lod_ready(c, me, filter, cell)) return rc;
     if (res < 1) return fail(c, PSGSDF_ERR_ARG, "%s: res %d (at least 1)", me, res);
@@ -21,8 +24,10 @@ int bake_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, 
     return PSGSDF_OK;
 }
 // the bake of both calls, its results in their pinned host slots (the stream has been waited for); dev (if asked for): the kernel's arguments, the
-// atlas's device planes among them (dev->nf == 0: an empty level-of-detail mesh, nothing was baked)
-int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out, psg::BakeArgs* dev = nullptr) {
+// atlas's device planes among them (dev->nf == 0: an empty level-of-detail mesh, nothing was baked).  max_texels (if not 0): a larger atlas is refused
+// like one beyond 16384, before it is allocated
+int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out, psg::BakeArgs* dev = nullptr,
+                long long max_texels = 0) {
     *out = psgsdf_bake{};
     MeshView lod;
     if (int rc = lod_stages(c, mem, me, filter, cell, LodOut{&out->xyz, &out->normals, &out->rgb, &out->n_vertices, &out->faces, &out->n_faces, &out->vertex_map,
@@ -37,6 +42,7 @@ int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_fi
     while (bpr > 1 && (bpr - 1) * (bpr - 1) >= nblk) --bpr;
     const long long W = bpr * B, H = (nblk + bpr - 1) / bpr * B;
     if (W > psg::kBakeMaxSide || H > psg::kBakeMaxSide) return give_up(PSGSDF_ERR_UNSUPPORTED, "the atlas would be larger than 16384 texels along a side");
+    if (max_texels && W * H > max_texels) return give_up(PSGSDF_ERR_UNSUPPORTED, "the atlas has more texels than the call's per-keyframe status plane may hold (2^30 bytes in all)");
     { RenderArgs ra; int rc = render_prepare(c, mem, ra, me); if (rc) { *out = psgsdf_bake{}; return rc; } a.r = ra; }
     a.has_band = c->inited ? 1 : 0;
     a.xyz = lod.xyz; a.nrm = lod.nrm; a.rgb = lod.rgb; a.faces = lod.faces; a.nf = lod.nf;
@@ -182,5 +188,57 @@ extern "C" int psgsdf_bake_lod_ao(psgsdf_ctx* c, const psgsdf_mesh_filter* filte
         if (int rc = ao_run(c, mem, me, *params, D, a, true, XO_BAKE_AO_MASK, XO_BAKE_AO_OCCLUSION, &out->mask, &out->occlusion, &out->counts)) { *out = psgsdf_bake_ao{}; return rc; }
     }
     out->dirs = D;
+    return PSGSDF_OK;
+}
+
+// ---- the albedo texture solved from the keyframes (kernels: photo.hip k_photo_pairs, k_photo_solve): the bake as above, its planes still on the
+// device; then per pass one launch over the (texel, keyframe) pairs, whose status bytes go to the caller's plane or to a bounded scratch buffer,
+// and one over the texels.
+extern "C" int psgsdf_bake_lod_photo(psgsdf_ctx* c, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, const psgsdf_photo_params* p, psgsdf_bake_photo* out) {
+    const char* me = "bake_lod_photo";
+    if (!out || !p) return fail(c, PSGSDF_ERR_ARG, "%s: null argument", me);
+    if (int rc = bake_ready(c, me, filter, cell, res, reach)) return rc;
+    if (!(p->bias > 0.0) || std::isinf(p->bias)) return fail(c, PSGSDF_ERR_ARG, "%s: the bias must be a finite length > 0", me);
+    if (!(p->cos_min >= -1.0) || !(p->cos_min < 1.0)) return fail(c, PSGSDF_ERR_ARG, "%s: cos_min %g (-1 <= cos_min < 1)", me, p->cos_min);
+    if (!(p->shade_min > 0.0) || std::isinf(p->shade_min)) return fail(c, PSGSDF_ERR_ARG, "%s: shade_min must be finite and > 0", me);
+    if ((p->want_status != 0 && p->want_status != 1) || p->reserved != 0) return fail(c, PSGSDF_ERR_ARG, "%s: want_status %d, reserved %d (0 or 1; reserved 0)", me, p->want_status, p->reserved);
+    if (!c || !c->inited || !c->have_frames) return fail(c, PSGSDF_ERR_STATE, "%s: init first (the keyframes, their poses and lights are read)", me);
+    { int rc = extract_ready(c, me); if (rc) return rc; }
+    *out = psgsdf_bake_photo{};
+    DevMem mem(c);
+    psg::BakeArgs b{};
+    const bool keep = p->want_status != 0;      // the caller's status plane: at most kPhotoChunk bytes, refused before the atlas is allocated
+    if (int rc = bake_device(c, mem, me, filter, cell, res, reach, &out->bake, &b, keep ? psg::kPhotoChunk / c->F : 0)) { *out = psgsdf_bake_photo{}; return rc; }
+    out->n_frames = c->F;
+    if (b.nf <= 0) return PSGSDF_OK;
+    auto give_up = [&](int code, const char* what) { *out = psgsdf_bake_photo{}; return fail(c, code, "%s: %s (%d x %d texels, %d keyframes)", me, what, b.W, b.H, c->F); };
+    psg::PhotoArgs a{};
+    a.n = (long long)b.W * b.H;
+    const SweepArgs e = make_args(c, 0);      // the energy's own view of the keyframes
+    a.r = b.r; a.im = e.im; a.cam = e.cam; a.rob = e.rob; a.F = e.F; a.model = e.model;
+    a.bias = p->bias; a.cos_min = p->cos_min; a.shade_min = (float)p->shade_min; a.vs = (double)c->grid.vs;
+    for (int k = 0; k < 3; ++k) a.origin[k] = (double)c->grid.origin[k];
+    a.xyz = b.xyz; a.nrm = b.nrm; a.faces = b.faces; a.res = b.res; a.W = b.W;
+    a.albedo = b.albedo; a.normal = b.normal; a.disp = b.disp; a.voxel = b.voxel; a.face = b.face;
+    a.scratch = !keep; a.stride = a.n; a.base = 0;
+    const size_t n = (size_t)a.n, n_status = (size_t)c->F * (size_t)psg::photo_pass_texels(a.n, c->F, a.scratch);
+    if (!mem.get(&a.photo, 3 * n) || !mem.get(&a.photo_rgb, 3 * n) || !mem.get(&a.n_obs, n) || !mem.get(&a.status, n_status) || !mem.get(&a.counts, (size_t)psg::kPhotoCounts))
+        return give_up(PSGSDF_ERR_DEVICE, "out of memory");
+    if (hipMemsetAsync(a.counts, 0, sizeof(unsigned long long) * psg::kPhotoCounts, c->stream) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "memset");
+    hipError_t launched = hipSuccess;
+    for (long long j0 = 0; j0 < a.n && launched == hipSuccess; j0 += psg::photo_pass_texels(a.n, a.F, a.scratch)) {
+        psg::photo_pass(a, j0);
+        timed(c, "k_photo_pairs", [&] { launched = psg::launch_photo_pairs(a, c->stream); });
+        if (launched == hipSuccess) timed(c, "k_photo_solve", [&] { launched = psg::launch_photo_solve(a, c->stream); });
+    }
+    if (launched != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, hipGetErrorString(launched));
+    unsigned long long cnt[psg::kPhotoCounts] = {};
+    if (hipMemcpyAsync(cnt, a.counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return give_up(PSGSDF_ERR_DEVICE, "download of the counts");
+    if (int rc = download(c, me, {{XO_PHOTO, a.photo, sizeof(float) * 3 * n, &out->photo}, {XO_PHOTO_RGB, a.photo_rgb, 3 * n, &out->photo_rgb},
+                                  {XO_PHOTO_NOBS, a.n_obs, sizeof(int) * n, &out->n_obs}, {XO_PHOTO_STATUS, a.status, keep ? n_status : 0, &out->status}})) { *out = psgsdf_bake_photo{}; return rc; }
+    psgsdf_photo_counts& k = out->counts;
+    k.n_samples = (int64_t)cnt[psg::PH_SAMPLES]; k.n_pairs = k.n_samples * c->F; k.n_used = (int64_t)cnt[psg::PH_USED]; k.n_outside = (int64_t)cnt[psg::PH_OUTSIDE];
+    k.n_grazing = (int64_t)cnt[psg::PH_GRAZING]; k.n_occluded = (int64_t)cnt[psg::PH_OCCLUDED]; k.n_buried = (int64_t)cnt[psg::PH_BURIED]; k.n_dark = (int64_t)cnt[psg::PH_DARK];
+    k.n_texels_solved = (int64_t)cnt[psg::PH_SOLVED];
     return PSGSDF_OK;
 }

@@ -41,6 +41,7 @@
 #include "../../include/psgsdf_fit.h"
 #include "../../include/psgsdf_bake.h"
 #include "../../include/psgsdf_occlusion.h"
+#include "../../include/psgsdf_photo.h"
 #include "../../include/psgsdf_compare.h"
 #include "../../include/psgsdf_align.h"
 #include "marching_cubes.hpp"
@@ -115,6 +116,10 @@ inline int& mesh_bake_res() { static int v = 0; return v; }
 // voxelPS --mesh-bake-ao K (with --mesh-bake): <name>_mesh_lod_ao.png next to the other maps (grey, 255 = open) and one `map_Ka` line in the .mtl: the
 // ambient occlusion of the reconstructed surface from K rays per texel, radius 8 voxels, origins 1 voxel off the surface (psgsdf_bake_lod_ao); 0: off
 inline int& mesh_bake_ao_dirs() { static int v = 0; return v; }
+// voxelPS --mesh-bake-photo (with --mesh-bake): <name>_mesh_lod_photo.png next to the other maps, the albedo of every texel solved from the keyframes that
+// see it (psgsdf_bake_lod_photo: rays lifted 1 voxel, cos_min 0.2, shade_min 0.05), and `map_Kd` in the .mtl names it; _albedo.png is still written.  A
+// dump taken before psgsdf_init (the fused volume's) has no keyframes to solve from and is baked as without the flag
+inline bool& mesh_bake_photo() { static bool v = false; return v; }
 // voxelPS --mesh-fit: next to every <name>_mesh.ply a <name>_mesh_fit.ply, the welded mesh with the photometric fit of every vertex (psgsdf_extract_mesh_fit): how many
 // keyframes saw it, the rms residual and the mean robust loss; single process only
 inline bool& mesh_fit() { static bool v = false; return v; }
@@ -667,12 +672,21 @@ struct VolumetricGradSdf {
         const double cell = mesh_lod_voxels() * (double)info.voxel_size;
         psgsdf_bake bk{};      // --mesh-bake: the same level-of-detail arrays (bit for bit) and the atlas, in one call
         psgsdf_bake_ao ao{};   // --mesh-bake-ao: the same bake (bit for bit) and the occlusion map
+        psgsdf_bake_photo ph{};   // --mesh-bake-photo: the same bake (bit for bit) and the albedo solved from the keyframes
         if (mesh_bake_res() > 0) {
+            bool baked = false;
             if (mesh_bake_ao_dirs() > 0) {
                 const psgsdf_ao_params ap{mesh_bake_ao_dirs(), 0, 8.0 * (double)info.voxel_size, (double)info.voxel_size};
                 if (psgsdf_bake_lod_ao(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &ap, &ao) != 0) return false;
-                bk = ao.bake;
-            } else if (psgsdf_bake_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &bk) != 0) return false;
+                bk = ao.bake; baked = true;
+            }
+            if (mesh_bake_photo()) {      // (behind the occlusion: its map has slots of its own, the bake's are filled again with the same bits)
+                const psgsdf_photo_params pp{(double)info.voxel_size, 0.2, 0.05, 0, 0};
+                const int rc = psgsdf_bake_lod_photo(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &pp, &ph);
+                if (rc == 0) { bk = ph.bake; baked = true; }
+                else if (rc != PSGSDF_ERR_STATE) return false;      // (before psgsdf_init: no keyframes yet)
+            }
+            if (!baked && psgsdf_bake_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &bk) != 0) return false;
             if (bk.n_faces_in == 0) return false;
             xyz = bk.xyz; nrm = bk.normals; rgb = bk.rgb; faces = bk.faces; nv = bk.n_vertices; nf = bk.n_faces; nv_in = bk.n_vertices_in; nf_in = bk.n_faces_in;
         } else if (psgsdf_extract_mesh_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vmap, &nv_in, &nf_in) != 0
@@ -702,13 +716,21 @@ struct VolumetricGradSdf {
                 occ->assign(ao.occlusion, ao.occlusion + px);
                 std::cout << "ambient occlusion: " << ao.counts.n_rays << " rays (" << ao.n_dirs << " per texel), " << ao.counts.n_occluded << " occluded, " << ao.counts.n_buried << " of them buried" << std::endl;
             }
+            const bool with_photo = ph.photo_rgb != nullptr;
+            auto pho = std::make_shared<std::vector<uint8_t>>();
+            if (with_photo) {
+                pho->assign(ph.photo_rgb, ph.photo_rgb + 3 * px);
+                std::cout << "photo albedo: " << ph.counts.n_texels_solved << " of " << ph.counts.n_samples << " texels solved from " << ph.counts.n_used << " of " << ph.counts.n_pairs
+                          << " views (" << ph.counts.n_outside << " outside, " << ph.counts.n_grazing << " grazing, " << ph.counts.n_occluded << " occluded, " << ph.counts.n_dark << " dark)" << std::endl;
+            }
             DumpQueue::get().push([=] {
                 const std::string lod = base + "_mesh_lod";
-                bool ok = write_obj_bake(lod + ".obj", lod + ".mtl", lod + "_albedo.png", lod + "_normal.png", vx->data(), vn->data(), (size_t)nv, vf->data(), uv->data(), (size_t)nf,
+                bool ok = write_obj_bake(lod + ".obj", lod + ".mtl", lod + (with_photo ? "_photo.png" : "_albedo.png"), lod + "_normal.png", vx->data(), vn->data(), (size_t)nv, vf->data(), uv->data(), (size_t)nf,
                                          with_ao ? lod + "_ao.png" : std::string());
                 ok = write_png(lod + "_albedo.png", W, H, 3, alb->data()) && ok;
                 ok = write_png(lod + "_normal.png", W, H, 3, nmap->data()) && ok;
                 if (with_ao) ok = write_png(lod + "_ao.png", W, H, 1, occ->data()) && ok;
+                if (with_photo) ok = write_png(lod + "_photo.png", W, H, 3, pho->data()) && ok;
                 if (!ok) { std::cout << "couldn't save the baked level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure(); }
             });
         }

@@ -346,6 +346,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_lod_voxels() = lod_ok ? v : 0.0; lod_flag = true; }      // <name>_mesh_lod.ply next to every <name>_mesh.ply: the vertices of every cube of S voxels merged (include/psgsdf_mesh.h psgsdf_extract_mesh_lod)
         else if (a == "--mesh-bake" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); bake_ok = end != argv[i] && *end == 0 && v >= 1 && v <= 16383; mesh_bake_res() = bake_ok ? (int)v : 0; bake_flag = true; }      // with --mesh-lod: <name>_mesh_lod.obj / .mtl / _albedo.png / _normal.png next to every <name>_mesh_lod.ply: the reconstruction's albedo and normals baked onto the coarse mesh, R texels along a triangle's edge (include/psgsdf_bake.h)
         else if (a == "--mesh-bake-ao" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); ao_ok = end != argv[i] && *end == 0 && (v == 8 || v == 16 || v == 32 || v == 64); mesh_bake_ao_dirs() = ao_ok ? (int)v : 0; ao_flag = true; }      // with --mesh-bake: <name>_mesh_lod_ao.png and a map_Ka line in the .mtl: ambient occlusion of the reconstructed surface, K rays per texel (include/psgsdf_occlusion.h)
+        else if (a == "--mesh-bake-photo") mesh_bake_photo() = true;      // with --mesh-bake: <name>_mesh_lod_photo.png, the albedo of every texel solved from the keyframes that see it, and map_Kd in the .mtl names it (include/psgsdf_photo.h); a dump taken before the optimiser holds the keyframes is baked as without the flag
         else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
         else if (a == "--compare-ply" && i + 1 < argc) cmp_file = argv[++i];      // <name>_compare.txt and <name>_mesh_compare.ply next to every <name>_mesh.ply: distances between the welded mesh and the mesh or cloud in FILE, precision / recall / F (include/psgsdf_compare.h)
         else if ((a == "--compare-tau" || a == "--compare-max") && i + 1 < argc) {      // the threshold of precision / recall and the matching radius, in voxels (defaults 1 and 8)
@@ -367,6 +368,8 @@ int main(int argc, char* argv[]) {
     if (ao_flag && !ao_ok) { std::cerr << "--mesh-bake-ao: rays per texel, 8, 16, 32 or 64" << std::endl; return 1; }
     if (ao_flag && !bake_flag) { std::cerr << "--mesh-bake-ao needs --mesh-bake R: the occlusion is one more map of the bake" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && ao_flag) { std::cerr << "--mesh-bake-ao needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if (mesh_bake_photo() && !bake_flag) { std::cerr << "--mesh-bake-photo needs --mesh-bake R: the photo map is one more map of the bake" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && mesh_bake_photo()) { std::cerr << "--mesh-bake-photo needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (bake_flag && !bake_ok) { std::cerr << "--mesh-bake: texels along a triangle's edge, a whole number >= 1" << std::endl; return 1; }
     if (bake_flag && !lod_flag) { std::cerr << "--mesh-bake needs --mesh-lod S: the maps are baked onto the level-of-detail mesh" << std::endl; return 1; }
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }
