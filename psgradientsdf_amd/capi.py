@@ -99,6 +99,10 @@ class BakeAo(C.Structure):      # psgsdf_bake_ao
                 ("n_dirs", C.c_int32), ("reserved", C.c_int32), ("counts", AoCounts)]
 
 
+class BakeCurvature(C.Structure):      # psgsdf_bake_curvature (include/psgsdf_curvature.h)
+    _fields_ = [("bake", Bake), ("mean", C.POINTER(C.c_float)), ("valid", C.POINTER(C.c_uint8)), ("n_valid", C.c_int64)]
+
+
 class PhotoParams(C.Structure):      # psgsdf_photo_params (include/psgsdf_photo.h)
     _fields_ = [("bias", C.c_double), ("cos_min", C.c_double), ("shade_min", C.c_double), ("want_status", C.c_int32), ("reserved", C.c_int32)]
 
@@ -643,6 +647,53 @@ class Api:
         out["mask"] = np.ctypeslib.as_array(b.mask, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint64)
         out["dirs"] = np.ctypeslib.as_array(b.dirs, shape=(b.n_dirs, 3)).copy()
         out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in AoCounts._fields_}
+        return out
+
+    # -- curvature of the reconstructed surface (include/psgsdf_curvature.h)
+    def curvature_voxels(self, lin):
+        """Curvature of the distance field's level set through the centre of each voxel lin[q] (linear indices (k ny + j) nx + i, any order, any
+        value; psgsdf_curvature_voxels): dict of valid [n] uint8, mean, gauss, k1, k2 [n] float32 (inverse mesh units; a convex sphere of radius r
+        has mean = k1 = k2 = 1 / r) and dir1 [n, 3] float32, the unit direction of k1.  An invalid voxel -- out of range, on a grid face, a stencil
+        voxel unobserved, a zero gradient -- holds zeros.  Single contexts only."""
+        lin = np.ascontiguousarray(lin, np.int64).reshape(-1)
+        n = len(lin)
+        vl = C.POINTER(C.c_uint8)(); ptr = [C.POINTER(C.c_float)() for _ in range(5)]
+        self._check(self._fn("curvature_voxels")(self.ctx, lin.ctypes.data_as(C.POINTER(C.c_int64)) if n else None, C.c_int64(n), C.byref(vl), *[C.byref(p) for p in ptr]), "curvature_voxels")
+        col = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if n else np.zeros(shape, dt)
+        out = dict(valid=col(vl, (n,), np.uint8))
+        for name, p in zip(("mean", "gauss", "k1", "k2"), ptr):
+            out[name] = col(p, (n,), np.float32)
+        out["dir1"] = col(ptr[4], (n, 3), np.float32)
+        return out
+
+    def extract_mesh_curvature(self):
+        """The welded mesh with the curvature of its vertices (psgsdf_extract_mesh_curvature): dict of xyz, normals, rgb, faces (extract_mesh_indexed's
+        arrays) and valid [V] uint8 (how many of the vertex's end voxels are valid: 2, 1 or 0), mean, gauss, k1, k2 [V] float32, interpolated between
+        the end voxels' results with the vertex's own parameter; zeros where valid == 0.  Single contexts only."""
+        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)()
+        vl = C.POINTER(C.c_uint8)(); ptr = [C.POINTER(C.c_float)() for _ in range(4)]; nv, nf = C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_curvature")(self.ctx, C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(vl), *[C.byref(p) for p in ptr]),
+                    "extract_mesh_curvature")
+        V, F = nv.value, nf.value
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        col = lambda p, dt: np.ctypeslib.as_array(p, shape=(V,)).copy() if V else np.zeros(0, dt)
+        out = dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32), valid=col(vl, np.uint8))
+        for name, p in zip(("mean", "gauss", "k1", "k2"), ptr):
+            out[name] = col(p, np.float32)
+        return out
+
+    def bake_lod_curvature(self, cell, res, reach=None, min_faces=0, min_area=0.0, keep_largest=0):
+        """bake_lod's dict for the same arguments (bit for bit) plus the mean curvature of every hit texel's voxel (psgsdf_bake_lod_curvature):
+        mean [H, W] float32, valid [H, W] uint8 (0 / 0 on missed, buried and padding texels) and n_valid.  Single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        b = BakeCurvature()
+        self._check(self._fn("bake_lod_curvature")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
+                                                   C.c_double(float(cell if reach is None else reach)), C.byref(b)), "bake_lod_curvature")
+        out = self._bake_dict(b.bake)
+        W, H = b.bake.width, b.bake.height
+        out["mean"] = np.ctypeslib.as_array(b.mean, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.float32)
+        out["valid"] = np.ctypeslib.as_array(b.valid, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint8)
+        out["n_valid"] = int(b.n_valid)
         return out
 
     # -- the albedo texture solved from the keyframes (include/psgsdf_photo.h)

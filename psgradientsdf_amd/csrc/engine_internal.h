@@ -10,6 +10,7 @@
 //   extract_bake.hip  the baked maps (include/psgsdf_bake.h), ambient occlusion (include/psgsdf_occlusion.h) and the albedo texture solved from the
 //                     keyframes (include/psgsdf_photo.h)
 //   extract_compare.hip  the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h)
+//   extract_curvature.hip  curvature per voxel, per vertex of the welded mesh and as a map of the bake (include/psgsdf_curvature.h)
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"
@@ -51,6 +52,9 @@ enum XoSlot {
     XO_PHOTO, XO_PHOTO_RGB, XO_PHOTO_NOBS, XO_PHOTO_STATUS,                // psgsdf_bake_lod_photo (everything else: psgsdf_bake_lod's slots)
     XO_CMP_VDIST, XO_CMP_VNEAREST, XO_CMP_VSIDE, XO_CMP_RDIST, XO_CMP_RNEAREST, XO_CMP_RSIDE,   // psgsdf_compare_reference (its mesh: XO_IMESH_*; with a filter also XO_COMPONENTS)
     XO_ALN_XYZ,                                                      // psgsdf_align_reference: the moved reference points (its mesh: XO_IMESH_*; with a filter also XO_COMPONENTS)
+    XO_CURV_VALID, XO_CURV_MEAN, XO_CURV_GAUSS, XO_CURV_K1, XO_CURV_K2, XO_CURV_DIR1,          // psgsdf_curvature_voxels
+    XO_VCURV_VALID, XO_VCURV_MEAN, XO_VCURV_GAUSS, XO_VCURV_K1, XO_VCURV_K2,                  // psgsdf_extract_mesh_curvature (its mesh: XO_IMESH_*)
+    XO_BAKE_CURV_MEAN, XO_BAKE_CURV_VALID,                           // psgsdf_bake_lod_curvature (everything else: psgsdf_bake_lod's slots)
     XO_COUNT
 };
 }  // namespace psge

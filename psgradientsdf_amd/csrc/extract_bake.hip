@@ -15,8 +15,8 @@ using namespace psge;
 
 // ---- the bake (kernel: bake.hip k_bake).  The clusters' device arrays are the kernel's mesh (lod_from_device hands them out: nothing is uploaded
 // again), the brick map comes from the renderer's prepare path.
-namespace {
-// what psgsdf_bake_lod, psgsdf_bake_lod_ao and psgsdf_bake_lod_photo check first
+namespace psge {
+// ---- stage 4 (mesh_stages.h)
 int bake_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach) {
     if (int rc = lod_ready(c, me, filter, cell)) return rc;
     if (res < 1) return fail(c, PSGSDF_ERR_ARG, "%s: res %d (at least 1)", me, res);
@@ -26,8 +26,8 @@ int bake_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, 
 // the bake of both calls, its results in their pinned host slots (the stream has been waited for); dev (if asked for): the kernel's arguments, the
 // atlas's device planes among them (dev->nf == 0: an empty level-of-detail mesh, nothing was baked).  max_texels (if not 0): a larger atlas is refused
 // like one beyond 16384, before it is allocated
-int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out, psg::BakeArgs* dev = nullptr,
-                long long max_texels = 0) {
+int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out, psg::BakeArgs* dev,
+                long long max_texels) {
     *out = psgsdf_bake{};
     MeshView lod;
     if (int rc = lod_stages(c, mem, me, filter, cell, LodOut{&out->xyz, &out->normals, &out->rgb, &out->n_vertices, &out->faces, &out->n_faces, &out->vertex_map,
@@ -78,7 +78,9 @@ int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_fi
     if (dev) *dev = a;
     return PSGSDF_OK;
 }
+}  // namespace psge
 
+namespace {
 // ---- ambient occlusion (kernel: occlusion.hip k_occlusion): K short rays per sample through the renderer's walk, the
 // samples either the caller's points or the texels of a bake, whose planes are still on the device when the rays start from them.
 int ao_bad_params(psgsdf_ctx* c, const char* me, const psgsdf_ao_params* p) {

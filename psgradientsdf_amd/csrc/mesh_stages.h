@@ -39,3 +39,13 @@ int lod_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, d
 // ... and the stages they run: compared_mesh, then the clusters unless it is empty (then the stream has been waited for and `o` is untouched)
 int lod_stages(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, const LodOut& o, MeshView* dev = nullptr);
 }  // namespace psge
+
+// ---- stage 4 (extract_bake.hip defines it; extract_curvature.hip goes on from it): the clusters baked
+struct psgsdf_bake;
+namespace psg { struct BakeArgs; }
+namespace psge {
+// what psgsdf_bake_lod and every call that starts with its bake check first
+int bake_ready(psgsdf_ctx* c, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach);
+int bake_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, double cell, int32_t res, double reach, psgsdf_bake* out, psg::BakeArgs* dev = nullptr,
+                long long max_texels = 0);
+}  // namespace psge

@@ -44,6 +44,7 @@
 #include "../../include/psgsdf_photo.h"
 #include "../../include/psgsdf_compare.h"
 #include "../../include/psgsdf_align.h"
+#include "../../include/psgsdf_curvature.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 #include "obj_writer.hpp"
@@ -123,6 +124,17 @@ inline bool& mesh_bake_photo() { static bool v = false; return v; }
 // voxelPS --mesh-fit: next to every <name>_mesh.ply a <name>_mesh_fit.ply, the welded mesh with the photometric fit of every vertex (psgsdf_extract_mesh_fit): how many
 // keyframes saw it, the rms residual and the mean robust loss; single process only
 inline bool& mesh_fit() { static bool v = false; return v; }
+// voxelPS --mesh-curvature: next to every <name>_mesh.ply a <name>_mesh_curvature.ply, the welded mesh with the curvature of every vertex
+// (psgsdf_extract_mesh_curvature): mean, Gaussian and the two principal curvatures, and how many of its end voxels could be evaluated; single process only
+inline bool& mesh_curvature() { static bool v = false; return v; }
+// voxelPS --mesh-bake-curvature S (with --mesh-bake): <name>_mesh_lod_curvature.png next to the other maps, 8-bit grey: the mean curvature of every hit
+// texel's voxel (psgsdf_bake_lod_curvature), mean * vs = S white, -S black, flat and every texel without a value 128; convex is bright; 0: off
+inline double& mesh_bake_curvature_scale() { static double v = 0.0; return v; }
+inline uint8_t curvature_to_u8(float mean, uint8_t valid, double vs, double S) {
+    if (!valid) return 128;
+    const double x = 0.5 + 0.5 * (double)mean * vs / S;
+    return (uint8_t)std::floor(255.0 * (!(x > 0.0) ? 0.0 : x > 1.0 ? 1.0 : x) + 0.5);
+}
 // voxelPS --compare-ply FILE [--compare-tau T] [--compare-max D]: next to every <name>_mesh.ply a <name>_compare.txt (both directions' counts, mean / rms /
 // max / signed mean, histogram, precision / recall / F) and a <name>_mesh_compare.ply (the welded mesh -- the filtered one, if a filter flag is given --
 // with every vertex's distance to the reference and the side it lies on): psgsdf_compare_reference against the mesh or cloud read from FILE, whose
@@ -285,6 +297,32 @@ inline bool write_mesh_fit_ply(const std::string& file, const float* xyz, const 
     const std::string base = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
     std::string v(nv * kPlyFitVertexBytes, '\0'); char* p = &v[0];
     for (size_t i = 0; i < nv; ++i, p += kPlyFitVertexBytes) { memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes); memcpy(p + 27, rms + i, 4); memcpy(p + 31, loss + i, 4); memcpy(p + 35, n_obs + i, 4); }
+    bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
+    return fclose(f) == 0 && ok;
+}
+// the welded mesh with the curvature of its vertices (include/psgsdf_curvature.h): the format of _mesh_indexed.ply with five more vertex properties behind
+// the colours -- float quality (the mean curvature), float gauss, float k1, float k2, uchar curvature_valid (valid end voxels) -- 44 B per vertex, and one
+// more header line with the mean of quality over the vertices with curvature_valid > 0 (in double, from the column as written) and their number.
+// `voxelPS --mesh-curvature`.
+constexpr size_t kPlyCurvatureVertexBytes = kPlyVertexBytes + 17;
+inline std::string mesh_curvature_comment(const float* mean, const uint8_t* valid, size_t nv) {
+    double q = 0.0; long long n = 0;
+    for (size_t i = 0; i < nv; ++i) if (valid[i] > 0) { q += (double)mean[i]; n += 1; }
+    char c[120];
+    snprintf(c, sizeof c, "comment curvature mean %.17g valid %lld\n", n ? q / (double)n : 0.0, n);
+    return c;
+}
+inline bool write_mesh_curvature_ply(const std::string& file, const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv, const int32_t* faces, size_t nf,
+                                     const float origin[3], float vs, const float* mean, const float* gauss, const float* k1, const float* k2, const uint8_t* valid) {
+    FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
+    const std::string h = mesh_indexed_header(nv, nf, origin, vs, mesh_curvature_comment(mean, valid, nv),
+                                              "property float quality\nproperty float gauss\nproperty float k1\nproperty float k2\nproperty uchar curvature_valid\n");
+    const std::string base = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    std::string v(nv * kPlyCurvatureVertexBytes, '\0'); char* p = &v[0];
+    for (size_t i = 0; i < nv; ++i, p += kPlyCurvatureVertexBytes) {
+        memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes);
+        memcpy(p + 27, mean + i, 4); memcpy(p + 31, gauss + i, 4); memcpy(p + 35, k1 + i, 4); memcpy(p + 39, k2 + i, 4); memcpy(p + 43, valid + i, 1);
+    }
     bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
     return fclose(f) == 0 && ok;
 }
@@ -586,6 +624,7 @@ struct VolumetricGradSdf {
         if (ctx && clean_mesh() && !device_mesh_clean(ctx, filename)) std::cout << "couldn't save the cleaned mesh of " << filename << std::endl;
         if (ctx && mesh_lod_voxels() > 0 && !device_mesh_lod(ctx, filename)) std::cout << "couldn't save the level-of-detail mesh of " << filename << std::endl;
         if (ctx && mesh_fit() && !device_mesh_fit(ctx, filename)) std::cout << "couldn't save the mesh with its fit of " << filename << std::endl;
+        if (ctx && mesh_curvature() && !device_mesh_curvature(ctx, filename)) std::cout << "couldn't save the mesh with its curvature of " << filename << std::endl;
         if (ctx && compare_ref().on && !device_mesh_compare(ctx, filename)) std::cout << "couldn't save the comparison of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
@@ -673,6 +712,7 @@ struct VolumetricGradSdf {
         psgsdf_bake bk{};      // --mesh-bake: the same level-of-detail arrays (bit for bit) and the atlas, in one call
         psgsdf_bake_ao ao{};   // --mesh-bake-ao: the same bake (bit for bit) and the occlusion map
         psgsdf_bake_photo ph{};   // --mesh-bake-photo: the same bake (bit for bit) and the albedo solved from the keyframes
+        psgsdf_bake_curvature cv{};   // --mesh-bake-curvature: the same bake (bit for bit) and the mean curvature of the hit voxels
         if (mesh_bake_res() > 0) {
             bool baked = false;
             if (mesh_bake_ao_dirs() > 0) {
@@ -685,6 +725,10 @@ struct VolumetricGradSdf {
                 const int rc = psgsdf_bake_lod_photo(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &pp, &ph);
                 if (rc == 0) { bk = ph.bake; baked = true; }
                 else if (rc != PSGSDF_ERR_STATE) return false;      // (before psgsdf_init: no keyframes yet)
+            }
+            if (mesh_bake_curvature_scale() > 0) {      // (likewise: the map in slots of its own, the bake's filled again with the same bits)
+                if (psgsdf_bake_lod_curvature(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &cv) != 0) return false;
+                bk = cv.bake; baked = true;
             }
             if (!baked && psgsdf_bake_lod(ctx, clean_mesh() ? &mesh_filter() : nullptr, cell, mesh_bake_res(), cell, &bk) != 0) return false;
             if (bk.n_faces_in == 0) return false;
@@ -723,6 +767,13 @@ struct VolumetricGradSdf {
                 std::cout << "photo albedo: " << ph.counts.n_texels_solved << " of " << ph.counts.n_samples << " texels solved from " << ph.counts.n_used << " of " << ph.counts.n_pairs
                           << " views (" << ph.counts.n_outside << " outside, " << ph.counts.n_grazing << " grazing, " << ph.counts.n_occluded << " occluded, " << ph.counts.n_dark << " dark)" << std::endl;
             }
+            const bool with_curv = cv.mean != nullptr;
+            auto cur = std::make_shared<std::vector<uint8_t>>();
+            if (with_curv) {
+                cur->resize(px);
+                for (size_t q = 0; q < px; ++q) (*cur)[q] = curvature_to_u8(cv.mean[q], cv.valid[q], (double)info.voxel_size, mesh_bake_curvature_scale());
+                std::cout << "curvature: " << cv.n_valid << " of " << bk.n_hits << " hit texels evaluated" << std::endl;
+            }
             DumpQueue::get().push([=] {
                 const std::string lod = base + "_mesh_lod";
                 bool ok = write_obj_bake(lod + ".obj", lod + ".mtl", lod + (with_photo ? "_photo.png" : "_albedo.png"), lod + "_normal.png", vx->data(), vn->data(), (size_t)nv, vf->data(), uv->data(), (size_t)nf,
@@ -731,6 +782,7 @@ struct VolumetricGradSdf {
                 ok = write_png(lod + "_normal.png", W, H, 3, nmap->data()) && ok;
                 if (with_ao) ok = write_png(lod + "_ao.png", W, H, 1, occ->data()) && ok;
                 if (with_photo) ok = write_png(lod + "_photo.png", W, H, 3, pho->data()) && ok;
+                if (with_curv) ok = write_png(lod + "_curvature.png", W, H, 1, cur->data()) && ok;
                 if (!ok) { std::cout << "couldn't save the baked level-of-detail mesh " << base << std::endl; DumpQueue::get().report_failure(); }
             });
         }
@@ -757,6 +809,29 @@ struct VolumetricGradSdf {
         DumpQueue::get().push([=] {
             if (!write_mesh_fit_ply(base + "_mesh_fit.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, fr->data(), fl->data(), fn->data())) {
                 std::cout << "couldn't save the mesh with its fit " << base << std::endl; DumpQueue::get().report_failure();
+            }
+        });
+        return true;
+    }
+    // <name>_mesh.ply -> <name>_mesh_curvature.ply (write_mesh_curvature_ply)
+    static bool device_mesh_curvature(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: welded mesh with vertex curvature (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string base = mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                 ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file;
+        const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr;
+        const uint8_t* valid = nullptr; const float *mean = nullptr, *gauss = nullptr, *k1 = nullptr, *k2 = nullptr; int64_t nv = 0, nf = 0;
+        if (psgsdf_extract_mesh_curvature(ctx, &xyz, &nrm, &rgb, &nv, &faces, &nf, &valid, &mean, &gauss, &k1, &k2) != 0 || nf == 0) return false;
+        auto vx = std::make_shared<std::vector<float>>(xyz, xyz + 3 * nv), vnr = std::make_shared<std::vector<float>>(nrm, nrm + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(rgb, rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(faces, faces + 3 * nf);
+        auto cm = std::make_shared<std::vector<float>>(mean, mean + nv), cg = std::make_shared<std::vector<float>>(gauss, gauss + nv);
+        auto c1 = std::make_shared<std::vector<float>>(k1, k1 + nv), c2 = std::make_shared<std::vector<float>>(k2, k2 + nv); auto cl = std::make_shared<std::vector<uint8_t>>(valid, valid + nv);
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            if (!write_mesh_curvature_ply(base + "_mesh_curvature.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs,
+                                          cm->data(), cg->data(), c1->data(), c2->data(), cl->data())) {
+                std::cout << "couldn't save the mesh with its curvature " << base << std::endl; DumpQueue::get().report_failure();
             }
         });
         return true;
@@ -1280,6 +1355,7 @@ public:
         if (clean_mesh() && !VolumetricGradSdf::device_mesh_clean(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the cleaned mesh " << save_path_ << filename << std::endl;
         if (mesh_lod_voxels() > 0 && !VolumetricGradSdf::device_mesh_lod(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the level-of-detail mesh " << save_path_ << filename << std::endl;
         if (mesh_fit() && !VolumetricGradSdf::device_mesh_fit(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the mesh with its fit " << save_path_ << filename << std::endl;
+        if (mesh_curvature() && !VolumetricGradSdf::device_mesh_curvature(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the mesh with its curvature " << save_path_ << filename << std::endl;
         if (compare_ref().on && !VolumetricGradSdf::device_mesh_compare(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the comparison " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");

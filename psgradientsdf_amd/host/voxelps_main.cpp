@@ -130,6 +130,20 @@ static int selftest_ply_fit(const char* path) {
     return psgsdf_host::write_mesh_fit_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, rms, loss, n_obs) ? 0 : 1;
 }
 
+// `--selftest-ply-curvature out.ply`: the same octahedron through the writer of `--mesh-curvature` (five more vertex properties, one more header line;
+// tests/test_curvature_cpu.py parses it back)
+static int selftest_ply_curvature(const char* path) {
+    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
+    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
+    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
+    const float origin[3] = {-0.25f, 0.5f, 1.0f};
+    const float mean[6] = {0.5f, -0.25f, 0.0f, 8.0f, 0.125f, -3.0f}, gauss[6] = {0.25f, 0.0625f, 0.0f, -4.0f, 0.01f, 9.0f};
+    const float k1[6] = {0.75f, -0.125f, 0.0f, 16.0f, 0.25f, -3.0f}, k2[6] = {0.25f, -0.375f, 0.0f, -0.25f, 0.04f, -3.0f};
+    const uint8_t valid[6] = {2, 1, 0, 2, 1, 2};
+    return psgsdf_host::write_mesh_curvature_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, mean, gauss, k1, k2, valid) ? 0 : 1;
+}
+
 // `--selftest-ply-compare out.ply`: the same octahedron through the writer of `--compare-ply` (two more vertex properties, one more header line;
 // tests/test_compare_cpu.py parses it back) and back through the reader of `--compare-ply`, which has to skip what it does not want by the
 // declared sizes: 0 iff the positions and faces it returns are the ones written
@@ -323,6 +337,7 @@ int main(int argc, char* argv[]) {
     if (argc >= 4 && std::string(argv[1]) == "--selftest-mc-ply") return selftest_mc_ply(atoi(argv[2]), argv[3]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-fit") return selftest_ply_fit(argv[2]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-curvature") return selftest_ply_curvature(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-obj-bake") return selftest_obj_bake(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-compare") return selftest_ply_compare(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
@@ -331,6 +346,7 @@ int main(int argc, char* argv[]) {
     bool lod_flag = false, lod_ok = true;     // --mesh-lod S given / S is a number > 0
     bool bake_flag = false, bake_ok = true;   // --mesh-bake R given / R is a whole number >= 1
     bool ao_flag = false, ao_ok = true;       // --mesh-bake-ao K given / K is 8, 16, 32 or 64
+    bool curv_flag = false, curv_ok = true;   // --mesh-bake-curvature S given / S is a finite number > 0
     std::string cmp_file, cmp_bad;            // --compare-ply FILE given / the --compare-* flag whose number is bad
     bool cmp_tau_flag = false, cmp_max_flag = false, cmp_iters_flag = false, cmp_bad_iters = false;
     std::string relight_file;                 // --relight FILE: every keyframe under the lights of FILE (relight/*.png, relight_report.txt; include/psgsdf_relight.h)
@@ -348,6 +364,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-bake-ao" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); ao_ok = end != argv[i] && *end == 0 && (v == 8 || v == 16 || v == 32 || v == 64); mesh_bake_ao_dirs() = ao_ok ? (int)v : 0; ao_flag = true; }      // with --mesh-bake: <name>_mesh_lod_ao.png and a map_Ka line in the .mtl: ambient occlusion of the reconstructed surface, K rays per texel (include/psgsdf_occlusion.h)
         else if (a == "--mesh-bake-photo") mesh_bake_photo() = true;      // with --mesh-bake: <name>_mesh_lod_photo.png, the albedo of every texel solved from the keyframes that see it, and map_Kd in the .mtl names it (include/psgsdf_photo.h); a dump taken before the optimiser holds the keyframes is baked as without the flag
         else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
+        else if (a == "--mesh-curvature") mesh_curvature() = true;      // <name>_mesh_curvature.ply next to every <name>_mesh.ply: the welded mesh with every vertex's mean, Gaussian and principal curvatures (include/psgsdf_curvature.h)
+        else if (a == "--mesh-bake-curvature" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); curv_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_bake_curvature_scale() = curv_ok ? v : 0.0; curv_flag = true; }      // with --mesh-bake: <name>_mesh_lod_curvature.png, the mean curvature of every texel's voxel in grey, convex bright; S: the curvature times the voxel size that maps to white
         else if (a == "--compare-ply" && i + 1 < argc) cmp_file = argv[++i];      // <name>_compare.txt and <name>_mesh_compare.ply next to every <name>_mesh.ply: distances between the welded mesh and the mesh or cloud in FILE, precision / recall / F (include/psgsdf_compare.h)
         else if ((a == "--compare-tau" || a == "--compare-max") && i + 1 < argc) {      // the threshold of precision / recall and the matching radius, in voxels (defaults 1 and 8)
             char* end = nullptr; const double v = strtod(argv[++i], &end);
@@ -370,6 +388,10 @@ int main(int argc, char* argv[]) {
     if ((want_ranks > 1 || multi_rank()) && ao_flag) { std::cerr << "--mesh-bake-ao needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (mesh_bake_photo() && !bake_flag) { std::cerr << "--mesh-bake-photo needs --mesh-bake R: the photo map is one more map of the bake" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && mesh_bake_photo()) { std::cerr << "--mesh-bake-photo needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if (curv_flag && !curv_ok) { std::cerr << "--mesh-bake-curvature: the mean curvature times the voxel size that maps to white, a finite number > 0" << std::endl; return 1; }
+    if (curv_flag && !bake_flag) { std::cerr << "--mesh-bake-curvature needs --mesh-bake R: the curvature is one more map of the bake" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && curv_flag) { std::cerr << "--mesh-bake-curvature needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && mesh_curvature()) { std::cerr << "--mesh-curvature needs a single process: a slab holds only its own planes of the volume (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
     if (bake_flag && !bake_ok) { std::cerr << "--mesh-bake: texels along a triangle's edge, a whole number >= 1" << std::endl; return 1; }
     if (bake_flag && !lod_flag) { std::cerr << "--mesh-bake needs --mesh-lod S: the maps are baked onto the level-of-detail mesh" << std::endl; return 1; }
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }
