@@ -696,6 +696,34 @@ class Api:
         out["n_valid"] = int(b.n_valid)
         return out
 
+    # -- unobserved voxels filled, and the closed mesh of the filled state (include/psgsdf_fill.h)
+    def fill_voxels(self, rounds, sweeps=4):
+        """The unobserved voxels within `rounds` city-block steps of an observed one, filled by front propagation of the first-order model
+        d + g . dx and relaxed by `sweeps` Jacobi sweeps (psgsdf_fill_voxels): dict of lin [n] int64 (ascending), dist [n], grad [n, 3], rgb [n, 3]
+        float32 and round [n] uint8 (the round a voxel was reached in, 1 .. rounds).  The context's state does not change.  Single contexts only."""
+        lin = C.POINTER(C.c_int64)(); ptr = [C.POINTER(C.c_float)() for _ in range(3)]; rnd = C.POINTER(C.c_uint8)(); n = C.c_int64()
+        self._check(self._fn("fill_voxels")(self.ctx, C.c_int32(int(rounds)), C.c_int32(int(sweeps)), C.byref(lin), *[C.byref(p) for p in ptr], C.byref(rnd), C.byref(n)), "fill_voxels")
+        n = n.value
+        col = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if n else np.zeros(shape, dt)
+        return dict(lin=col(lin, (n,), np.int64), dist=col(ptr[0], (n,), np.float32), grad=col(ptr[1], (n, 3), np.float32), rgb=col(ptr[2], (n, 3), np.float32),
+                    round=col(rnd, (n,), np.uint8))
+
+    def extract_mesh_filled(self, rounds, sweeps=4, min_faces=0, min_area=0.0, keep_largest=0):
+        """extract_mesh_components' dict for the state with its unobserved voxels filled as fill_voxels(rounds, sweeps) fills them
+        (psgsdf_extract_mesh_filled), plus vertex_filled [V] uint8: how many of the vertex's end voxels are filled, 0, 1 or 2.  rounds = 0 gives
+        extract_mesh_components' arrays bit for bit.  Single contexts only."""
+        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
+        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)(); vc = C.POINTER(C.c_int32)(); vf = C.POINTER(C.c_uint8)()
+        comps = C.c_void_p(); nv, nf, nc = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_filled")(self.ctx, C.c_int32(int(rounds)), C.c_int32(int(sweeps)), C.byref(flt) if flt is not None else None, C.byref(xyz), C.byref(nrm),
+                                                    C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(vc), C.byref(comps), C.byref(nc), C.byref(vf)), "extract_mesh_filled")
+        V, F, K = nv.value, nf.value, nc.value
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        table = np.frombuffer(C.string_at(comps, K * MESH_COMPONENT_DTYPE.itemsize), MESH_COMPONENT_DTYPE).copy() if K else np.zeros(0, MESH_COMPONENT_DTYPE)
+        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
+                    vertex_component=np.ctypeslib.as_array(vc, shape=(V,)).copy() if V else np.zeros(0, np.int32), components=table,
+                    vertex_filled=np.ctypeslib.as_array(vf, shape=(V,)).copy() if V else np.zeros(0, np.uint8))
+
     # -- the albedo texture solved from the keyframes (include/psgsdf_photo.h)
     def bake_lod_photo(self, cell, res, reach=None, bias=None, cos_min=0.2, shade_min=0.05, status=False, min_faces=0, min_area=0.0, keep_largest=0):
         """bake_lod's dict for the same arguments (bit for bit) plus the albedo of every texel solved from the keyframes that see it

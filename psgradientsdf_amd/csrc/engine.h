@@ -338,6 +338,7 @@ struct WMeshGrid {
     int zc0;                     // first cell plane of this context (cropped) = kp0, the cropped plane of key slot plane 0
     long long nown;              // key slots of the planes this context owns: [0, nown); [nown, nown + 4 d0 d1) is the plane above
     float voxel[3], origin[3];   // psgsdf_extract_mesh's vertex frame
+    int poff[3];                 // added to a crop voxel's index before the frame is applied: 0 unless the frame is another box's (extract_fill.hip)
 };
 // counts of kept faces per cell (cnt[ncell]) and used-key flags (1) in flag (zeroed first)
 void launch_wmesh_mark(const WMeshGrid& g, long long ncell, int* cnt, int* flag, hipStream_t s);

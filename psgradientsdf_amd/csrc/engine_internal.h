@@ -11,6 +11,7 @@
 //                     keyframes (include/psgsdf_photo.h)
 //   extract_compare.hip  the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h)
 //   extract_curvature.hip  curvature per voxel, per vertex of the welded mesh and as a map of the bake (include/psgsdf_curvature.h)
+//   extract_fill.hip  unobserved voxels filled from their neighbours, and the welded mesh and components of the filled state (include/psgsdf_fill.h)
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"
@@ -55,6 +56,8 @@ enum XoSlot {
     XO_CURV_VALID, XO_CURV_MEAN, XO_CURV_GAUSS, XO_CURV_K1, XO_CURV_K2, XO_CURV_DIR1,          // psgsdf_curvature_voxels
     XO_VCURV_VALID, XO_VCURV_MEAN, XO_VCURV_GAUSS, XO_VCURV_K1, XO_VCURV_K2,                  // psgsdf_extract_mesh_curvature (its mesh: XO_IMESH_*)
     XO_BAKE_CURV_MEAN, XO_BAKE_CURV_VALID,                           // psgsdf_bake_lod_curvature (everything else: psgsdf_bake_lod's slots)
+    XO_FILL_LIN, XO_FILL_DIST, XO_FILL_GRAD, XO_FILL_RGB, XO_FILL_ROUND,   // psgsdf_fill_voxels
+    XO_FILL_VERTEX,                                                  // psgsdf_extract_mesh_filled (everything else: psgsdf_extract_mesh_components' slots)
     XO_COUNT
 };
 }  // namespace psge

@@ -263,10 +263,10 @@ int download(psgsdf_ctx* c, const char* me, const std::vector<XoCopy>& list) {
     for (const XoCopy& e : list) if (e.bytes) memcpy(e.out, &h[e.slot], sizeof(void*));
     return 0;
 }
-int crop_box_dev(psgsdf_ctx* c, int lo[3], int hi[3], bool* any) {
+int crop_box_dev(psgsdf_ctx* c, int lo[3], int hi[3], bool* any, const float* dist) {
     // (a slab looks at the planes it OWNS: [z0, z1) of the volume = local planes [z0 - zlo, z1 - zlo))
     const long long plane = (long long)c->grid.dim[0] * c->grid.dim[1], n = plane * (c->z1 - c->z0);
-    const float* dist0 = c->dense.dist + plane * (c->z0 - c->zlo);
+    const float* dist0 = (dist ? dist : c->dense.dist) + plane * (c->z0 - c->zlo);
     const int nblk = (int)std::max<long long>(1, std::min<long long>((n + kBlock - 1) / kBlock, 2048));
     int box[6];
     {

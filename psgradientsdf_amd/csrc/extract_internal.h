@@ -13,8 +13,13 @@ namespace psge {
 int scan_counts(psgsdf_ctx* c, int* v, long long n, int* sums, int* total_host);
 // engine-owned pinned host buffer that lives until the next extraction on this context
 int host_out(psgsdf_ctx* c, XoSlot slot, size_t bytes, void** p);
-// the crop box of |d| <= sqrt(3) vs; any = false if no voxel qualifies (collective on a multi-rank context; waits for the stream)
-int crop_box_dev(psgsdf_ctx* c, int lo[3], int hi[3], bool* any);
+// the eight float planes a mesh is made from, where a call puts its own in the place of the context's (extract_fill.hip: the filled state).  Every
+// stage that takes a `const PlaneView*` reads c->dense for nullptr; a view is in the layout of c->dense and of a single-rank context.  framed: the
+// vertices are placed in the frame of the box [flo, flo + fd) instead of the view's own crop box (the cells, keys and faces are the view's own)
+struct PlaneView { const float* dist; const float* g[3]; const float* weight; const float* rho[3]; bool framed = false; int flo[3] = {0, 0, 0}, fd[3] = {0, 0, 0}; };
+// the crop box of |d| <= sqrt(3) vs; any = false if no voxel qualifies (collective on a multi-rank context; waits for the stream); dist: the plane
+// looked at, the context's if nullptr
+int crop_box_dev(psgsdf_ctx* c, int lo[3], int hi[3], bool* any, const float* dist = nullptr);
 // state checks of every extraction call, pending work flushed, the band's state scattered into the dense arrays
 int extract_ready(psgsdf_ctx* c, const char* what);
 // the calls that are not collective refuse a multi-rank context, `why` behind the colon.  A call checks this before anything collective and before
@@ -39,14 +44,15 @@ int download(psgsdf_ctx* c, const char* me, const std::vector<XoCopy>& list);
 
 // the frame of the crop box [lo, hi] both meshes are built in (McGrid / WMeshGrid): the dense planes, the box, the voxel size and origin of
 // MarchingCubes as write_mesh sets them up (host/ps_optimizer.hpp, operation for operation: the meshes are compared bit for bit) and this
-// context's cell planes [g.zc0, *zc1): the cells whose lower plane it owns.  false: the box has no cell (computeIsoSurface runs to dim - 2)
-template <class Grid> bool crop_frame(const psgsdf_ctx* c, const int lo[3], const int hi[3], Grid& g, int* zc1) {
+// context's cell planes [g.zc0, *zc1): the cells whose lower plane it owns.  false: the box has no cell (computeIsoSurface runs to dim - 2).
+// pv: the planes the frame points at instead of the context's
+template <class Grid> bool crop_frame(const psgsdf_ctx* c, const int lo[3], const int hi[3], Grid& g, int* zc1, const PlaneView* pv = nullptr) {
 #pragma clang fp contract(off)
-    g.dist = c->dense.dist; g.weight = c->dense.weight;
+    g.dist = pv ? pv->dist : c->dense.dist; g.weight = pv ? pv->weight : c->dense.weight;
     g.nx = c->grid.dim[0]; g.ny = c->grid.dim[1]; g.zlo = c->zlo;
     const float vs = c->grid.vs;
     for (int a = 0; a < 3; ++a) {
-        g.rho[a] = c->dense.rho[a];
+        g.rho[a] = pv ? pv->rho[a] : c->dense.rho[a];
         g.lo[a] = lo[a]; g.d[a] = hi[a] - lo[a] + 1;
         const float size = vs * g.d[a];                    // write_mesh: size[] = {vs * d[0], ..}, org[] = {-vs * lo[0], ..}
         g.voxel[a] = size / g.d[a];                        // MarchingCubes ctor: voxel_ = size / dim

@@ -12,14 +12,21 @@ using namespace psge;
 
 namespace psge {
 // ---- stage 1 (mesh_stages.h)
-int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m) {
+int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m, const PlaneView* pv) {
     const char* me = "extract_mesh_indexed";
     int lo[3], hi[3]; bool any = false;
-    { int rc = crop_box_dev(c, lo, hi, &any); if (rc) return rc; }      // (collective: every rank takes the same early returns below)
+    { int rc = crop_box_dev(c, lo, hi, &any, pv ? pv->dist : nullptr); if (rc) return rc; }      // (collective: every rank takes the same early returns below)
     if (!any) return PSGSDF_OK;
     psg::WMeshGrid g{}; int zc1 = 0;
-    if (!crop_frame(c, lo, hi, g, &zc1)) return PSGSDF_OK;      // psgsdf_extract_mesh's frame
-    for (int a = 0; a < 3; ++a) g.g[a] = c->dense.g[a];
+    if (!crop_frame(c, lo, hi, g, &zc1, pv)) return PSGSDF_OK;      // psgsdf_extract_mesh's frame
+    for (int a = 0; a < 3; ++a) g.g[a] = pv ? pv->g[a] : c->dense.g[a];
+    if (pv && pv->framed) {      // another box's frame, crop_frame's arithmetic on that box: a voxel has the position it has in a mesh of that box
+        const float vs = c->grid.vs;
+        for (int a = 0; a < 3; ++a) {
+            const float size = vs * pv->fd[a];
+            g.voxel[a] = size / pv->fd[a]; g.origin[a] = -vs * pv->flo[a]; g.poff[a] = lo[a] - pv->flo[a];
+        }
+    }
     g.zh = -1;
     const long long P = 4ll * g.d[0] * g.d[1];      // key slots per plane
     if (P * (g.d[2] + 1) >= (1ll << 31)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%s: %lld key slots", me, P * (g.d[2] + 1));
@@ -97,9 +104,9 @@ int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m) {
 }
 // ---- stage 2 (mesh_stages.h)
 bool bad_filter(const psgsdf_mesh_filter& flt) { return flt.min_area != flt.min_area || flt.keep_largest < 0; }
-int mcomp_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter& flt, MCompDev* d) {
+int mcomp_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter& flt, MCompDev* d, const PlaneView* pv) {
     WMeshDev m;
-    if (int rc = wmesh_device(c, mem, &m)) return rc;
+    if (int rc = wmesh_device(c, mem, &m, pv)) return rc;
     const int nv = m.nv, nf = m.nf;
     if (nv == 0 || nf == 0) return hipStreamSynchronize(c->stream) != hipSuccess ? fail(c, PSGSDF_ERR_DEVICE, "%s: kernels", me) : PSGSDF_OK;      // (every vertex belongs to a face: both or neither)
     // temporaries: 3 ints per vertex (parent, root flag / component number, component of the vertex), the edge table (6 slots of 12 B per face),
@@ -152,7 +159,7 @@ int mcomp_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_f
     }
     int n_kept = 0;
     for (int i = 0; i < nc; ++i) n_kept += list[i].kept;
-    static_cast<MeshView&>(*d) = m; d->vertex_component = vcomp; d->nc = nc; d->list = list;
+    static_cast<MeshView&>(*d) = m; d->vertex_component = vcomp; d->nc = nc; d->list = list; d->welded = m;
     if (n_kept == nc) return PSGSDF_OK;      // everything kept: the arrays as they are
     std::vector<int> hk((size_t)nc);
     for (int i = 0; i < nc; ++i) hk[(size_t)i] = list[i].kept;
@@ -167,7 +174,7 @@ int mcomp_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_f
         if (!mem.get(&o_xyz, 3 * (size_t)ov) || !mem.get(&o_nrm, 3 * (size_t)ov) || !mem.get(&o_rgb, 3 * (size_t)ov) || !mem.get(&o_vcomp, (size_t)ov) || !mem.get(&o_faces, 3 * (size_t)of)) return oom();
         timed(c, "mcomp_compact", [&] { psg::launch_mcomp_compact(d_kept, vcomp, nv, m.faces, nf, vflag, fflag, m.xyz, m.nrm, m.rgb, o_xyz, o_nrm, o_rgb, o_vcomp, o_faces, c->stream); });
     }
-    d->xyz = o_xyz; d->nrm = o_nrm; d->rgb = o_rgb; d->faces = o_faces; d->vertex_component = o_vcomp; d->nv = ov; d->nf = of;
+    d->xyz = o_xyz; d->nrm = o_nrm; d->rgb = o_rgb; d->faces = o_faces; d->vertex_component = o_vcomp; d->nv = ov; d->nf = of; d->vkeep = vflag;
     return PSGSDF_OK;
 }
 int compared_mesh(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter* filter, MeshView* mv) {

@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(kBlock) k_wmesh_verts(WMeshGrid g, const int* 
     float pl[3], gl[3], cl[3];
     const long long dl = wlin(g, i, j, k);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) pl[a] = p[a] * g.voxel[a] - g.origin[a];      // voxelToWorld, as extract.hip mc_cell
+    for (int a = 0; a < 3; ++a) pl[a] = (p[a] + g.poff[a]) * g.voxel[a] - g.origin[a];      // voxelToWorld, as extract.hip mc_cell
     unit_grad(g.g, dl, gl);
     for (int a = 0; a < 3; ++a) cl[a] = g.rho[a][dl];
     float pos[3], n[3], col[3];
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(kBlock) k_wmesh_verts(WMeshGrid g, const int* 
     } else {
         const int ph[3] = {i + (type == 0), j + (type == 1), k + (type == 2)};
         float phf[3], gh[3], ch[3];
-        for (int a = 0; a < 3; ++a) phf[a] = ph[a] * g.voxel[a] - g.origin[a];
+        for (int a = 0; a < 3; ++a) phf[a] = (ph[a] + g.poff[a]) * g.voxel[a] - g.origin[a];
         const long long dh = wlin(g, ph[0], ph[1], ph[2]);
         if (ph[2] + g.lo[2] == g.zh) {      // the upper end in the plane above this slab: gradient and albedo from the exchanged plane
             const long long hq = (long long)(ph[1] + g.lo[1]) * g.nx + (ph[0] + g.lo[0]);

@@ -11,14 +11,16 @@ struct MeshView { const float *xyz = nullptr, *nrm = nullptr; const unsigned cha
 
 // ---- stage 1: the welded mesh of the context's state (this rank's share; collective on a multi-rank context).  nv == 0 && nf == 0: nothing was
 // launched for it.  grid, num: the key slots and their vertex numbers (the scan of the used-key flags)
+// pv (single-rank contexts only): the planes the mesh is made from instead of the context's
 struct WMeshDev : MeshView { long long first = 0; psg::WMeshGrid grid{}; const int* num = nullptr; };
-int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m);
+int wmesh_device(psgsdf_ctx* c, DevMem& mem, WMeshDev* m, const PlaneView* pv = nullptr);
 
 // ---- stage 2: the components of the welded mesh and the mesh without the ones the filter drops (the welded arrays themselves if all are kept); the
-// component list is written to its pinned host slot.  nc == 0: an empty mesh, the stream has been waited for
-struct MCompDev : MeshView { const int* vertex_component = nullptr; int nc = 0; psgsdf_mesh_component* list = nullptr; };
+// component list is written to its pinned host slot.  nc == 0: an empty mesh, the stream has been waited for.  welded: the stage-1 mesh it came
+// from; vkeep: the exclusive scan of the kept flags of the welded vertices (their numbers in this mesh), nullptr if all are kept
+struct MCompDev : MeshView { const int* vertex_component = nullptr; int nc = 0; psgsdf_mesh_component* list = nullptr; WMeshDev welded; const int* vkeep = nullptr; };
 bool bad_filter(const psgsdf_mesh_filter& flt);
-int mcomp_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter& flt, MCompDev* d);
+int mcomp_device(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_mesh_filter& flt, MCompDev* d, const PlaneView* pv = nullptr);
 
 // the mesh a call goes on from: the welded mesh as it is (no filter: no component pass) or its kept components; an empty view for an empty mesh or a
 // filter that drops everything

@@ -45,6 +45,7 @@
 #include "../../include/psgsdf_compare.h"
 #include "../../include/psgsdf_align.h"
 #include "../../include/psgsdf_curvature.h"
+#include "../../include/psgsdf_fill.h"
 #include "marching_cubes.hpp"
 #include "png_writer.hpp"
 #include "obj_writer.hpp"
@@ -135,6 +136,11 @@ inline uint8_t curvature_to_u8(float mean, uint8_t valid, double vs, double S) {
     const double x = 0.5 + 0.5 * (double)mean * vs / S;
     return (uint8_t)std::floor(255.0 * (!(x > 0.0) ? 0.0 : x > 1.0 ? 1.0 : x) + 0.5);
 }
+// voxelPS --mesh-fill R [--mesh-fill-sweeps K]: next to every <name>_mesh.ply a <name>_mesh_filled.ply, the welded mesh of the state with its unobserved
+// voxels filled over R rounds and K relaxation sweeps (psgsdf_extract_mesh_filled; the filter flags apply to it) and how many of every vertex's end
+// voxels are filled; -1: off; single process only
+inline int& mesh_fill_rounds() { static int v = -1; return v; }
+inline int& mesh_fill_sweeps() { static int v = 4; return v; }
 // voxelPS --compare-ply FILE [--compare-tau T] [--compare-max D]: next to every <name>_mesh.ply a <name>_compare.txt (both directions' counts, mean / rms /
 // max / signed mean, histogram, precision / recall / F) and a <name>_mesh_compare.ply (the welded mesh -- the filtered one, if a filter flag is given --
 // with every vertex's distance to the reference and the side it lies on): psgsdf_compare_reference against the mesh or cloud read from FILE, whose
@@ -323,6 +329,25 @@ inline bool write_mesh_curvature_ply(const std::string& file, const float* xyz, 
         memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes);
         memcpy(p + 27, mean + i, 4); memcpy(p + 31, gauss + i, 4); memcpy(p + 35, k1 + i, 4); memcpy(p + 39, k2 + i, 4); memcpy(p + 43, valid + i, 1);
     }
+    bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
+    return fclose(f) == 0 && ok;
+}
+// the welded mesh of the filled state (include/psgsdf_fill.h): the format of _mesh_indexed.ply with one more vertex property behind the colours -- uchar
+// filled (filled end voxels: 0, 1 or 2) -- 28 B per vertex, and one more header line: the rounds, the sweeps, the voxels filled and the boundary edges of
+// the kept components without and with the filling.  `voxelPS --mesh-fill`.
+constexpr size_t kPlyFilledVertexBytes = kPlyVertexBytes + 1;
+inline std::string mesh_filled_comment(int rounds, int sweeps, long long voxels, long long boundary_before, long long boundary_after) {
+    char c[200];
+    snprintf(c, sizeof c, "comment fill rounds %d sweeps %d voxels %lld boundary_edges %lld %lld\n", rounds, sweeps, voxels, boundary_before, boundary_after);
+    return c;
+}
+inline bool write_mesh_filled_ply(const std::string& file, const float* xyz, const float* nrm, const uint8_t* rgb, size_t nv, const int32_t* faces, size_t nf,
+                                  const float origin[3], float vs, const uint8_t* filled, const std::string& comment) {
+    FILE* f = fopen(file.c_str(), "wb"); if (!f) return false;
+    const std::string h = mesh_indexed_header(nv, nf, origin, vs, comment, "property uchar filled\n");
+    const std::string base = mesh_indexed_vertices(xyz, nrm, rgb, nv), q = mesh_indexed_faces(faces, nf);
+    std::string v(nv * kPlyFilledVertexBytes, '\0'); char* p = &v[0];
+    for (size_t i = 0; i < nv; ++i, p += kPlyFilledVertexBytes) { memcpy(p, base.data() + i * kPlyVertexBytes, kPlyVertexBytes); memcpy(p + 27, filled + i, 1); }
     bool ok = fwrite(h.data(), 1, h.size(), f) == h.size() && fwrite(v.data(), 1, v.size(), f) == v.size() && fwrite(q.data(), 1, q.size(), f) == q.size();
     return fclose(f) == 0 && ok;
 }
@@ -625,6 +650,7 @@ struct VolumetricGradSdf {
         if (ctx && mesh_lod_voxels() > 0 && !device_mesh_lod(ctx, filename)) std::cout << "couldn't save the level-of-detail mesh of " << filename << std::endl;
         if (ctx && mesh_fit() && !device_mesh_fit(ctx, filename)) std::cout << "couldn't save the mesh with its fit of " << filename << std::endl;
         if (ctx && mesh_curvature() && !device_mesh_curvature(ctx, filename)) std::cout << "couldn't save the mesh with its curvature of " << filename << std::endl;
+        if (ctx && mesh_fill_rounds() >= 0 && !device_mesh_filled(ctx, filename)) std::cout << "couldn't save the filled mesh of " << filename << std::endl;
         if (ctx && compare_ref().on && !device_mesh_compare(ctx, filename)) std::cout << "couldn't save the comparison of " << filename << std::endl;
         if (ctx && !host_writers()) return device_mesh(ctx, filename);
         return sync_host() && write_mesh(filename, grid_dim_, voxel_size_, dist, weight, rgb);
@@ -832,6 +858,36 @@ struct VolumetricGradSdf {
             if (!write_mesh_curvature_ply(base + "_mesh_curvature.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs,
                                           cm->data(), cg->data(), c1->data(), c2->data(), cl->data())) {
                 std::cout << "couldn't save the mesh with its curvature " << base << std::endl; DumpQueue::get().report_failure();
+            }
+        });
+        return true;
+    }
+    // <name>_mesh.ply -> <name>_mesh_filled.ply (write_mesh_filled_ply): three calls -- the components of the state as it is (for the boundary edges the
+    // filling starts from), the filled voxels (for their number), the mesh of the filled state
+    static bool device_mesh_filled(psgsdf_ctx* ctx, const std::string& mesh_file) {
+        PSG_STAGE("dump: welded mesh of the filled state (device) + binary PLY");
+        const std::string tail = "_mesh.ply";
+        const std::string base = mesh_file.size() >= tail.size() && mesh_file.compare(mesh_file.size() - tail.size(), tail.size(), tail) == 0
+                                 ? mesh_file.substr(0, mesh_file.size() - tail.size()) : mesh_file;
+        const int R = mesh_fill_rounds(), K = mesh_fill_sweeps();
+        const psgsdf_mesh_filter* flt = clean_mesh() ? &mesh_filter() : nullptr;
+        const float* xyz = nullptr; const float* nrm = nullptr; const uint8_t* rgb = nullptr; const int32_t* faces = nullptr; const int32_t* vcomp = nullptr;
+        const psgsdf_mesh_component* comps = nullptr; const uint8_t* filled = nullptr; int64_t nv = 0, nf = 0, nc = 0;
+        auto boundary = [&] { long long b = 0; for (int64_t i = 0; i < nc; ++i) if (comps[i].kept) b += comps[i].n_boundary_edges; return b; };
+        if (psgsdf_extract_mesh_components(ctx, flt, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vcomp, &comps, &nc) != 0) return false;
+        const long long before = boundary();
+        const int64_t* lin = nullptr; const float *fd = nullptr, *fg = nullptr, *fc = nullptr; const uint8_t* fr = nullptr; int64_t n_filled = 0;
+        if (psgsdf_fill_voxels(ctx, R, K, &lin, &fd, &fg, &fc, &fr, &n_filled) != 0) return false;
+        if (psgsdf_extract_mesh_filled(ctx, R, K, flt, &xyz, &nrm, &rgb, &nv, &faces, &nf, &vcomp, &comps, &nc, &filled) != 0 || nf == 0) return false;
+        const std::string comment = mesh_filled_comment(R, K, (long long)n_filled, before, boundary());
+        auto vx = std::make_shared<std::vector<float>>(xyz, xyz + 3 * nv), vnr = std::make_shared<std::vector<float>>(nrm, nrm + 3 * nv);
+        auto vc = std::make_shared<std::vector<uint8_t>>(rgb, rgb + 3 * nv); auto vf = std::make_shared<std::vector<int32_t>>(faces, faces + 3 * nf);
+        auto fl = std::make_shared<std::vector<uint8_t>>(filled, filled + nv);
+        psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+        const std::array<float, 3> org = {info.origin[0], info.origin[1], info.origin[2]}; const float vs = info.voxel_size;
+        DumpQueue::get().push([=] {
+            if (!write_mesh_filled_ply(base + "_mesh_filled.ply", vx->data(), vnr->data(), vc->data(), (size_t)nv, vf->data(), (size_t)nf, org.data(), vs, fl->data(), comment)) {
+                std::cout << "couldn't save the filled mesh " << base << std::endl; DumpQueue::get().report_failure();
             }
         });
         return true;
@@ -1356,6 +1412,7 @@ public:
         if (mesh_lod_voxels() > 0 && !VolumetricGradSdf::device_mesh_lod(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the level-of-detail mesh " << save_path_ << filename << std::endl;
         if (mesh_fit() && !VolumetricGradSdf::device_mesh_fit(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the mesh with its fit " << save_path_ << filename << std::endl;
         if (mesh_curvature() && !VolumetricGradSdf::device_mesh_curvature(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the mesh with its curvature " << save_path_ << filename << std::endl;
+        if (mesh_fill_rounds() >= 0 && !VolumetricGradSdf::device_mesh_filled(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the filled mesh " << save_path_ << filename << std::endl;
         if (compare_ref().on && !VolumetricGradSdf::device_mesh_compare(ctx_, save_path_ + filename + "_mesh.ply")) std::cout << "couldn't save the comparison " << save_path_ << filename << std::endl;
         if (!host_writers()) {
             const bool ok = VolumetricGradSdf::device_mesh(ctx_, save_path_ + filename + "_mesh.ply");

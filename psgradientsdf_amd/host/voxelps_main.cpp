@@ -347,6 +347,7 @@ int main(int argc, char* argv[]) {
     bool bake_flag = false, bake_ok = true;   // --mesh-bake R given / R is a whole number >= 1
     bool ao_flag = false, ao_ok = true;       // --mesh-bake-ao K given / K is 8, 16, 32 or 64
     bool curv_flag = false, curv_ok = true;   // --mesh-bake-curvature S given / S is a finite number > 0
+    bool fill_flag = false, fill_ok = true, fillk_flag = false, fillk_ok = true;   // --mesh-fill R given / R is a whole number in 0 .. 255; --mesh-fill-sweeps K given / K is a whole number in 0 .. 4096
     std::string cmp_file, cmp_bad;            // --compare-ply FILE given / the --compare-* flag whose number is bad
     bool cmp_tau_flag = false, cmp_max_flag = false, cmp_iters_flag = false, cmp_bad_iters = false;
     std::string relight_file;                 // --relight FILE: every keyframe under the lights of FILE (relight/*.png, relight_report.txt; include/psgsdf_relight.h)
@@ -366,6 +367,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
         else if (a == "--mesh-curvature") mesh_curvature() = true;      // <name>_mesh_curvature.ply next to every <name>_mesh.ply: the welded mesh with every vertex's mean, Gaussian and principal curvatures (include/psgsdf_curvature.h)
         else if (a == "--mesh-bake-curvature" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); curv_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_bake_curvature_scale() = curv_ok ? v : 0.0; curv_flag = true; }      // with --mesh-bake: <name>_mesh_lod_curvature.png, the mean curvature of every texel's voxel in grey, convex bright; S: the curvature times the voxel size that maps to white
+        else if (a == "--mesh-fill" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); fill_ok = end != argv[i] && *end == 0 && v >= 0 && v <= PSGSDF_FILL_MAX_ROUNDS; mesh_fill_rounds() = fill_ok ? (int)v : -1; fill_flag = true; }      // <name>_mesh_filled.ply next to every <name>_mesh.ply: the welded mesh of the state with its unobserved voxels filled over R front rounds, holes up to about 2 R voxels wide closed (include/psgsdf_fill.h)
+        else if (a == "--mesh-fill-sweeps" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); fillk_ok = end != argv[i] && *end == 0 && v >= 0 && v <= PSGSDF_FILL_MAX_SWEEPS; if (fillk_ok) mesh_fill_sweeps() = (int)v; fillk_flag = true; }      // with --mesh-fill: the relaxation sweeps over the filled voxels (default 4)
         else if (a == "--compare-ply" && i + 1 < argc) cmp_file = argv[++i];      // <name>_compare.txt and <name>_mesh_compare.ply next to every <name>_mesh.ply: distances between the welded mesh and the mesh or cloud in FILE, precision / recall / F (include/psgsdf_compare.h)
         else if ((a == "--compare-tau" || a == "--compare-max") && i + 1 < argc) {      // the threshold of precision / recall and the matching radius, in voxels (defaults 1 and 8)
             char* end = nullptr; const double v = strtod(argv[++i], &end);
@@ -392,6 +395,10 @@ int main(int argc, char* argv[]) {
     if (curv_flag && !bake_flag) { std::cerr << "--mesh-bake-curvature needs --mesh-bake R: the curvature is one more map of the bake" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && curv_flag) { std::cerr << "--mesh-bake-curvature needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && mesh_curvature()) { std::cerr << "--mesh-curvature needs a single process: a slab holds only its own planes of the volume (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
+    if (fill_flag && !fill_ok) { std::cerr << "--mesh-fill: the front rounds, a whole number in 0 .. " << PSGSDF_FILL_MAX_ROUNDS << std::endl; return 1; }
+    if (fillk_flag && !fillk_ok) { std::cerr << "--mesh-fill-sweeps: the relaxation sweeps, a whole number in 0 .. " << PSGSDF_FILL_MAX_SWEEPS << std::endl; return 1; }
+    if (fillk_flag && !fill_flag) { std::cerr << "--mesh-fill-sweeps needs --mesh-fill R: the sweeps relax the voxels it fills" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && fill_flag) { std::cerr << "--mesh-fill needs a single process: a slab holds only its own planes of the volume (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
     if (bake_flag && !bake_ok) { std::cerr << "--mesh-bake: texels along a triangle's edge, a whole number >= 1" << std::endl; return 1; }
     if (bake_flag && !lod_flag) { std::cerr << "--mesh-bake needs --mesh-lod S: the maps are baked onto the level-of-detail mesh" << std::endl; return 1; }
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }

@@ -1,7 +1,7 @@
 // voxelps_scene — drives the C++ mirror classes exactly the way main_ps.cpp:193-202,323-330 drives the reference's,
 // on a scene dumped as raw little-endian arrays (tests write it with numpy; the PNG / pose-file loaders of the
 // reference are SURVEY §8f "next" rows).  Usage: voxelps_scene <scene_dir>/ <output_dir>/ [--mesh-curvature] [--mesh-lod S --mesh-bake R
-// [--mesh-bake-curvature S]]
+// [--mesh-bake-curvature S]] [--mesh-fill R [--mesh-fill-sweeps K]]
 //   scene_dir/meta.txt : dim0 dim1 dim2 voxel_size shift0 shift1 shift2 T F W H vis_words model(0|1|2) max_it conv upsample reg_n reg_l damping
 //   K.f32 (9) dist.f32 grad.f32 weight.f32 rgb.f32 vis.u64 images.f32 poses.f32 frame_idx.i32
 #include <cstdio>
@@ -26,6 +26,8 @@ int main(int argc, char** argv) {
     for (int i = 3; i < argc; ++i) {      // the dump flags of voxelPS a test compares with the ctypes path on the same scene (checked there; here they are taken as given)
         const std::string a = argv[i];
         if (a == "--mesh-curvature") mesh_curvature() = true;
+        else if (a == "--mesh-fill" && i + 1 < argc) mesh_fill_rounds() = atoi(argv[++i]);
+        else if (a == "--mesh-fill-sweeps" && i + 1 < argc) mesh_fill_sweeps() = atoi(argv[++i]);
         else if (a == "--mesh-lod" && i + 1 < argc) mesh_lod_voxels() = atof(argv[++i]);
         else if (a == "--mesh-bake" && i + 1 < argc) mesh_bake_res() = atoi(argv[++i]);
         else if (a == "--mesh-bake-curvature" && i + 1 < argc) mesh_bake_curvature_scale() = atof(argv[++i]);
