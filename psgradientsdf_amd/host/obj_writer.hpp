@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "text_format.hpp"
+
 namespace psgsdf_host {
 
 inline std::string path_basename(const std::string& p) { const size_t s = p.find_last_of('/'); return s == std::string::npos ? p : p.substr(s + 1); }
@@ -37,15 +39,10 @@ inline bool write_obj_bake(const std::string& obj_path, const std::string& mtl_p
         snprintf(line, sizeof line, "f %lld/%lld/%lld %lld/%lld/%lld %lld/%lld/%lld\n", a, t, a, b, t + 1, b, c, t + 2, c);
         s += line;
     }
-    FILE* fo = fopen(obj_path.c_str(), "wb");
-    bool ok = fo && fwrite(s.data(), 1, s.size(), fo) == s.size();
-    if (fo && fclose(fo) != 0) ok = false;
+    const bool ok = save_text(obj_path, s);
     const std::string m = "newmtl baked\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nmap_Kd " + path_basename(albedo_png) + "\nnorm " + path_basename(normal_png) + "\n"
                           + (ao_png.empty() ? "" : "map_Ka " + path_basename(ao_png) + "\n");      // (--mesh-bake-ao: the ambient-occlusion map)
-    FILE* fm = fopen(mtl_path.c_str(), "wb");
-    ok = fm && fwrite(m.data(), 1, m.size(), fm) == m.size() && ok;
-    if (fm && fclose(fm) != 0) ok = false;
-    return ok;
+    return save_text(mtl_path, m) && ok;
 }
 
 }  // namespace psgsdf_host

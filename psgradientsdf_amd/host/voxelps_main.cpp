@@ -38,13 +38,6 @@ static void sampleKeyFrame(A& frames, B& stamps, C_& images, D& poses, int max_n
     f2.push_back(frames.back()); s2.push_back(stamps.back()); i2.push_back(images.back()); p2.push_back(poses.back());
     frames = f2; stamps = s2; images = i2; poses = p2;
 }
-static void quat_of(const Mat4f& M, float q[4]) {   // Eigen::Quaternionf(Matrix3f): x y z w
-    float t = M[0] + M[5] + M[10];
-    if (t > 0) { t = std::sqrt(t + 1.0f); q[3] = 0.5f * t; t = 0.5f / t; q[0] = (M[9] - M[6]) * t; q[1] = (M[2] - M[8]) * t; q[2] = (M[4] - M[1]) * t; }
-    else { int a = 0; if (M[5] > M[0]) a = 1; if (M[10] > M[a * 5]) a = 2; int b = (a + 1) % 3, c = (b + 1) % 3;
-        t = std::sqrt(M[a * 5] - M[b * 5] - M[c * 5] + 1.0f); q[a] = 0.5f * t; t = 0.5f / t;
-        q[3] = (M[c * 4 + b] - M[b * 4 + c]) * t; q[b] = (M[b * 4 + a] + M[a * 4 + b]) * t; q[c] = (M[c * 4 + a] + M[a * 4 + c]) * t; }
-}
 
 // host-side self tests that need no GPU (tests/test_host_tools.py): PNG decoding and the generated marching-cubes table
 static int selftest_png(const char* path) {
@@ -106,76 +99,64 @@ static int selftest_mc_ply(int n, const char* path) {
     return mc.savePly(path) ? 0 : 1;
 }
 
-// `--selftest-ply-indexed out.ply`: a fixed octahedron (6 vertices, 8 outward-wound faces, unit normals) through the binary writer of the welded
-// mesh (tests/test_mesh_indexed_cpu.py parses it back)
-static int selftest_ply_indexed(const char* path) {
-    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
-    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
-    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
-    const float origin[3] = {-0.25f, 0.5f, 1.0f};
-    return psgsdf_host::write_mesh_indexed_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f) ? 0 : 1;
+// the fixture of the writers' self tests: a fixed octahedron (6 vertices, 8 outward-wound faces, unit normals), its grid origin and voxel size
+namespace octa {
+const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
+const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
+const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
+const float origin[3] = {-0.25f, 0.5f, 1.0f}, vs = 0.004f;
+const MeshView mesh{&xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8};
 }
+// `--selftest-ply-indexed out.ply`: the octahedron through the binary writer of the welded mesh (tests/test_mesh_indexed_cpu.py parses it back)
+static int selftest_ply_indexed(const char* path) { return write_mesh_indexed_ply(path, octa::mesh, octa::origin, octa::vs) ? 0 : 1; }
 
-// `--selftest-ply-fit out.ply`: the same octahedron through the writer of `--mesh-fit` (three more vertex properties, one more header line;
-// tests/test_fit_cpu.py parses it back)
+// `--selftest-ply-fit out.ply`: the octahedron with the columns and the header line of `--mesh-fit` (tests/test_fit_cpu.py parses it back)
 static int selftest_ply_fit(const char* path) {
-    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
-    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
-    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
-    const float origin[3] = {-0.25f, 0.5f, 1.0f};
     const float rms[6] = {0.125f, 0.03125f, 0.0f, 0.25f, 0.0625f, 0.5f}, loss[6] = {0.75f, 0.01f, 0.0f, 1.5f, 0.02f, 2.25f};
     const int32_t n_obs[6] = {3, 8, 0, 1, 16, 2};
-    return psgsdf_host::write_mesh_fit_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, rms, loss, n_obs) ? 0 : 1;
+    return write_mesh_indexed_ply(path, octa::mesh, octa::origin, octa::vs, mesh_fit_comment(rms, n_obs, 6), {ply_column("quality", rms), ply_column("loss", loss), ply_column("n_obs", n_obs)}) ? 0 : 1;
 }
 
-// `--selftest-ply-curvature out.ply`: the same octahedron through the writer of `--mesh-curvature` (five more vertex properties, one more header line;
-// tests/test_curvature_cpu.py parses it back)
+// `--selftest-ply-curvature out.ply`: the octahedron with the columns and the header line of `--mesh-curvature` (tests/test_curvature_cpu.py parses it back)
 static int selftest_ply_curvature(const char* path) {
-    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
-    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
-    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
-    const float origin[3] = {-0.25f, 0.5f, 1.0f};
     const float mean[6] = {0.5f, -0.25f, 0.0f, 8.0f, 0.125f, -3.0f}, gauss[6] = {0.25f, 0.0625f, 0.0f, -4.0f, 0.01f, 9.0f};
     const float k1[6] = {0.75f, -0.125f, 0.0f, 16.0f, 0.25f, -3.0f}, k2[6] = {0.25f, -0.375f, 0.0f, -0.25f, 0.04f, -3.0f};
     const uint8_t valid[6] = {2, 1, 0, 2, 1, 2};
-    return psgsdf_host::write_mesh_curvature_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, mean, gauss, k1, k2, valid) ? 0 : 1;
+    return write_mesh_indexed_ply(path, octa::mesh, octa::origin, octa::vs, mesh_curvature_comment(mean, valid, 6),
+                                  {ply_column("quality", mean), ply_column("gauss", gauss), ply_column("k1", k1), ply_column("k2", k2), ply_column("curvature_valid", valid)}) ? 0 : 1;
 }
 
-// `--selftest-ply-compare out.ply`: the same octahedron through the writer of `--compare-ply` (two more vertex properties, one more header line;
-// tests/test_compare_cpu.py parses it back) and back through the reader of `--compare-ply`, which has to skip what it does not want by the
-// declared sizes: 0 iff the positions and faces it returns are the ones written
+// `--selftest-ply-filled out.ply`: the octahedron with the column and the header line of `--mesh-fill` (tests/test_fill_cpu.py parses it back)
+static int selftest_ply_filled(const char* path) {
+    const uint8_t filled[6] = {0, 1, 2, 0, 2, 1};
+    return write_mesh_indexed_ply(path, octa::mesh, octa::origin, octa::vs, mesh_filled_comment(3, 4, 17, 12, 0), {ply_column("filled", filled)}) ? 0 : 1;
+}
+
+// `--selftest-ply-compare out.ply`: the octahedron with the columns of `--compare-ply` and one more header line (tests/test_compare_cpu.py parses it
+// back) and back through the reader of `--compare-ply`, which has to skip what it does not want by the declared sizes: 0 iff the positions and faces
+// it returns are the ones written
 static int selftest_ply_compare(const char* path) {
-    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
-    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-    const uint8_t rgb[6][3] = {{255, 0, 0}, {0, 255, 0}, {0, 0, 255}, {1, 2, 3}, {128, 64, 32}, {7, 77, 177}};
-    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
-    const float origin[3] = {-0.25f, 0.5f, 1.0f};
     const float dist[6] = {0.125f, 0.03125f, 0.0f, INFINITY, 0.0625f, 0.5f};
     const int8_t side[6] = {1, -1, 0, 0, -1, 1};
-    if (!psgsdf_host::write_mesh_compare_ply(path, &xyz[0][0], &nrm[0][0], &rgb[0][0], 6, &faces[0][0], 8, origin, 0.004f, dist, side, "comment compare selftest\n")) return 1;
+    if (!write_mesh_indexed_ply(path, octa::mesh, octa::origin, octa::vs, "comment compare selftest\n", {ply_column("distance", dist), ply_column("side", side)})) return 1;
     std::vector<float> rx; std::vector<int32_t> rf; std::string why;
-    if (!psgsdf_host::read_reference_ply(path, rx, rf, why)) { std::cerr << why << std::endl; return 1; }
-    return rx.size() == 18 && rf.size() == 24 && memcmp(rx.data(), xyz, sizeof xyz) == 0 && memcmp(rf.data(), faces, sizeof faces) == 0 ? 0 : 1;
+    if (!read_reference_ply(path, rx, rf, why)) { std::cerr << why << std::endl; return 1; }
+    return rx.size() == 18 && rf.size() == 24 && memcmp(rx.data(), octa::xyz, sizeof octa::xyz) == 0 && memcmp(rf.data(), octa::faces, sizeof octa::faces) == 0 ? 0 : 1;
 }
 
-// `--selftest-obj-bake out.obj`: the same octahedron with made-up texture coordinates (dyadic, so that 1 - v is exact) through the writer of
+// `--selftest-obj-bake out.obj`: the octahedron with made-up texture coordinates (dyadic, so that 1 - v is exact) through the writer of
 // `--mesh-bake` -- out.obj, out.mtl -- and three normals through the normal map's byte rule into out_normal.png (tests/test_bake_cpu.py parses them back)
 static int selftest_obj_bake(const char* path) {
-    const float xyz[6][3] = {{1.5f, 0, 0}, {-1.5f, 0, 0}, {0, 2.25f, 0}, {0, -2.25f, 0}, {0, 0, 0.75f}, {0, 0, -0.75f}};
-    const float nrm[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-    const int32_t faces[8][3] = {{0, 2, 4}, {2, 1, 4}, {1, 3, 4}, {3, 0, 4}, {2, 0, 5}, {1, 2, 5}, {3, 1, 5}, {0, 3, 5}};
     float uv[8][3][2];
     for (int f = 0; f < 8; ++f) for (int k = 0; k < 3; ++k) { uv[f][k][0] = (3 * f + k) / 32.0f; uv[f][k][1] = (f + k) / 16.0f; }
     std::string base = path;
     if (base.size() > 4 && base.compare(base.size() - 4, 4, ".obj") == 0) base.resize(base.size() - 4);
     const float nm[3][3] = {{1.0f, 0.0f, -1.0f}, {0.0f, 0.0f, 0.0f}, {0.5f, -0.5f, 0.25f}};
     uint8_t px[9];
-    for (int q = 0; q < 9; ++q) px[q] = psgsdf_host::normal_to_u8((&nm[0][0])[q]);
-    const bool ok = psgsdf_host::write_obj_bake(path, base + ".mtl", base + "_albedo.png", base + "_normal.png", &xyz[0][0], &nrm[0][0], 6, &faces[0][0], &uv[0][0][0], 8);
-    return ok && psgsdf_host::write_png(base + "_normal.png", 3, 1, 3, px) ? 0 : 1;
+    for (int q = 0; q < 9; ++q) px[q] = normal_to_u8((&nm[0][0])[q]);
+    const bool ok = write_obj_bake(path, base + ".mtl", base + "_albedo.png", base + "_normal.png", octa::mesh.xyz, octa::mesh.normals, octa::mesh.nv, octa::mesh.faces, &uv[0][0][0], octa::mesh.nf);
+    return ok && write_png(base + "_normal.png", 3, 1, 3, px) ? 0 : 1;
 }
 
 // the focus measure of one colour PNG as the keyframe selector computes it (SharpDetector.h:22-37), and the keyframe sub-sampling of
@@ -338,6 +319,7 @@ int main(int argc, char* argv[]) {
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-indexed") return selftest_ply_indexed(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-fit") return selftest_ply_fit(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-curvature") return selftest_ply_curvature(argv[2]);
+    if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-filled") return selftest_ply_filled(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-obj-bake") return selftest_obj_bake(argv[2]);
     if (argc >= 3 && std::string(argv[1]) == "--selftest-ply-compare") return selftest_ply_compare(argv[2]);
     int want_ranks = 1; std::string transport = "rccl";
@@ -352,49 +334,50 @@ int main(int argc, char* argv[]) {
     bool cmp_tau_flag = false, cmp_max_flag = false, cmp_iters_flag = false, cmp_bad_iters = false;
     std::string relight_file;                 // --relight FILE: every keyframe under the lights of FILE (relight/*.png, relight_report.txt; include/psgsdf_relight.h)
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
+    DumpOptions& opt = dump_options();      // (every dump flag is documented at its member, device_dumps.hpp)
     for (int i = 1; i < argc; ++i) { std::string a = argv[i]; if (a == "--config_file" && i + 1 < argc) configfile = argv[++i]; else if (a.rfind("--config_file=", 0) == 0) configfile = a.substr(14);
         else if (a == "--timing" && i + 1 < argc) timing_file = argv[++i];
-        else if (a == "--host-writers") host_writers() = true;
+        else if (a == "--host-writers") opt.host_writers = true;
         else if (a == "--render-keyframes") render_keyframes = true;
         else if (a == "--relight" && i + 1 < argc) relight_file = argv[++i];
-        else if (a == "--indexed-mesh") indexed_mesh() = true;      // a <name>_mesh_indexed.ply (welded, normals, binary; include/psgsdf_mesh.h) next to every <name>_mesh.ply
-        else if (a == "--mesh-min-faces" && i + 1 < argc) { mesh_filter().min_faces = atoll(argv[++i]); clean_mesh() = true; filter_flag = a; }      // <name>_mesh_clean.ply + <name>_mesh_components.txt next to every <name>_mesh.ply:
-        else if (a == "--mesh-keep-largest" && i + 1 < argc) { mesh_filter().keep_largest = atoi(argv[++i]); clean_mesh() = true; filter_flag = a; }   // the welded mesh without its small connected components (include/psgsdf_mesh.h)
-        else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_lod_voxels() = lod_ok ? v : 0.0; lod_flag = true; }      // <name>_mesh_lod.ply next to every <name>_mesh.ply: the vertices of every cube of S voxels merged (include/psgsdf_mesh.h psgsdf_extract_mesh_lod)
-        else if (a == "--mesh-bake" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); bake_ok = end != argv[i] && *end == 0 && v >= 1 && v <= 16383; mesh_bake_res() = bake_ok ? (int)v : 0; bake_flag = true; }      // with --mesh-lod: <name>_mesh_lod.obj / .mtl / _albedo.png / _normal.png next to every <name>_mesh_lod.ply: the reconstruction's albedo and normals baked onto the coarse mesh, R texels along a triangle's edge (include/psgsdf_bake.h)
-        else if (a == "--mesh-bake-ao" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); ao_ok = end != argv[i] && *end == 0 && (v == 8 || v == 16 || v == 32 || v == 64); mesh_bake_ao_dirs() = ao_ok ? (int)v : 0; ao_flag = true; }      // with --mesh-bake: <name>_mesh_lod_ao.png and a map_Ka line in the .mtl: ambient occlusion of the reconstructed surface, K rays per texel (include/psgsdf_occlusion.h)
-        else if (a == "--mesh-bake-photo") mesh_bake_photo() = true;      // with --mesh-bake: <name>_mesh_lod_photo.png, the albedo of every texel solved from the keyframes that see it, and map_Kd in the .mtl names it (include/psgsdf_photo.h); a dump taken before the optimiser holds the keyframes is baked as without the flag
-        else if (a == "--mesh-fit") mesh_fit() = true;      // <name>_mesh_fit.ply next to every <name>_mesh.ply: the welded mesh with every vertex's observations, rms residual and mean loss (include/psgsdf_fit.h)
-        else if (a == "--mesh-curvature") mesh_curvature() = true;      // <name>_mesh_curvature.ply next to every <name>_mesh.ply: the welded mesh with every vertex's mean, Gaussian and principal curvatures (include/psgsdf_curvature.h)
-        else if (a == "--mesh-bake-curvature" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); curv_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; mesh_bake_curvature_scale() = curv_ok ? v : 0.0; curv_flag = true; }      // with --mesh-bake: <name>_mesh_lod_curvature.png, the mean curvature of every texel's voxel in grey, convex bright; S: the curvature times the voxel size that maps to white
-        else if (a == "--mesh-fill" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); fill_ok = end != argv[i] && *end == 0 && v >= 0 && v <= PSGSDF_FILL_MAX_ROUNDS; mesh_fill_rounds() = fill_ok ? (int)v : -1; fill_flag = true; }      // <name>_mesh_filled.ply next to every <name>_mesh.ply: the welded mesh of the state with its unobserved voxels filled over R front rounds, holes up to about 2 R voxels wide closed (include/psgsdf_fill.h)
-        else if (a == "--mesh-fill-sweeps" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); fillk_ok = end != argv[i] && *end == 0 && v >= 0 && v <= PSGSDF_FILL_MAX_SWEEPS; if (fillk_ok) mesh_fill_sweeps() = (int)v; fillk_flag = true; }      // with --mesh-fill: the relaxation sweeps over the filled voxels (default 4)
-        else if (a == "--compare-ply" && i + 1 < argc) cmp_file = argv[++i];      // <name>_compare.txt and <name>_mesh_compare.ply next to every <name>_mesh.ply: distances between the welded mesh and the mesh or cloud in FILE, precision / recall / F (include/psgsdf_compare.h)
-        else if ((a == "--compare-tau" || a == "--compare-max") && i + 1 < argc) {      // the threshold of precision / recall and the matching radius, in voxels (defaults 1 and 8)
+        else if (a == "--indexed-mesh") opt.indexed_mesh = true;
+        else if (a == "--mesh-min-faces" && i + 1 < argc) { opt.mesh_filter.min_faces = atoll(argv[++i]); opt.clean_mesh = true; filter_flag = a; }
+        else if (a == "--mesh-keep-largest" && i + 1 < argc) { opt.mesh_filter.keep_largest = atoi(argv[++i]); opt.clean_mesh = true; filter_flag = a; }
+        else if (a == "--mesh-lod" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); lod_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; opt.lod_voxels = lod_ok ? v : 0.0; lod_flag = true; }
+        else if (a == "--mesh-bake" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); bake_ok = end != argv[i] && *end == 0 && v >= 1 && v <= 16383; opt.bake_res = bake_ok ? (int)v : 0; bake_flag = true; }
+        else if (a == "--mesh-bake-ao" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); ao_ok = end != argv[i] && *end == 0 && (v == 8 || v == 16 || v == 32 || v == 64); opt.bake_ao_dirs = ao_ok ? (int)v : 0; ao_flag = true; }
+        else if (a == "--mesh-bake-photo") opt.bake_photo = true;
+        else if (a == "--mesh-fit") opt.fit = true;
+        else if (a == "--mesh-curvature") opt.curvature = true;
+        else if (a == "--mesh-bake-curvature" && i + 1 < argc) { char* end = nullptr; const double v = strtod(argv[++i], &end); curv_ok = end != argv[i] && *end == 0 && std::isfinite(v) && v > 0; opt.bake_curvature_scale = curv_ok ? v : 0.0; curv_flag = true; }
+        else if (a == "--mesh-fill" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); fill_ok = end != argv[i] && *end == 0 && v >= 0 && v <= PSGSDF_FILL_MAX_ROUNDS; opt.fill_rounds = fill_ok ? (int)v : -1; fill_flag = true; }
+        else if (a == "--mesh-fill-sweeps" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); fillk_ok = end != argv[i] && *end == 0 && v >= 0 && v <= PSGSDF_FILL_MAX_SWEEPS; if (fillk_ok) opt.fill_sweeps = (int)v; fillk_flag = true; }
+        else if (a == "--compare-ply" && i + 1 < argc) cmp_file = argv[++i];
+        else if ((a == "--compare-tau" || a == "--compare-max") && i + 1 < argc) {
             char* end = nullptr; const double v = strtod(argv[++i], &end);
             if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0) || v > 64) cmp_bad = a;
-            (a == "--compare-tau" ? compare_ref().tau_voxels : compare_ref().max_voxels) = v; (a == "--compare-tau" ? cmp_tau_flag : cmp_max_flag) = true; }
-        else if (a == "--compare-align") compare_ref().align = true;      // with --compare-ply: the reference is first aligned to every dump's mesh by ICP on the device (include/psgsdf_align.h); <name>_align.txt next to <name>_compare.txt
-        else if (a == "--compare-align-iters" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); if (end == argv[i] || *end || v < 0 || v > 64) cmp_bad_iters = true; compare_ref().align_iters = (int)v; cmp_iters_flag = true; }
+            (a == "--compare-tau" ? opt.compare.tau_voxels : opt.compare.max_voxels) = v; (a == "--compare-tau" ? cmp_tau_flag : cmp_max_flag) = true; }
+        else if (a == "--compare-align") opt.compare.align = true;
+        else if (a == "--compare-align-iters" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); if (end == argv[i] || *end || v < 0 || v > 64) cmp_bad_iters = true; opt.compare.align_iters = (int)v; cmp_iters_flag = true; }
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
         else if (a == "--gpus" && i + 1 < argc) want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--rank" && i + 1 < argc) rank_info().rank = atoi(argv[++i]);
         else if (a == "--nranks" && i + 1 < argc) rank_info().n = atoi(argv[++i]);
         else if (a == "--fds" && i + 1 < argc) { std::string f = argv[++i]; size_t p0 = 0; while (p0 <= f.size()) { size_t p1 = f.find(',', p0); if (p1 == std::string::npos) p1 = f.size(); rank_info().fds.push_back(atoi(f.substr(p0, p1 - p0).c_str())); p0 = p1 + 1; } }
-        else if (a == "--comm-id" && i + 1 < argc) { std::string h = argv[++i]; for (size_t q = 0; q + 1 < h.size(); q += 2) rank_info().id.push_back((uint8_t)strtol(h.substr(q, 2).c_str(), nullptr, 16)); } }      // round 4's dump path (dense download, host marching cubes, iostream) and frame path (serial decode, normals through the host): the cross-check of the device / threaded one
+        else if (a == "--comm-id" && i + 1 < argc) { std::string h = argv[++i]; for (size_t q = 0; q + 1 < h.size(); q += 2) rank_info().id.push_back((uint8_t)strtol(h.substr(q, 2).c_str(), nullptr, 16)); } }
     if (transport != "rccl" && transport != "sockets") { std::cerr << "--transport: rccl or sockets" << std::endl; return 1; }
-    if ((want_ranks > 1 || multi_rank()) && host_writers()) { std::cerr << "--host-writers is the single-process cross-check" << std::endl; return 1; }
-    if ((want_ranks > 1 || multi_rank()) && clean_mesh()) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && opt.host_writers) { std::cerr << "--host-writers is the single-process cross-check" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && opt.clean_mesh) { std::cerr << filter_flag << " needs a single process: mesh components are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << " yet" << std::endl; return 1; }
     if (ao_flag && !ao_ok) { std::cerr << "--mesh-bake-ao: rays per texel, 8, 16, 32 or 64" << std::endl; return 1; }
     if (ao_flag && !bake_flag) { std::cerr << "--mesh-bake-ao needs --mesh-bake R: the occlusion is one more map of the bake" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && ao_flag) { std::cerr << "--mesh-bake-ao needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
-    if (mesh_bake_photo() && !bake_flag) { std::cerr << "--mesh-bake-photo needs --mesh-bake R: the photo map is one more map of the bake" << std::endl; return 1; }
-    if ((want_ranks > 1 || multi_rank()) && mesh_bake_photo()) { std::cerr << "--mesh-bake-photo needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if (opt.bake_photo && !bake_flag) { std::cerr << "--mesh-bake-photo needs --mesh-bake R: the photo map is one more map of the bake" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && opt.bake_photo) { std::cerr << "--mesh-bake-photo needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (curv_flag && !curv_ok) { std::cerr << "--mesh-bake-curvature: the mean curvature times the voxel size that maps to white, a finite number > 0" << std::endl; return 1; }
     if (curv_flag && !bake_flag) { std::cerr << "--mesh-bake-curvature needs --mesh-bake R: the curvature is one more map of the bake" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && curv_flag) { std::cerr << "--mesh-bake-curvature needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
-    if ((want_ranks > 1 || multi_rank()) && mesh_curvature()) { std::cerr << "--mesh-curvature needs a single process: a slab holds only its own planes of the volume (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && opt.curvature) { std::cerr << "--mesh-curvature needs a single process: a slab holds only its own planes of the volume (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
     if (fill_flag && !fill_ok) { std::cerr << "--mesh-fill: the front rounds, a whole number in 0 .. " << PSGSDF_FILL_MAX_ROUNDS << std::endl; return 1; }
     if (fillk_flag && !fillk_ok) { std::cerr << "--mesh-fill-sweeps: the relaxation sweeps, a whole number in 0 .. " << PSGSDF_FILL_MAX_SWEEPS << std::endl; return 1; }
     if (fillk_flag && !fill_flag) { std::cerr << "--mesh-fill-sweeps needs --mesh-fill R: the sweeps relax the voxels it fills" << std::endl; return 1; }
@@ -404,27 +387,27 @@ int main(int argc, char* argv[]) {
     if (lod_flag && !lod_ok) { std::cerr << "--mesh-lod: a cell size > 0, in voxels" << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && bake_flag) { std::cerr << "--mesh-bake needs a single process: the level-of-detail mesh it bakes onto is not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if ((want_ranks > 1 || multi_rank()) && lod_flag) { std::cerr << "--mesh-lod needs a single process: clusters are not merged across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
-    if ((want_ranks > 1 || multi_rank()) && mesh_fit()) { std::cerr << "--mesh-fit needs a single process: the fit is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if ((want_ranks > 1 || multi_rank()) && opt.fit) { std::cerr << "--mesh-fit needs a single process: the fit is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (!cmp_bad.empty()) { std::cerr << cmp_bad << ": a number of voxels, 0 < tau <= max <= 64" << std::endl; return 1; }
     if ((cmp_tau_flag || cmp_max_flag) && cmp_file.empty()) { std::cerr << "--compare-tau / --compare-max need --compare-ply FILE: the reference to compare with" << std::endl; return 1; }
     if (cmp_bad_iters) { std::cerr << "--compare-align-iters: a whole number of steps, 0 .. 64" << std::endl; return 1; }
-    if (cmp_iters_flag && !compare_ref().align) { std::cerr << "--compare-align-iters needs --compare-align" << std::endl; return 1; }
-    if (compare_ref().align && cmp_file.empty()) { std::cerr << "--compare-align needs --compare-ply FILE: the reference to align" << std::endl; return 1; }
-    if (compare_ref().align && (want_ranks > 1 || multi_rank())) { std::cerr << "--compare-align needs a single process: the welded mesh is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
+    if (cmp_iters_flag && !opt.compare.align) { std::cerr << "--compare-align-iters needs --compare-align" << std::endl; return 1; }
+    if (opt.compare.align && cmp_file.empty()) { std::cerr << "--compare-align needs --compare-ply FILE: the reference to align" << std::endl; return 1; }
+    if (opt.compare.align && (want_ranks > 1 || multi_rank())) { std::cerr << "--compare-align needs a single process: the welded mesh is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
     if (!cmp_file.empty()) {
         if (want_ranks > 1 || multi_rank()) { std::cerr << "--compare-ply needs a single process: the welded mesh is not gathered across the slabs of --gpus " << std::max(want_ranks, rank_info().n) << std::endl; return 1; }
-        if (compare_ref().tau_voxels > compare_ref().max_voxels) { std::cerr << (cmp_tau_flag ? "--compare-tau" : "--compare-max") << ": tau " << compare_ref().tau_voxels << " is more than the matching radius " << compare_ref().max_voxels << std::endl; return 1; }
+        if (opt.compare.tau_voxels > opt.compare.max_voxels) { std::cerr << (cmp_tau_flag ? "--compare-tau" : "--compare-max") << ": tau " << opt.compare.tau_voxels << " is more than the matching radius " << opt.compare.max_voxels << std::endl; return 1; }
         std::string why;
-        if (!read_reference_ply(cmp_file, compare_ref().xyz, compare_ref().faces, why)) { std::cerr << "--compare-ply: " << why << std::endl; return 1; }
-        compare_ref().file = cmp_file; compare_ref().on = true;
+        if (!read_reference_ply(cmp_file, opt.compare.xyz, opt.compare.faces, why)) { std::cerr << "--compare-ply: " << why << std::endl; return 1; }
+        opt.compare.file = cmp_file; opt.compare.on = true;
     }
     if (!relight_file.empty()) {
         if (want_ranks > 1 || multi_rank()) { std::cerr << "--relight needs a single process: a slab holds only its own planes of the volume the shadow rays cross (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
         std::string why;
-        if (!read_relight_file(relight_file, relight_spec(), why)) { std::cerr << "--relight: " << why << std::endl; return 1; }
-        relight_spec().on = true;
+        if (!read_relight_file(relight_file, opt.relight, why)) { std::cerr << "--relight: " << why << std::endl; return 1; }
+        opt.relight.on = true;
     }
-    if (mesh_filter().keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
+    if (opt.mesh_filter.keep_largest < 0) { std::cerr << "--mesh-keep-largest: a count >= 0" << std::endl; return 1; }
     if (want_ranks > 1 && !multi_rank()) return launch_ranks(want_ranks, transport == "sockets", argc, argv);
     static std::ofstream null_out;
     if (multi_rank()) {
@@ -504,9 +487,9 @@ int main(int argc, char* argv[]) {
     int dist_to_last_keyframe = 0; bool GT_pose = false;
     if (!loader->load_pose(pose_file, poses)) { std::cout << "GT poses is not avalible!" << std::endl; poses.push_back(I4); }
     else { std::cout << poses.size() << " GT poses are loaded." << std::endl; GT_pose = true; }
-    { std::string d, r; for (size_t i = 0; i < first; ++i) if (host_writers()) loader->load_next(color, depth); else loader->next_names(d, r); }      // (frames in front of "first" are skipped; the reference decodes them, nothing reads them)
+    { std::string d, r; for (size_t i = 0; i < first; ++i) if (opt.host_writers) loader->load_next(color, depth); else loader->next_names(d, r); }      // (frames in front of "first" are skipped; the reference decodes them, nothing reads them)
     Mat4f cur_pose = I4;
-    size_t window = host_writers() ? 1 : std::min<size_t>(4, std::max(2u, std::thread::hardware_concurrency() / 2));
+    size_t window = opt.host_writers ? 1 : std::min<size_t>(4, std::max(2u, std::thread::hardware_concurrency() / 2));
     if (const char* e = getenv("VOXELPS_PREFETCH")) window = (size_t)std::max(1, atoi(e));      // (frames decoded ahead of the fusion)
     FramePrefetcher prefetch(loader, window);
     std::string stamp_rgb, stamp_depth;
@@ -514,7 +497,7 @@ int main(int argc, char* argv[]) {
         std::cout << "Working on frame: " << i << std::endl;
         {
             PSG_STAGE("decode: PNG colour + depth (host; wait for the prefetched frame)");
-            if (host_writers()) { if (!loader->load_next(color, depth)) { std::cerr << " -> Frame " << i << " could not be loaded!" << std::endl; break; } stamp_rgb = loader->rgb_timestamp(); stamp_depth = loader->depth_timestamp(); }
+            if (opt.host_writers) { if (!loader->load_next(color, depth)) { std::cerr << " -> Frame " << i << " could not be loaded!" << std::endl; break; } stamp_rgb = loader->rgb_timestamp(); stamp_depth = loader->depth_timestamp(); }
             else {
                 auto fr = prefetch.next();
                 if (!fr) { std::cerr << " -> Frame " << i << " could not be loaded!" << std::endl; break; }
@@ -554,7 +537,7 @@ int main(int argc, char* argv[]) {
                 } else ++dist_to_last_keyframe;
             }
         }
-        float q[4]; quat_of(cur_pose, q);
+        float q[4]; quat_of(cur_pose.data(), q);
         pose_out << stamp_depth << " " << cur_pose[3] << " " << cur_pose[7] << " " << cur_pose[11] << " " << q[0] << " " << q[1] << " " << q[2] << " " << q[3] << "\n";
     }
     pose_out.close();
@@ -565,12 +548,12 @@ int main(int argc, char* argv[]) {
     std::cout << " selected key frame: " << std::endl; for (int k : keyframes) std::cout << k << " "; std::cout << std::endl;
     if ((int)keyframes.size() > max_key) sampleKeyFrame(keyframes, key_stamps, key_images, key_poses, max_key);
     std::cout << " selected key frame after sampling: " << std::endl; for (int k : keyframes) std::cout << k << " "; std::cout << std::endl;
-    skip_sync_back() = !host_writers();
+    opt.skip_sync_back = !opt.host_writers;
     vOpt->setImages(key_images); vOpt->setKeyframes(keyframes); vOpt->setKeytimestamps(key_stamps); vOpt->setPoses(key_poses);
     vOpt->init();
     vOpt->alternatingOptimize(light, albedo, distance, pose);
     if (render_keyframes && !vOpt->renderKeyframes(output)) { std::cerr << "--render-keyframes: rendering failed" << std::endl; return 1; }   // (collective on a multi-rank run)
-    if (relight_spec().on && !vOpt->relightKeyframes(output, relight_spec())) { std::cerr << "--relight: relighting failed" << std::endl; return 1; }
+    if (opt.relight.on && !vOpt->relightKeyframes(output, opt.relight)) { std::cerr << "--relight: relighting failed" << std::endl; return 1; }
     DumpQueue::get().drain();
     const int write_failures = DumpQueue::get().failures();      // (a rank whose piece of a shared output file could not be written: the file has a hole where it belongs)
     if (write_failures) std::cerr << "rank " << rank_info().rank << ": " << write_failures << " output file piece(s) could not be written" << std::endl;

@@ -23,14 +23,15 @@ template <class T> static bool slurp(const std::string& path, std::vector<T>& v,
 int main(int argc, char** argv) {
     if (argc < 3) { std::cerr << "usage: voxelps_scene <scene_dir>/ <output_dir>/" << std::endl; return 1; }
     std::string in = argv[1], out = argv[2];
+    DumpOptions& opt = dump_options();
     for (int i = 3; i < argc; ++i) {      // the dump flags of voxelPS a test compares with the ctypes path on the same scene (checked there; here they are taken as given)
         const std::string a = argv[i];
-        if (a == "--mesh-curvature") mesh_curvature() = true;
-        else if (a == "--mesh-fill" && i + 1 < argc) mesh_fill_rounds() = atoi(argv[++i]);
-        else if (a == "--mesh-fill-sweeps" && i + 1 < argc) mesh_fill_sweeps() = atoi(argv[++i]);
-        else if (a == "--mesh-lod" && i + 1 < argc) mesh_lod_voxels() = atof(argv[++i]);
-        else if (a == "--mesh-bake" && i + 1 < argc) mesh_bake_res() = atoi(argv[++i]);
-        else if (a == "--mesh-bake-curvature" && i + 1 < argc) mesh_bake_curvature_scale() = atof(argv[++i]);
+        if (a == "--mesh-curvature") opt.curvature = true;
+        else if (a == "--mesh-fill" && i + 1 < argc) opt.fill_rounds = atoi(argv[++i]);
+        else if (a == "--mesh-fill-sweeps" && i + 1 < argc) opt.fill_sweeps = atoi(argv[++i]);
+        else if (a == "--mesh-lod" && i + 1 < argc) opt.lod_voxels = atof(argv[++i]);
+        else if (a == "--mesh-bake" && i + 1 < argc) opt.bake_res = atoi(argv[++i]);
+        else if (a == "--mesh-bake-curvature" && i + 1 < argc) opt.bake_curvature_scale = atof(argv[++i]);
         else { std::cerr << "unknown flag " << a << std::endl; return 1; }
     }
     std::ifstream meta(in + "meta.txt");

@@ -3,6 +3,8 @@ against a voxel-by-voxel transcription of the header, the hand-computed cases th
 the bumpy sphere with a hole (tests/test_mesh_indexed_gpu.py analytic_engine): boundary edges, Euler characteristic, winding, distance to the surface."""
 import functools
 import math
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -10,7 +12,10 @@ import pytest
 import _fill_ref as fref
 import _mesh_ref as mref
 from psgradientsdf_amd import synth
+from test_mesh_indexed_cpu import read_ply_indexed
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "psgradientsdf_amd", "host", "voxelPS")
 f32 = np.float32
 VS = 0.01
 
@@ -38,6 +43,26 @@ def fill_comment(head):
     w = next(h for h in head if h.startswith("comment fill ")).split()
     assert w[2:9:2] == ["rounds", "sweeps", "voxels", "boundary_edges"] and len(w) == 11, w
     return dict(rounds=int(w[3]), sweeps=int(w[5]), voxels=int(w[7]), before=int(w[9]), after=int(w[10]))
+
+
+@pytest.mark.skipif(not os.path.exists(EXE), reason="voxelPS not built")
+def test_selftest_ply_filled_parses_back(tmp_path):
+    """`voxelPS --selftest-ply-filled`: the octahedron of --selftest-ply-indexed with `filled` behind the colours, through the one writer of the welded mesh"""
+    out, plain = str(tmp_path / "octa_filled.ply"), str(tmp_path / "octa.ply")
+    for flag, path in (("--selftest-ply-filled", out), ("--selftest-ply-indexed", plain)):
+        r = subprocess.run([EXE, flag, path], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stdout + r.stderr
+    head, verts, faces = read_ply_filled(out)      # (asserts the property lines, the 28-byte records and the file's length)
+    phead, pverts, pfaces = read_ply_indexed(plain)
+    assert len(verts) == 6 and np.array_equal(faces, pfaces) and len(faces) == 8
+    assert verts.dtype.itemsize == 28 and pverts.dtype.itemsize == 27
+    assert [bytes(v.tobytes()[:27]) for v in verts] == [bytes(v.tobytes()) for v in pverts]
+    for k in pverts.dtype.names:
+        assert np.array_equal(verts[k], pverts[k]), k
+    assert verts["filled"].tolist() == [0, 1, 2, 0, 2, 1]
+    assert fill_comment(head) == dict(rounds=3, sweeps=4, voxels=17, before=12, after=0)
+    assert [h for h in head if not h.startswith(("comment fill", "property"))] == [h for h in phead if not h.startswith("property")]
+    assert [h for h in head if h.startswith("property")] == [h for h in phead if h.startswith("property")][:9] + ["property uchar filled", "property list uchar int vertex_indices"]
 
 
 def volume(dim, observed, dist=None, grad=None, rgb=None, seed=0):

@@ -243,7 +243,7 @@ def test_keyframe_sampling_against_numpy(built, n, max_num):
 
 
 def test_threaded_writers_print_floats_like_the_reference(built):
-    """The round-5 writers format floats with their own "%g" (host/ps_optimizer.hpp format_g6: exact power-of-ten scaling in double, snprintf for the values
+    """The round-5 writers format floats with their own "%g" (host/text_format.hpp format_g6: exact power-of-ten scaling in double, snprintf for the values
     within 1e-6 of a rounding tie and outside the exact powers' reach) into per-thread buffers; the reference (and round 4's writers) with `ostream << float`,
     one std::endl per line.  `voxelPS --selftest-fmt N`: N pseudo-random float bit patterns (every exponent, denormals, infinities, NaNs), N uniform values in
     (-2, 2), N log-uniform over 1e-7 .. 1e7, 3 N floats at and next to seven-digit decimals ending in 5 (the nearest a float gets to a tie of the sixth
