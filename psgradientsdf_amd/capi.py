@@ -227,6 +227,66 @@ def _fp(a, dtype=np.float32):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
+_F32P, _U8P, _I32P = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+_ITER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(IterStats))      # psgsdf_iter_cb
+
+
+def _ref(s):
+    return None if s is None else C.byref(s)
+
+
+def _owned(ptr, shape, dtype):
+    """The engine's result behind `ptr` as an array the caller owns: the engine's results are valid until the next extraction call, so every one of
+    them is copied here.  A shape without elements gives zeros(shape, dtype) and the pointer (NULL, then) is never touched."""
+    shape = tuple(int(n) for n in shape)
+    if 0 in shape:
+        return np.zeros(shape, dtype)
+    return np.ctypeslib.as_array(ptr, shape=shape).copy()
+
+
+def _mesh_filter(min_faces, min_area, keep_largest, always=False):
+    """the psgsdf_mesh_filter of the three keyword arguments, or None (the engine's NULL: the whole mesh) when all three are zero"""
+    if not (always or min_faces or min_area or keep_largest):
+        return None
+    return MeshFilter(int(min_faces), float(min_area), int(keep_largest))
+
+
+def _counts(c):
+    """a counts struct (AoCounts, PhotoCounts, RelightCounts) as a dict of ints"""
+    return {k: int(getattr(c, k)) for k, _ in c._fields_}
+
+
+def _mesh_arrays(r):
+    """xyz, normals, rgb, faces of a result that holds the welded mesh (Bake, Compare, Align, _MeshHead)"""
+    V, F = r.n_vertices, r.n_faces
+    return dict(xyz=_owned(r.xyz, (V, 3), np.float32), normals=_owned(r.normals, (V, 3), np.float32), rgb=_owned(r.rgb, (V, 3), np.uint8), faces=_owned(r.faces, (F, 3), np.int32))
+
+
+class _MeshHead:
+    """the six out-parameters every welded-mesh call begins with"""
+
+    def __init__(self):
+        self.xyz, self.normals, self.rgb, self.faces, self._nv, self._nf = _F32P(), _F32P(), _U8P(), _I32P(), C.c_int64(), C.c_int64()
+
+    n_vertices = property(lambda self: self._nv.value)
+    n_faces = property(lambda self: self._nf.value)
+
+    def refs(self):
+        """in the ABI's order"""
+        return [C.byref(x) for x in (self.xyz, self.normals, self.rgb, self._nv, self.faces, self._nf)]
+
+    def arrays(self):
+        return _mesh_arrays(self)
+
+
+def _reference(ref_xyz, ref_faces):
+    """(points [n, 3] float32, faces [f, 3] int32 or None, the four arguments points, n, faces, f of a psgsdf_*_reference call)"""
+    xyz = np.ascontiguousarray(ref_xyz, np.float32).reshape(-1, 3)
+    faces = None if ref_faces is None else np.ascontiguousarray(ref_faces, np.int32).reshape(-1, 3)
+    nf = 0 if faces is None else len(faces)
+    return xyz, faces, (xyz.ctypes.data_as(_F32P), C.c_int64(len(xyz)), faces.ctypes.data_as(_I32P) if nf else None, C.c_int64(nf))
+
+
 class PsgsdfError(RuntimeError):
     pass
 
@@ -317,15 +377,21 @@ class Api:
         zlo, zhi = max(0, z0 - 1), min(nz, z1 + 1)
         p = planes(zlo, zhi)
         self.upload_volume_slab(z0, z1, p["dist"], p["grad"], p["weight"], p["rgb"], p["vis"], sc.vis_words)
+        self._scene_keyframes(sc, u8)
+        self.init()
+        return z0, z1
+
+    def _scene_keyframes(self, sc, u8, require=False):
+        """a scene's keyframes, as 8-bit RGB if u8 (None: whenever the scene has them); require: asking for 8-bit images the scene has not is a ValueError"""
         has_u8 = getattr(sc, "images_u8", None) is not None
         if u8 is None:
             u8 = has_u8
         if u8:
+            if require and not has_u8:
+                raise ValueError("scene has no 8-bit images")
             self.set_keyframes_u8(sc.frame_idx, sc.images_u8, sc.image_scale, sc.poses)
         else:
             self.set_keyframes(sc.frame_idx, sc.images, sc.poses)
-        self.init()
-        return z0, z1
 
     def set_keyframes(self, frame_idx, images, poses):
         F, H, W, _ = images.shape
@@ -351,15 +417,7 @@ class Api:
     def load_scene(self, sc, u8=None):
         """u8: hand the keyframes over as 8-bit RGB when the scene has them (default: whenever it has)"""
         self.upload_volume(sc.dist, sc.grad, sc.weight, sc.rgb, sc.vis, sc.vis_words)
-        has_u8 = getattr(sc, "images_u8", None) is not None
-        if u8 is None:
-            u8 = has_u8
-        if u8:
-            if not has_u8:
-                raise ValueError("scene has no 8-bit images")
-            self.set_keyframes_u8(sc.frame_idx, sc.images_u8, sc.image_scale, sc.poses)
-        else:
-            self.set_keyframes(sc.frame_idx, sc.images, sc.poses)
+        self._scene_keyframes(sc, u8, require=True)
         self.init()
 
     def init(self):
@@ -431,8 +489,7 @@ class Api:
         n, res = C.c_int(), C.c_int()
         cb = None
         if on_iter is not None:
-            CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(IterStats))
-            cb = CB(lambda user, done, rec: 1 if on_iter(done, rec.contents.as_dict()) else 0)
+            cb = _ITER_CB(lambda user, done, rec: 1 if on_iter(done, rec.contents.as_dict()) else 0)
         self._check(self._fn("optimize")(self.ctx, C.c_int(flags), arr, C.c_int(cap), C.byref(n), C.byref(res), cb, None), "optimize")
         return [arr[i].as_dict() for i in range(min(n.value, cap))], bool(res.value)
 
@@ -445,8 +502,7 @@ class Api:
             self._observer = None
             self._check(self._fn("set_record_observer")(self.ctx, None, None), "set_record_observer")
             return
-        CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(IterStats))
-        self._observer = CB(lambda user, done, rec: 1 if fn(done, IterStats.from_buffer_copy(rec.contents)) else 0)      # (a 120-byte copy, fields read on demand: the callback sits on the loop's critical path)
+        self._observer = _ITER_CB(lambda user, done, rec: 1 if fn(done, IterStats.from_buffer_copy(rec.contents)) else 0)      # (a 120-byte copy, fields read on demand: the callback sits on the loop's critical path)
         self._check(self._fn("set_record_observer")(self.ctx, self._observer, None), "set_record_observer")
 
     def upsample2x(self):
@@ -457,6 +513,10 @@ class Api:
         i = Info()
         self._check(self._fn("get_info")(self.ctx, C.byref(i)), "get_info")
         return i
+
+    def _vs(self):
+        """the voxel size as the engine rounds it: the unit of the extraction calls' default radii and biases"""
+        return float(np.float32(self.info().voxel_size))
 
     def download_volume(self, want_vis=False):
         i = self.info()
@@ -517,13 +577,13 @@ class Api:
         depth, normal, albedo and voxel as render returns them.  Single contexts only."""
         v, W, H = self._view("relight", frame, pose, K, size)
         arr = (Light * max(len(lights), 1))(*[make_light(d) for d in lights])
-        vs = float(np.float32(self.info().voxel_size))
+        vs = self._vs()
         p = RelightParams(float(vs if bias is None else bias), float(0.0 if reach is None else reach), len(lights), 0)
         out = np.zeros((max(len(lights), 1), 4, H, W), np.float32)
         geo = np.zeros((8, H, W), np.float32) if geometry else None
         cnt = (RelightCounts * max(len(lights), 1))()
         self._check(self._fn("relight")(self.ctx, C.byref(v), arr, C.byref(p), out.ctypes.data_as(C.c_void_p), geo.ctypes.data_as(C.c_void_p) if geometry else None, cnt), "relight")
-        res = dict(rendered=out[:, :3].copy(), visibility=out[:, 3].copy(), counts=[{k: int(getattr(cnt[l], k)) for k, _ in RelightCounts._fields_} for l in range(len(lights))])
+        res = dict(rendered=out[:, :3].copy(), visibility=out[:, 3].copy(), counts=[_counts(cnt[l]) for l in range(len(lights))])
         if geometry:
             res.update(depth=geo[0].copy(), normal=geo[1:4].copy(), albedo=geo[4:7].copy(), voxel=geo[7].view(np.int32).copy())
         return res
@@ -538,53 +598,42 @@ class Api:
     # -- the writers' geometry, extracted on the device (valid until the next extraction: copied here)
     def extract_mesh(self):
         """(xyz [n_vertices, 3] float32 grid-local, rgb [n_vertices, 3] uint8): three consecutive vertices are one face (psgsdf_extract_mesh)"""
-        xyz = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); n = C.c_int64()
+        xyz, rgb, n = _F32P(), _U8P(), C.c_int64()
         self._check(self._fn("extract_mesh")(self.ctx, C.byref(xyz), C.byref(rgb), C.byref(n)), "extract_mesh")
-        if n.value == 0:
-            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
-        return np.ctypeslib.as_array(xyz, shape=(n.value, 3)).copy(), np.ctypeslib.as_array(rgb, shape=(n.value, 3)).copy()
+        return _owned(xyz, (n.value, 3), np.float32), _owned(rgb, (n.value, 3), np.uint8)
 
     def extract_mesh_indexed(self):
         """(xyz [V, 3] float32 grid-local, normals [V, 3] float32, rgb [V, 3] uint8, faces [F, 3] int32, first_vertex): the welded mesh of
         include/psgsdf_mesh.h.  On a context attached to a rank: a collective call returning this rank's share; face indices are global and
         first_vertex is the global number of the share's vertex 0."""
-        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)()
-        nv, nf, first = C.c_int64(), C.c_int64(), C.c_int64()
-        self._check(self._fn("extract_mesh_indexed")(self.ctx, C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(first)), "extract_mesh_indexed")
-        V, F = nv.value, nf.value
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
-        return arr(xyz, V, np.float32), arr(nrm, V, np.float32), arr(rgb, V, np.uint8), arr(fc, F, np.int32), first.value
+        m, first = _MeshHead(), C.c_int64()
+        self._check(self._fn("extract_mesh_indexed")(self.ctx, *m.refs(), C.byref(first)), "extract_mesh_indexed")
+        return (*m.arrays().values(), first.value)
 
     def extract_mesh_components(self, min_faces=0, min_area=0.0, keep_largest=0):
         """The welded mesh without the components the filter drops, and the table of ALL its components (include/psgsdf_mesh.h
         psgsdf_extract_mesh_components): dict of xyz [V, 3] float32, normals [V, 3] float32, rgb [V, 3] uint8, faces [F, 3] int32 (renumbered),
         vertex_component [V] int32 (index into components), components (structured array, MESH_COMPONENT_DTYPE).  A component passes if
         n_faces >= min_faces and area >= min_area; keep_largest > 0 keeps only that many of them, those with the most faces.  Single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest))
-        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)(); vc = C.POINTER(C.c_int32)()
-        comps = C.c_void_p(); nv, nf, nc = C.c_int64(), C.c_int64(), C.c_int64()
-        self._check(self._fn("extract_mesh_components")(self.ctx, C.byref(flt), C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf),
-                                                        C.byref(vc), C.byref(comps), C.byref(nc)), "extract_mesh_components")
-        V, F, K = nv.value, nf.value, nc.value
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
+        return self._mesh_components("extract_mesh_components", [C.byref(_mesh_filter(min_faces, min_area, keep_largest, always=True))])
+
+    def _mesh_components(self, name, args, more=()):
+        """a call that returns the welded mesh, its vertices' components and the component table after its own `args`, and `more` after those"""
+        m, vc, comps, nc = _MeshHead(), _I32P(), C.c_void_p(), C.c_int64()
+        self._check(self._fn(name)(self.ctx, *args, *m.refs(), C.byref(vc), C.byref(comps), C.byref(nc), *more), name)
+        K = nc.value
         table = np.frombuffer(C.string_at(comps, K * MESH_COMPONENT_DTYPE.itemsize), MESH_COMPONENT_DTYPE).copy() if K else np.zeros(0, MESH_COMPONENT_DTYPE)
-        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
-                    vertex_component=np.ctypeslib.as_array(vc, shape=(V,)).copy() if V else np.zeros(0, np.int32), components=table)
+        return dict(m.arrays(), vertex_component=_owned(vc, (m.n_vertices,), np.int32), components=table)
 
     def extract_mesh_lod(self, cell, min_faces=0, min_area=0.0, keep_largest=0):
         """A coarser mesh by vertex clustering (include/psgsdf_mesh.h psgsdf_extract_mesh_lod): the vertices of the welded mesh -- of the mesh
         extract_mesh_components(min_faces, min_area, keep_largest) returns, if one of the three is non-zero -- that fall into the same cube of
         edge `cell` (the mesh's units) become one vertex.  dict of xyz [V, 3] float32, normals [V, 3] float32, rgb [V, 3] uint8, faces [F, 3] int32,
         vertex_map [n_vertices_in] int32 (the output vertex of every input vertex, or -1), n_vertices_in, n_faces_in.  Single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
-        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)(); vm = C.POINTER(C.c_int32)()
-        nv, nf, nvi, nfi = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        self._check(self._fn("extract_mesh_lod")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv),
-                                                 C.byref(fc), C.byref(nf), C.byref(vm), C.byref(nvi), C.byref(nfi)), "extract_mesh_lod")
-        V, F, Vi = nv.value, nf.value, nvi.value
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
-        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
-                    vertex_map=np.ctypeslib.as_array(vm, shape=(Vi,)).copy() if Vi else np.zeros(0, np.int32), n_vertices_in=Vi, n_faces_in=nfi.value)
+        m, vm, nvi, nfi = _MeshHead(), _I32P(), C.c_int64(), C.c_int64()
+        self._check(self._fn("extract_mesh_lod")(self.ctx, _ref(_mesh_filter(min_faces, min_area, keep_largest)), C.c_double(float(cell)), *m.refs(),
+                                                 C.byref(vm), C.byref(nvi), C.byref(nfi)), "extract_mesh_lod")
+        return dict(m.arrays(), vertex_map=_owned(vm, (nvi.value,), np.int32), n_vertices_in=nvi.value, n_faces_in=nfi.value)
 
     def bake_lod(self, cell, res, reach=None, min_faces=0, min_area=0.0, keep_largest=0):
         """Albedo, normal and displacement maps baked onto the level-of-detail mesh (include/psgsdf_bake.h psgsdf_bake_lod): extract_mesh_lod's dict for
@@ -592,27 +641,30 @@ class Api:
         float32, displacement [H, W] float32, voxel [H, W] int32 (-1: no hit), face [H, W] int32 (-1: padding) and the counts n_texels, n_hits,
         n_hits_off_band, n_buried, n_misses.  res: texels along a triangle's edge; reach: how far outside the coarse triangle a texel's ray starts, in
         the mesh's units (None: cell).  Single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
-        b = Bake()
-        self._check(self._fn("bake_lod")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
-                                         C.c_double(float(cell if reach is None else reach)), C.byref(b)), "bake_lod")
-        return self._bake_dict(b)
+        return self._bake("bake_lod", (min_faces, min_area, keep_largest), cell, res, reach, None, Bake())
+
+    def _bake(self, name, flt, cell, res, reach, params, result):
+        """one of the psgsdf_bake_lod* calls: the arguments they share (flt: min_faces, min_area, keep_largest), the call's own params struct (or None:
+        it has none) and its result struct, a Bake or a struct that begins with one; _bake_dict of that bake, to which the caller adds its own planes"""
+        own = () if params is None else (C.byref(params),)
+        self._check(self._fn(name)(self.ctx, _ref(_mesh_filter(*flt)), C.c_double(float(cell)), C.c_int32(int(res)), C.c_double(float(cell if reach is None else reach)),
+                                   *own, C.byref(result)), name)
+        return self._bake_dict(result if isinstance(result, Bake) else result.bake)
 
     @staticmethod
     def _bake_dict(b):
-        V, F, Vi, W, H = b.n_vertices, b.n_faces, b.n_vertices_in, b.width, b.height
-        arr = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
-        out = dict(xyz=arr(b.xyz, (V, 3), np.float32), normals=arr(b.normals, (V, 3), np.float32), rgb=arr(b.rgb, (V, 3), np.uint8), faces=arr(b.faces, (F, 3), np.int32),
-                   vertex_map=arr(b.vertex_map, (Vi,), np.int32), n_vertices_in=Vi, n_faces_in=b.n_faces_in,
-                   uv=arr(b.uv, (F if W else 0, 3, 2), np.float32), width=W, height=H, albedo=arr(b.albedo, (H, W, 3), np.uint8), normal=arr(b.normal, (H, W, 3), np.float32),
-                   displacement=arr(b.displacement, (H, W), np.float32), voxel=arr(b.voxel, (H, W), np.int32), face=arr(b.face, (H, W), np.int32))
+        Vi, W, H = b.n_vertices_in, b.width, b.height
+        out = dict(_mesh_arrays(b), vertex_map=_owned(b.vertex_map, (Vi,), np.int32), n_vertices_in=Vi, n_faces_in=b.n_faces_in,
+                   uv=_owned(b.uv, (b.n_faces if W else 0, 3, 2), np.float32), width=W, height=H, albedo=_owned(b.albedo, (H, W, 3), np.uint8),
+                   normal=_owned(b.normal, (H, W, 3), np.float32), displacement=_owned(b.displacement, (H, W), np.float32), voxel=_owned(b.voxel, (H, W), np.int32),
+                   face=_owned(b.face, (H, W), np.int32))
         for k in ("n_texels", "n_hits", "n_hits_off_band", "n_buried", "n_misses"):
             out[k] = int(getattr(b, k))
         return out
 
     # -- ambient occlusion (include/psgsdf_occlusion.h)
     def _ao_params(self, n_dirs, radius, bias):
-        vs = float(np.float32(self.info().voxel_size))
+        vs = self._vs()
         return AoParams(int(n_dirs), 0, float(8 * vs if radius is None else radius), float(vs if bias is None else bias))
 
     def occlusion_points(self, xyz, normals, n_dirs=16, radius=None, bias=None):
@@ -625,28 +677,19 @@ class Api:
         if len(xyz) != len(normals):
             raise ValueError("occlusion_points: xyz and normals differ in length")
         n, p = len(xyz), self._ao_params(n_dirs, radius, bias)
-        mask = C.POINTER(C.c_uint64)(); occ = C.POINTER(C.c_uint8)(); dirs = C.POINTER(C.c_double)(); cnt = AoCounts()
-        self._check(self._fn("occlusion_points")(self.ctx, xyz.ctypes.data_as(C.POINTER(C.c_float)), normals.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(n), C.byref(p),
+        mask = C.POINTER(C.c_uint64)(); occ = _U8P(); dirs = C.POINTER(C.c_double)(); cnt = AoCounts()
+        self._check(self._fn("occlusion_points")(self.ctx, xyz.ctypes.data_as(_F32P), normals.ctypes.data_as(_F32P), C.c_int64(n), C.byref(p),
                                                  C.byref(mask), C.byref(occ), C.byref(dirs), C.byref(cnt)), "occlusion_points")
-        out = dict(occlusion=np.ctypeslib.as_array(occ, shape=(n,)).copy() if n else np.zeros(0, np.uint8),
-                   mask=np.ctypeslib.as_array(mask, shape=(n,)).copy() if n else np.zeros(0, np.uint64), dirs=np.ctypeslib.as_array(dirs, shape=(p.n_dirs, 3)).copy())
-        out["counts"] = {k: int(getattr(cnt, k)) for k, _ in AoCounts._fields_}
-        return out
+        return dict(occlusion=_owned(occ, (n,), np.uint8), mask=_owned(mask, (n,), np.uint64), dirs=_owned(dirs, (p.n_dirs, 3), np.float64), counts=_counts(cnt))
 
     def bake_lod_ao(self, cell, res, reach=None, n_dirs=16, radius=None, bias=None, min_faces=0, min_area=0.0, keep_largest=0):
         """bake_lod's dict for the same arguments (bit for bit) plus the ambient-occlusion map of the atlas (psgsdf_bake_lod_ao): occlusion [H, W]
         uint8 (255: open; padding 0), mask [H, W] uint64, dirs [n_dirs, 3] float64 and counts, a dict of n_samples (the owned texels), n_valid,
         n_rays, n_occluded, n_buried (rays; the bake's own n_buried, texels, stays where it is).  n_dirs, radius, bias: as for occlusion_points.  Single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
-        b, p = BakeAo(), self._ao_params(n_dirs, radius, bias)
-        self._check(self._fn("bake_lod_ao")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
-                                            C.c_double(float(cell if reach is None else reach)), C.byref(p), C.byref(b)), "bake_lod_ao")
-        out = self._bake_dict(b.bake)
-        W, H = b.bake.width, b.bake.height
-        out["occlusion"] = np.ctypeslib.as_array(b.occlusion, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint8)
-        out["mask"] = np.ctypeslib.as_array(b.mask, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint64)
-        out["dirs"] = np.ctypeslib.as_array(b.dirs, shape=(b.n_dirs, 3)).copy()
-        out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in AoCounts._fields_}
+        b = BakeAo()
+        out = self._bake("bake_lod_ao", (min_faces, min_area, keep_largest), cell, res, reach, self._ao_params(n_dirs, radius, bias), b)
+        H, W = out["height"], out["width"]
+        out.update(occlusion=_owned(b.occlusion, (H, W), np.uint8), mask=_owned(b.mask, (H, W), np.uint64), dirs=_owned(b.dirs, (b.n_dirs, 3), np.float64), counts=_counts(b.counts))
         return out
 
     # -- curvature of the reconstructed surface (include/psgsdf_curvature.h)
@@ -657,43 +700,32 @@ class Api:
         voxel unobserved, a zero gradient -- holds zeros.  Single contexts only."""
         lin = np.ascontiguousarray(lin, np.int64).reshape(-1)
         n = len(lin)
-        vl = C.POINTER(C.c_uint8)(); ptr = [C.POINTER(C.c_float)() for _ in range(5)]
+        vl = _U8P(); ptr = [_F32P() for _ in range(5)]
         self._check(self._fn("curvature_voxels")(self.ctx, lin.ctypes.data_as(C.POINTER(C.c_int64)) if n else None, C.c_int64(n), C.byref(vl), *[C.byref(p) for p in ptr]), "curvature_voxels")
-        col = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if n else np.zeros(shape, dt)
-        out = dict(valid=col(vl, (n,), np.uint8))
+        out = dict(valid=_owned(vl, (n,), np.uint8))
         for name, p in zip(("mean", "gauss", "k1", "k2"), ptr):
-            out[name] = col(p, (n,), np.float32)
-        out["dir1"] = col(ptr[4], (n, 3), np.float32)
+            out[name] = _owned(p, (n,), np.float32)
+        out["dir1"] = _owned(ptr[4], (n, 3), np.float32)
         return out
 
     def extract_mesh_curvature(self):
         """The welded mesh with the curvature of its vertices (psgsdf_extract_mesh_curvature): dict of xyz, normals, rgb, faces (extract_mesh_indexed's
         arrays) and valid [V] uint8 (how many of the vertex's end voxels are valid: 2, 1 or 0), mean, gauss, k1, k2 [V] float32, interpolated between
         the end voxels' results with the vertex's own parameter; zeros where valid == 0.  Single contexts only."""
-        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)()
-        vl = C.POINTER(C.c_uint8)(); ptr = [C.POINTER(C.c_float)() for _ in range(4)]; nv, nf = C.c_int64(), C.c_int64()
-        self._check(self._fn("extract_mesh_curvature")(self.ctx, C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(vl), *[C.byref(p) for p in ptr]),
-                    "extract_mesh_curvature")
-        V, F = nv.value, nf.value
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
-        col = lambda p, dt: np.ctypeslib.as_array(p, shape=(V,)).copy() if V else np.zeros(0, dt)
-        out = dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32), valid=col(vl, np.uint8))
+        m, vl, ptr = _MeshHead(), _U8P(), [_F32P() for _ in range(4)]
+        self._check(self._fn("extract_mesh_curvature")(self.ctx, *m.refs(), C.byref(vl), *[C.byref(p) for p in ptr]), "extract_mesh_curvature")
+        out = dict(m.arrays(), valid=_owned(vl, (m.n_vertices,), np.uint8))
         for name, p in zip(("mean", "gauss", "k1", "k2"), ptr):
-            out[name] = col(p, np.float32)
+            out[name] = _owned(p, (m.n_vertices,), np.float32)
         return out
 
     def bake_lod_curvature(self, cell, res, reach=None, min_faces=0, min_area=0.0, keep_largest=0):
         """bake_lod's dict for the same arguments (bit for bit) plus the mean curvature of every hit texel's voxel (psgsdf_bake_lod_curvature):
         mean [H, W] float32, valid [H, W] uint8 (0 / 0 on missed, buried and padding texels) and n_valid.  Single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
         b = BakeCurvature()
-        self._check(self._fn("bake_lod_curvature")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
-                                                   C.c_double(float(cell if reach is None else reach)), C.byref(b)), "bake_lod_curvature")
-        out = self._bake_dict(b.bake)
-        W, H = b.bake.width, b.bake.height
-        out["mean"] = np.ctypeslib.as_array(b.mean, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.float32)
-        out["valid"] = np.ctypeslib.as_array(b.valid, shape=(H, W)).copy() if W * H else np.zeros((H, W), np.uint8)
-        out["n_valid"] = int(b.n_valid)
+        out = self._bake("bake_lod_curvature", (min_faces, min_area, keep_largest), cell, res, reach, None, b)
+        H, W = out["height"], out["width"]
+        out.update(mean=_owned(b.mean, (H, W), np.float32), valid=_owned(b.valid, (H, W), np.uint8), n_valid=int(b.n_valid))
         return out
 
     # -- unobserved voxels filled, and the closed mesh of the filled state (include/psgsdf_fill.h)
@@ -701,28 +733,20 @@ class Api:
         """The unobserved voxels within `rounds` city-block steps of an observed one, filled by front propagation of the first-order model
         d + g . dx and relaxed by `sweeps` Jacobi sweeps (psgsdf_fill_voxels): dict of lin [n] int64 (ascending), dist [n], grad [n, 3], rgb [n, 3]
         float32 and round [n] uint8 (the round a voxel was reached in, 1 .. rounds).  The context's state does not change.  Single contexts only."""
-        lin = C.POINTER(C.c_int64)(); ptr = [C.POINTER(C.c_float)() for _ in range(3)]; rnd = C.POINTER(C.c_uint8)(); n = C.c_int64()
+        lin = C.POINTER(C.c_int64)(); ptr = [_F32P() for _ in range(3)]; rnd = _U8P(); n = C.c_int64()
         self._check(self._fn("fill_voxels")(self.ctx, C.c_int32(int(rounds)), C.c_int32(int(sweeps)), C.byref(lin), *[C.byref(p) for p in ptr], C.byref(rnd), C.byref(n)), "fill_voxels")
         n = n.value
-        col = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if n else np.zeros(shape, dt)
-        return dict(lin=col(lin, (n,), np.int64), dist=col(ptr[0], (n,), np.float32), grad=col(ptr[1], (n, 3), np.float32), rgb=col(ptr[2], (n, 3), np.float32),
-                    round=col(rnd, (n,), np.uint8))
+        return dict(lin=_owned(lin, (n,), np.int64), dist=_owned(ptr[0], (n,), np.float32), grad=_owned(ptr[1], (n, 3), np.float32), rgb=_owned(ptr[2], (n, 3), np.float32),
+                    round=_owned(rnd, (n,), np.uint8))
 
     def extract_mesh_filled(self, rounds, sweeps=4, min_faces=0, min_area=0.0, keep_largest=0):
         """extract_mesh_components' dict for the state with its unobserved voxels filled as fill_voxels(rounds, sweeps) fills them
         (psgsdf_extract_mesh_filled), plus vertex_filled [V] uint8: how many of the vertex's end voxels are filled, 0, 1 or 2.  rounds = 0 gives
         extract_mesh_components' arrays bit for bit.  Single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
-        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)(); vc = C.POINTER(C.c_int32)(); vf = C.POINTER(C.c_uint8)()
-        comps = C.c_void_p(); nv, nf, nc = C.c_int64(), C.c_int64(), C.c_int64()
-        self._check(self._fn("extract_mesh_filled")(self.ctx, C.c_int32(int(rounds)), C.c_int32(int(sweeps)), C.byref(flt) if flt is not None else None, C.byref(xyz), C.byref(nrm),
-                                                    C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(vc), C.byref(comps), C.byref(nc), C.byref(vf)), "extract_mesh_filled")
-        V, F, K = nv.value, nf.value, nc.value
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
-        table = np.frombuffer(C.string_at(comps, K * MESH_COMPONENT_DTYPE.itemsize), MESH_COMPONENT_DTYPE).copy() if K else np.zeros(0, MESH_COMPONENT_DTYPE)
-        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
-                    vertex_component=np.ctypeslib.as_array(vc, shape=(V,)).copy() if V else np.zeros(0, np.int32), components=table,
-                    vertex_filled=np.ctypeslib.as_array(vf, shape=(V,)).copy() if V else np.zeros(0, np.uint8))
+        vf = _U8P()
+        out = self._mesh_components("extract_mesh_filled", [C.c_int32(int(rounds)), C.c_int32(int(sweeps)), _ref(_mesh_filter(min_faces, min_area, keep_largest))], [C.byref(vf)])
+        out["vertex_filled"] = _owned(vf, (len(out["xyz"]),), np.uint8)
+        return out
 
     # -- the albedo texture solved from the keyframes (include/psgsdf_photo.h)
     def bake_lod_photo(self, cell, res, reach=None, bias=None, cos_min=0.2, shade_min=0.05, status=False, min_faces=0, min_area=0.0, keep_largest=0):
@@ -732,19 +756,12 @@ class Api:
         n_samples, n_pairs, n_used, n_outside, n_grazing, n_occluded, n_buried, n_dark, n_texels_solved.  A keyframe counts for a texel if the
         texel projects into it, its normal makes a cosine > cos_min with the direction to the camera, the ray towards the camera (lifted off the
         surface by `bias`; None: 1 voxel) is free, and the model's shading is >= shade_min.  After init; single contexts only."""
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
-        vs = float(np.float32(self.info().voxel_size))
+        vs = self._vs()
         b, p = BakePhoto(), PhotoParams(float(vs if bias is None else bias), float(cos_min), float(shade_min), 1 if status else 0, 0)
-        self._check(self._fn("bake_lod_photo")(self.ctx, C.byref(flt) if flt is not None else None, C.c_double(float(cell)), C.c_int32(int(res)),
-                                               C.c_double(float(cell if reach is None else reach)), C.byref(p), C.byref(b)), "bake_lod_photo")
-        out = self._bake_dict(b.bake)
-        W, H, F = b.bake.width, b.bake.height, b.n_frames
-        arr = lambda ptr, shape, dt: np.ctypeslib.as_array(ptr, shape=shape).copy() if W * H else np.zeros(shape, dt)
-        out["photo"] = arr(b.photo, (H, W, 3), np.float32)
-        out["photo_rgb"] = arr(b.photo_rgb, (H, W, 3), np.uint8)
-        out["n_obs"] = arr(b.n_obs, (H, W), np.int32)
-        out["status"] = arr(b.status, (F, H, W), np.uint8) if status else None
-        out["counts"] = {k: int(getattr(b.counts, k)) for k, _ in PhotoCounts._fields_}
+        out = self._bake("bake_lod_photo", (min_faces, min_area, keep_largest), cell, res, reach, p, b)
+        H, W = out["height"], out["width"]
+        out.update(photo=_owned(b.photo, (H, W, 3), np.float32), photo_rgb=_owned(b.photo_rgb, (H, W, 3), np.uint8), n_obs=_owned(b.n_obs, (H, W), np.int32),
+                   status=_owned(b.status, (b.n_frames, H, W), np.uint8) if status else None, counts=_counts(b.counts))
         return out
 
     # -- comparison with a reference mesh or cloud (include/psgsdf_compare.h)
@@ -756,21 +773,15 @@ class Api:
         (inf: unmatched), vertex_nearest [V] int32 (a reference face or point, -1: none), vertex_side [V] int8; ref_dist, ref_nearest (a face of the
         mesh), ref_side [n] the other way; to_reference and to_reconstruction, dicts of psgsdf_compare_side's fields (hist: [16] int64); precision,
         recall, fscore.  Single contexts only."""
-        ref_xyz = np.ascontiguousarray(ref_xyz, np.float32).reshape(-1, 3)
-        faces = None if ref_faces is None else np.ascontiguousarray(ref_faces, np.int32).reshape(-1, 3)
-        vs = float(np.float32(self.info().voxel_size))
+        ref_xyz, faces, ref = _reference(ref_xyz, ref_faces)
+        vs = self._vs()
         p = CompareParams(float(8 * vs if max_dist is None else max_dist), float(vs if tau is None else tau), float(grid_cell), (C.c_int32 * 2)(0, 0))
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
         r = Compare()
-        self._check(self._fn("compare_reference")(self.ctx, C.byref(flt) if flt is not None else None, ref_xyz.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(len(ref_xyz)),
-                                                  faces.ctypes.data_as(C.POINTER(C.c_int32)) if faces is not None and len(faces) else None,
-                                                  C.c_int64(0 if faces is None else len(faces)), C.byref(p), C.byref(r)), "compare_reference")
-        V, F, n = r.n_vertices, r.n_faces, len(ref_xyz)
-        arr = lambda ptr, shape, dt: np.ctypeslib.as_array(ptr, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
-        out = dict(xyz=arr(r.xyz, (V, 3), np.float32), normals=arr(r.normals, (V, 3), np.float32), rgb=arr(r.rgb, (V, 3), np.uint8), faces=arr(r.faces, (F, 3), np.int32),
-                   vertex_dist=arr(r.vertex_dist, (V,), np.float32), vertex_nearest=arr(r.vertex_nearest, (V,), np.int32), vertex_side=arr(r.vertex_side, (V,), np.int8),
-                   ref_dist=arr(r.ref_dist, (n,), np.float32), ref_nearest=arr(r.ref_nearest, (n,), np.int32), ref_side=arr(r.ref_side, (n,), np.int8),
-                   precision=float(r.precision), recall=float(r.recall), fscore=float(r.fscore))
+        self._check(self._fn("compare_reference")(self.ctx, _ref(_mesh_filter(min_faces, min_area, keep_largest)), *ref, C.byref(p), C.byref(r)), "compare_reference")
+        V, n = r.n_vertices, len(ref_xyz)
+        out = dict(_mesh_arrays(r), vertex_dist=_owned(r.vertex_dist, (V,), np.float32), vertex_nearest=_owned(r.vertex_nearest, (V,), np.int32),
+                   vertex_side=_owned(r.vertex_side, (V,), np.int8), ref_dist=_owned(r.ref_dist, (n,), np.float32), ref_nearest=_owned(r.ref_nearest, (n,), np.int32),
+                   ref_side=_owned(r.ref_side, (n,), np.int8), precision=float(r.precision), recall=float(r.recall), fscore=float(r.fscore))
         for name in ("to_reference", "to_reconstruction"):
             s = getattr(r, name)
             out[name] = {k: (np.array(s.hist, np.int64) if k == "hist" else getattr(s, k)) for k, _ in CompareSide._fields_}
@@ -787,68 +798,52 @@ class Api:
         dicts: radius, rms, n_pairs, min_pivot, step [6]; after TOO_FEW / DEGENERATE one more entry, the state that refused), system0 [28],
         final (a dict like iters'), aligned_xyz [n, 3] float32 (the reference under transform) and the compared mesh xyz, normals, rgb, faces.
         Single contexts only."""
-        ref_xyz = np.ascontiguousarray(ref_xyz, np.float32).reshape(-1, 3)
-        faces = None if ref_faces is None else np.ascontiguousarray(ref_faces, np.int32).reshape(-1, 3)
-        vs = float(np.float32(self.info().voxel_size))
+        ref_xyz, faces, ref = _reference(ref_xyz, ref_faces)
+        vs = self._vs()
         T = np.eye(4) if init is None else np.ascontiguousarray(init, np.float64).reshape(4, 4)
         p = AlignParams((C.c_double * 16)(*T.ravel()), float(8 * vs if max_dist is None else max_dist), float(vs if min_dist is None else min_dist), float(shrink), float(eps_rot),
                         float(1e-3 * vs if eps_trans is None else eps_trans), float(grid_cell), int(directions), int(max_iters), (C.c_int32 * 2)(0, 0))
-        flt = MeshFilter(int(min_faces), float(min_area), int(keep_largest)) if (min_faces or min_area or keep_largest) else None
         r = Align()
-        self._check(self._fn("align_reference")(self.ctx, C.byref(flt) if flt is not None else None, ref_xyz.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(len(ref_xyz)),
-                                                faces.ctypes.data_as(C.POINTER(C.c_int32)) if faces is not None and len(faces) else None,
-                                                C.c_int64(0 if faces is None else len(faces)), C.byref(p), C.byref(r)), "align_reference")
-        V, F, n = r.n_vertices, r.n_faces, len(ref_xyz)
-        arr = lambda ptr, shape, dt: np.ctypeslib.as_array(ptr, shape=shape).copy() if int(np.prod(shape)) else np.zeros(shape, dt)
+        self._check(self._fn("align_reference")(self.ctx, _ref(_mesh_filter(min_faces, min_area, keep_largest)), *ref, C.byref(p), C.byref(r)), "align_reference")
         shown = r.n_iters + (1 if r.status in (ALIGN_DEGENERATE, ALIGN_TOO_FEW) and r.n_iters < 64 and p.max_iters > 0 else 0)
         return dict(transform=np.array(r.transform, np.float64).reshape(4, 4), centre=np.array(r.centre, np.float64), status=int(r.status), n_iters=int(r.n_iters),
                     iters=[r.iters[k].as_dict() for k in range(shown)], system0=np.array(r.system0, np.float64), final=r.final.as_dict(),
-                    aligned_xyz=arr(r.aligned_xyz, (n, 3), np.float32), xyz=arr(r.xyz, (V, 3), np.float32), normals=arr(r.normals, (V, 3), np.float32),
-                    rgb=arr(r.rgb, (V, 3), np.uint8), faces=arr(r.faces, (F, 3), np.int32))
+                    aligned_xyz=_owned(r.aligned_xyz, (len(ref_xyz), 3), np.float32), **_mesh_arrays(r))
 
     # -- the photometric fit resolved over the surface (include/psgsdf_fit.h)
     def band_fit(self):
         """Per band row, in download_band's order (psgsdf_band_fit): dict of n_obs [n_band] int32 (the observations the energy counts), loss [n_band]
         float64 (the row's share of the sum behind energy()[0]: sum(loss) / n_band is E_ps), sum_r2 [n_band, 3] float32 (squared residuals per channel).
         Single contexts only."""
-        no = C.POINTER(C.c_int32)(); ls = C.POINTER(C.c_double)(); r2 = C.POINTER(C.c_float)(); n = C.c_int64()
+        no = _I32P(); ls = C.POINTER(C.c_double)(); r2 = _F32P(); n = C.c_int64()
         self._check(self._fn("band_fit")(self.ctx, C.byref(no), C.byref(ls), C.byref(r2), C.byref(n)), "band_fit")
         S = n.value
-        if S == 0:
-            return dict(n_obs=np.zeros(0, np.int32), loss=np.zeros(0, np.float64), sum_r2=np.zeros((0, 3), np.float32))
-        return dict(n_obs=np.ctypeslib.as_array(no, shape=(S,)).copy(), loss=np.ctypeslib.as_array(ls, shape=(S,)).copy(), sum_r2=np.ctypeslib.as_array(r2, shape=(S, 3)).copy())
+        return dict(n_obs=_owned(no, (S,), np.int32), loss=_owned(ls, (S,), np.float64), sum_r2=_owned(r2, (S, 3), np.float32))
 
     def extract_mesh_fit(self):
         """The welded mesh with the fit of its vertices (psgsdf_extract_mesh_fit): dict of xyz, normals, rgb, faces (extract_mesh_indexed's arrays) and
         n_obs [V] int32, rms [V] float32, loss [V] float32 -- the observations of the vertex's end voxels, their rms residual and mean robust loss; zeros
         where nothing was observed.  Single contexts only."""
-        xyz = C.POINTER(C.c_float)(); nrm = C.POINTER(C.c_float)(); rgb = C.POINTER(C.c_uint8)(); fc = C.POINTER(C.c_int32)()
-        no = C.POINTER(C.c_int32)(); rms = C.POINTER(C.c_float)(); ls = C.POINTER(C.c_float)(); nv, nf = C.c_int64(), C.c_int64()
-        self._check(self._fn("extract_mesh_fit")(self.ctx, C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(nv), C.byref(fc), C.byref(nf), C.byref(no), C.byref(rms), C.byref(ls)), "extract_mesh_fit")
-        V, F = nv.value, nf.value
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n, 3)).copy() if n else np.zeros((0, 3), dt)
-        col = lambda p, dt: np.ctypeslib.as_array(p, shape=(V,)).copy() if V else np.zeros(0, dt)
-        return dict(xyz=arr(xyz, V, np.float32), normals=arr(nrm, V, np.float32), rgb=arr(rgb, V, np.uint8), faces=arr(fc, F, np.int32),
-                    n_obs=col(no, np.int32), rms=col(rms, np.float32), loss=col(ls, np.float32))
+        m, no, rms, ls = _MeshHead(), _I32P(), _F32P(), _F32P()
+        self._check(self._fn("extract_mesh_fit")(self.ctx, *m.refs(), C.byref(no), C.byref(rms), C.byref(ls)), "extract_mesh_fit")
+        V = m.n_vertices
+        return dict(m.arrays(), n_obs=_owned(no, (V,), np.int32), rms=_owned(rms, (V,), np.float32), loss=_owned(ls, (V,), np.float32))
 
     def extract_pointcloud(self, which=0):
         """(xyz_nxyz [n, 6] float32, rgb [n, 3] int32); which = 0: the band voxels, 1: every fused voxel (psgsdf_extract_pointcloud)"""
-        pn = C.POINTER(C.c_float)(); col = C.POINTER(C.c_int32)(); n = C.c_int64()
+        pn, col, n = _F32P(), _I32P(), C.c_int64()
         self._check(self._fn("extract_pointcloud")(self.ctx, C.c_int(which), C.byref(pn), C.byref(col), C.byref(n)), "extract_pointcloud")
-        if n.value == 0:
-            return np.zeros((0, 6), np.float32), np.zeros((0, 3), np.int32)
-        return np.ctypeslib.as_array(pn, shape=(n.value, 6)).copy(), np.ctypeslib.as_array(col, shape=(n.value, 3)).copy()
+        return _owned(pn, (n.value, 6), np.float32), _owned(col, (n.value, 3), np.int32)
 
     def extract_sdf(self):
         """(lo [3], dim [3], -dist block [dim2, dim1, dim0]) of the crop box |d| <= sqrt(3) vs (psgsdf_extract_sdf)"""
-        lo = (C.c_int32 * 3)(); dim = (C.c_int32 * 3)(); v = C.POINTER(C.c_float)()
+        lo = (C.c_int32 * 3)(); dim = (C.c_int32 * 3)(); v = _F32P()
         self._check(self._fn("extract_sdf")(self.ctx, lo, dim, C.byref(v)), "extract_sdf")
         d = list(dim)
         mi = self.mg_info()      # a slab of a multi-rank run gets the planes of the (global) box it owns
         own = max(0, min(lo[2] + d[2], mi["z1"]) - max(lo[2], mi["z0"])) if mi["n_ranks"] > 1 else d[2]
-        if d[0] == 0 or own == 0:
-            return list(lo), d, np.zeros((0, max(d[1], 0), max(d[0], 0)), np.float32)
-        return list(lo), d, np.ctypeslib.as_array(v, shape=(own, d[1], d[0])).copy()
+        empty = d[0] == 0 or own == 0
+        return list(lo), d, _owned(v, (0, max(d[1], 0), max(d[0], 0)) if empty else (own, d[1], d[0]), np.float32)
 
     def download_band(self, n=None):
         """one rank: the whole band.  A slab of a multi-rank run: pass n = row1 - row0 of mg_info (its own band voxels)"""

@@ -1,10 +1,9 @@
 """worker of tests/test_mesh_indexed_gpu.py: one rank of a world-N context (the engine's socket transport) that brings a synthetic scene to a state
 and records its share of the welded mesh (psgsdf_extract_mesh_indexed, a collective call) and its planes of the volume.
 
-    python _mesh_ranks_worker.py RANK WORLD SPEC.json OUT.npz      (peer sockets: MESH_FDS, CU range: MESH_CU_MASKS)
+    python _mesh_ranks_worker.py RANK WORLD SPEC.json OUT.npz      (started by tests/_ranks.py run_spec: peer sockets and CU range in its variables)
 spec: model, N, F, mode = iterate (2 iterations) | refine (2 iterations, the 2x refinement, 1 more) | fuse_rebalance (slab-parallel fusion, re-cut, 1 iteration)
 """
-import faulthandler
 import json
 import os
 import sys
@@ -16,13 +15,11 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main(rank, world, spec, out):
-    faulthandler.dump_traceback_later(int(spec.get("timeout", 100)), exit=True)
-    if os.environ.get("MESH_CU_MASKS"):      # ranks sharing the one GPU on disjoint CU ranges
-        os.environ["PSGSDF_CU_MASK"] = os.environ["MESH_CU_MASKS"].split(",")[rank]
+    import _ranks
+    _ranks.arm(rank, spec)
     from psgradientsdf_amd import capi, synth
     sc = synth.make_scene(N=spec["N"], F=spec["F"], W=160, H=120, model=spec["model"])
-    eng = capi.load_engine(sc, sc.K, capi.default_settings(sc.model_id), 0)
-    eng.comm_init_sockets([int(x) for x in os.environ["MESH_FDS"].split(",")], rank, world)
+    eng = _ranks.engine(sc, rank, world)
     mode = spec["mode"]
     if mode == "fuse_rebalance":      # every rank fuses every frame into the planes it holds, then the slabs are re-cut
         eng.volume_init(sc.F)

@@ -2,9 +2,8 @@
 collective: the ranks listed in spec["callers"] make them, the others do not, and nobody may wait for anybody.  Afterwards every rank takes part in
 the collective psgsdf_extract_mesh_indexed, which must still work.
 
-    python _refused_ranks_worker.py RANK WORLD SPEC.json OUT.json      (peer sockets: MESH_FDS, CU range: MESH_CU_MASKS)
+    python _refused_ranks_worker.py RANK WORLD SPEC.json OUT.json      (started by tests/_ranks.py run_spec: peer sockets and CU range in its variables)
 """
-import faulthandler
 import json
 import os
 import sys
@@ -24,6 +23,11 @@ def _with_reference(name):
     return calls
 
 
+def _curvature(eng, vs, N):
+    lin = np.arange(N ** 3 // 2, N ** 3 // 2 + 5, dtype=np.int64)
+    return [lambda: eng.curvature_voxels(lin), eng.extract_mesh_curvature, lambda: eng.bake_lod_curvature(2 * vs, 4), lambda: eng.bake_lod_curvature(2 * vs, 4, keep_largest=1)]
+
+
 def _occlusion(eng, vs, N):
     pts = np.full((5, 3), 0.5 * N * vs, np.float32); nrm = np.tile(np.float32([0, 0, 1]), (5, 1))
     return [lambda: eng.occlusion_points(pts, nrm), lambda: eng.bake_lod_ao(2 * vs, 4), lambda: eng.bake_lod_ao(2 * vs, 4, keep_largest=1)]
@@ -34,6 +38,8 @@ FAMILIES = {
     "align": ((160, 120), _with_reference("align_reference")),
     "bake": ((160, 120), lambda eng, vs, N: [lambda: eng.bake_lod(2 * vs, 4), lambda: eng.bake_lod(2 * vs, 4, keep_largest=1)]),
     "compare": ((160, 120), _with_reference("compare_reference")),
+    "curvature": ((64, 48), _curvature),
+    "fill": ((64, 48), lambda eng, vs, N: [lambda: eng.fill_voxels(2, 1), lambda: eng.extract_mesh_filled(2, 1)]),
     "fit": ((64, 48), lambda eng, vs, N: [eng.band_fit, eng.extract_mesh_fit]),
     "mesh_components": ((160, 120), lambda eng, vs, N: [lambda: eng.extract_mesh_components(), lambda: eng.extract_mesh_components(keep_largest=1)]),
     "mesh_lod": ((160, 120), lambda eng, vs, N: [lambda: eng.extract_mesh_lod(2 * vs), lambda: eng.extract_mesh_lod(2 * vs, keep_largest=1)]),
@@ -44,14 +50,12 @@ FAMILIES = {
 
 
 def main(rank, world, spec, out):
-    faulthandler.dump_traceback_later(int(spec.get("timeout", 100)), exit=True)
-    if os.environ.get("MESH_CU_MASKS"):      # ranks sharing the one GPU on disjoint CU ranges
-        os.environ["PSGSDF_CU_MASK"] = os.environ["MESH_CU_MASKS"].split(",")[rank]
+    import _ranks
+    _ranks.arm(rank, spec)
     from psgradientsdf_amd import capi, synth
     (W, H), calls = FAMILIES[spec["family"]]
     sc = synth.make_scene(N=spec["N"], F=spec["F"], W=W, H=H, model="SH1")
-    eng = capi.load_engine(sc, sc.K, capi.default_settings(sc.model_id), 0)
-    eng.comm_init_sockets([int(x) for x in os.environ["MESH_FDS"].split(",")], rank, world)
+    eng = _ranks.engine(sc, rank, world)
     eng.load_scene(sc)
     eng.init_albedo()
     errors = []

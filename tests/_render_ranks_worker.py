@@ -1,9 +1,8 @@
 """worker of tests/test_render_ranks_gpu.py: one rank of a world-N context (the engine's socket transport; N = 1: a plain single-rank context) that
 loads a synthetic scene -- or a stitched state -- and records what the collective render calls return, or runs a few iterations and records the state.
 
-    python _render_ranks_worker.py RANK WORLD SPEC.json OUT.npz      (peer sockets: RENDER_FDS, CU range: RENDER_CU_MASKS)
+    python _render_ranks_worker.py RANK WORLD SPEC.json OUT.npz      (started by tests/_ranks.py run_spec: peer sockets and CU range in its variables)
 """
-import faulthandler
 import json
 import os
 import sys
@@ -49,9 +48,8 @@ def cameras(eng, world):
 
 
 def main(rank, world, spec, out):
-    faulthandler.dump_traceback_later(int(spec.get("timeout", 100)), exit=True)
-    if os.environ.get("RENDER_CU_MASKS"):      # ranks sharing the one GPU on disjoint CU ranges
-        os.environ["PSGSDF_CU_MASK"] = os.environ["RENDER_CU_MASKS"].split(",")[rank]
+    import _ranks
+    _ranks.arm(rank, spec)
     from psgradientsdf_amd import capi, synth
     model = spec["model"]
     sc = synth.make_scene(N=spec["N"], F=spec["F"], W=spec["W"], H=spec["H"], model=model, u8=spec["u8"])
@@ -62,9 +60,7 @@ def main(rank, world, spec, out):
         z = np.load(spec["state"])
         sc.dist, sc.grad, sc.weight, sc.rgb = (np.ascontiguousarray(z[k]).reshape(np.shape(getattr(sc, k))) for k in ("dist", "grad", "weight", "rgb"))
         sc.poses = np.ascontiguousarray(z["poses"]); light = z["light"]
-    eng = capi.load_engine(sc, sc.K, capi.default_settings(sc.model_id), 0)
-    if world > 1:
-        eng.comm_init_sockets([int(x) for x in os.environ["RENDER_FDS"].split(",")], rank, world)
+    eng = _ranks.engine(sc, rank, world)
     eng.load_scene(sc, u8=spec["u8"])
     if light is None:      # the light is loaded (the scene's own: LED [3], SH [F][nb]), not initialised from the (rank-order) sums of the volume
         light = sc.light_gt

@@ -6,19 +6,18 @@ Every operation of the definition is an IEEE double operation, so the device is 
 Largest distance measured on the MI355X over the cases below: 0 ulp (profiles/curvature_mi355x.md)."""
 import filecmp
 import functools
-import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import _curvature_ref as cref
+from _refused_ranks import refused_ranks
 from psgradientsdf_amd import capi, synth
 from test_curvature_cpu import N, SHAPES, VS, assert_analytic, assert_header_matches_columns, read_ply_curvature, shape_volume
 from test_mesh_indexed_cpu import read_ply_indexed
-from test_mesh_indexed_gpu import EXE, NCU, _socket_mesh, analytic_engine, ulps, voxelps_config
+from test_mesh_indexed_gpu import EXE, analytic_engine, ulps, voxelps_config
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -254,28 +253,8 @@ def test_errors(built):
 
 def test_ranks_are_refused_before_any_exchange(built, tmp_path):
     """on a context attached to a rank: PSGSDF_ERR_UNSUPPORTED at once -- only rank 1 calls, so a collective refusal would hang -- and the context
-    goes on working (the collective psgsdf_extract_mesh_indexed afterwards).  tests/_refused_ranks.py's driver with this family's worker."""
-    world, timeout = 2, 150
-    sp = str(tmp_path / "spec.json"); json.dump({"family": "curvature", "N": 32, "F": 3, "callers": [1], "timeout": timeout - 20}, open(sp, "w"))
-    mesh = _socket_mesh(world)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MESH_CU_MASKS=",".join(f"{r * NCU // world}:{(r + 1) * NCU // world}" for r in range(world)))
-    outs = [str(tmp_path / f"rank{r}.json") for r in range(world)]
-    worker = os.path.join(ROOT, "tests", "_curvature_ranks_worker.py")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), sp, outs[r]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(env, MESH_FDS=",".join(str(f) for f in mesh[r])), pass_fds=[f for f in mesh[r] if f >= 0]) for r in range(world)]
-    for row in mesh:
-        for f in row:
-            if f >= 0:
-                os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    res = [json.load(open(o)) for o in outs]
+    goes on working (the collective psgsdf_extract_mesh_indexed afterwards).  tests/_refused_ranks.py's driver with this family."""
+    res = refused_ranks(tmp_path, "curvature", N=32, F=3)
     assert res[0]["errors"] == [] and len(res[1]["errors"]) == 4
     for e, name in zip(res[1]["errors"], ("curvature_voxels", "extract_mesh_curvature", "bake_lod_curvature", "bake_lod_curvature")):
         assert "rc=-3" in e and "rank 1 of 2" in e and name in e, e

@@ -4,22 +4,19 @@ holes, the empty cases, multi-rank shares, voxelPS --indexed-mesh, and the kerne
 import filecmp
 import json
 import os
-import socket
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import _mesh_ref as ref
+from _ranks import NCU, run_spec, stitch
 from psgradientsdf_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "psgradientsdf_amd", "host", "voxelPS")
 GOLD = os.path.join(ROOT, "tests", "golden", "sokrates_small")
-WORKER = os.path.join(ROOT, "tests", "_mesh_ranks_worker.py")
-NCU = 256      # MI355X
 
 
 def ulps(a, b):
@@ -183,44 +180,8 @@ def test_empty_volume_state_error_and_reproducible(built):
     assert len(xyz) == 0 and len(faces) == 0 and first == 0
 
 
-def _socket_mesh(world):
-    mesh = [[-1] * world for _ in range(world)]
-    for r in range(world):
-        for q in range(r + 1, world):
-            a, b = socket.socketpair(socket.AF_UNIX, socket.SOCK_STREAM)
-            mesh[r][q], mesh[q][r] = a.detach(), b.detach()
-    return mesh
-
-
 def run_ranks(tmp_path, world, timeout=150, **spec):
-    spec.setdefault("timeout", timeout - 20)
-    sp = str(tmp_path / "spec.json"); json.dump(spec, open(sp, "w"))
-    mesh = _socket_mesh(world)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MESH_CU_MASKS=",".join(f"{r * NCU // world}:{(r + 1) * NCU // world}" for r in range(world)))
-    outs = [str(tmp_path / f"rank{r}.npz") for r in range(world)]
-    procs = [subprocess.Popen([sys.executable, WORKER, str(r), str(world), sp, outs[r]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(env, MESH_FDS=",".join(str(f) for f in mesh[r])), pass_fds=[f for f in mesh[r] if f >= 0]) for r in range(world)]
-    for row in mesh:
-        for f in row:
-            if f >= 0:
-                os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [dict(np.load(o)) for o in outs]
-
-
-def stitch(res, key):
-    out = np.full_like(res[0][key], np.nan)
-    for got in res:
-        m = ~np.isnan(got[key]); out[m] = got[key][m]
-    assert not np.isnan(out).any()
-    return out
+    return [dict(np.load(o)) for o in run_spec("_mesh_ranks_worker.py", tmp_path, "mesh", "npz", world, timeout, spec)]
 
 
 @pytest.mark.parametrize("world,mode,N", [(2, "iterate", 48), (3, "refine", 32), (4, "fuse_rebalance", 48), (3, "iterate", 40)])

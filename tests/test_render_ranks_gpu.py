@@ -3,63 +3,19 @@ GPU on disjoint CU ranges and meet through the engine's socket transport.  Every
 the same state returns, bit for bit (planes compared as uint32, stats as float64 bits), while each rank holds only its slab."""
 import json
 import os
-import socket
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from _ranks import NCU, run_spec, stitch
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "_render_ranks_worker.py")
-NCU = 256      # MI355X
-
-
-def _mesh(world):
-    mesh = [[-1] * world for _ in range(world)]
-    for r in range(world):
-        for q in range(r + 1, world):
-            a, b = socket.socketpair(socket.AF_UNIX, socket.SOCK_STREAM)
-            mesh[r][q], mesh[q][r] = a.detach(), b.detach()
-    return mesh
 
 
 def run(tmp_path, tag, world, timeout=120, **spec):
     """world ranks of the worker (1: a plain single-rank context); returns every rank's npz"""
-    spec.setdefault("timeout", timeout - 20)
-    sp = str(tmp_path / f"{tag}.json"); json.dump(spec, open(sp, "w"))
-    mesh = _mesh(world) if world > 1 else None
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    if world > 1:
-        env["RENDER_CU_MASKS"] = ",".join(f"{r * NCU // world}:{(r + 1) * NCU // world}" for r in range(world))
-    outs = [str(tmp_path / f"{tag}.rank{r}.npz") for r in range(world)]
-    procs = [subprocess.Popen([sys.executable, WORKER, str(r), str(world), sp, outs[r]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                              env=dict(env, RENDER_FDS=",".join(str(f) for f in mesh[r])) if mesh else env, pass_fds=[f for f in mesh[r] if f >= 0] if mesh else ())
-             for r in range(world)]
-    if mesh:
-        for row in mesh:
-            for f in row:
-                if f >= 0:
-                    os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [dict(np.load(o)) for o in outs]
-
-
-def stitch(res, key):
-    """the slabs tile the volume: every rank filled the z-planes it owns, NaN elsewhere"""
-    out = np.full_like(res[0][key], np.nan)
-    for got in res:
-        m = ~np.isnan(got[key]); assert not (m & ~np.isnan(out)).any(); out[m] = got[key][m]
-    assert not np.isnan(out).any()
-    return out
+    return [dict(np.load(o)) for o in run_spec("_render_ranks_worker.py", tmp_path, tag, "npz", world, timeout, spec)]
 
 
 def bits(a):

@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+import _ranks
+from _ranks import stitch
 from psgradientsdf_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -21,46 +23,12 @@ def free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
-def socket_mesh(world):
-    """one connected stream-socket pair per pair of ranks: mesh[r][q] = rank r's end of its connection to rank q (psgsdf_comm_init_sockets)"""
-    mesh = [[-1] * world for _ in range(world)]
-    for r in range(world):
-        for q in range(r + 1, world):
-            a, b = socket.socketpair(socket.AF_UNIX, socket.SOCK_STREAM)
-            mesh[r][q], mesh[q][r] = a.detach(), b.detach()
-    return mesh
-
-
 def run_ranks(tmp_path, model, world, transport, mode, N, n_iters, extra_env=None, timeout=150):
+    """the slab worker keeps its own command line and variable names (tools/soak_slab.py and the cases below name them); CU ranges are the caller's (extra_env)"""
     port = free_port(); out = str(tmp_path / "slab")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SLAB_WORKER_TIMEOUT=str(timeout - 40), **(extra_env or {}))
-    mesh = socket_mesh(world) if transport == "sockets" else None
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_slab_worker_gpu.py"), str(r), str(world), str(port), model, out, str(n_iters), str(N), transport, mode],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(env, SLAB_FDS=",".join(str(f) for f in mesh[r])) if mesh else env,
-                              pass_fds=[f for f in mesh[r] if f >= 0] if mesh else ()) for r in range(world)]
-    if mesh:
-        for row in mesh:
-            for f in row:
-                if f >= 0:
-                    os.close(f)
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=timeout)
-            assert p.returncode == 0, o[-3000:]
-    finally:
-        for p in procs:      # a rank that is still alive here would keep the GPU (and the next test) busy
-            if p.poll() is None:
-                p.kill()
+    _ranks.run_ranks("_slab_worker_gpu.py", [[r, world, port, model, out, n_iters, N, transport, mode] for r in range(world)], world, timeout,
+                     env={"SLAB_WORKER_TIMEOUT": str(timeout - 40), **(extra_env or {})}, mesh=transport == "sockets", split=False, names=("SLAB_FDS", "SLAB_CU_MASKS"))
     return [np.load(out + f".rank{r}.npz") for r in range(world)]
-
-
-def stitch(res, key):
-    """the slabs tile the volume: every rank filled the z-planes it owns, NaN elsewhere"""
-    out = np.full_like(res[0][key], np.nan)
-    for got in res:
-        m = ~np.isnan(got[key]); assert not (m & ~np.isnan(out)).any(); out[m] = got[key][m]
-    assert not np.isnan(out).any()
-    return out
 
 
 @pytest.mark.parametrize("model,world,transport", [("SH1", 1, "rccl"), ("SH1", 1, "rccl-perpass"), ("SH1", 2, "gloo"), ("SH1", 2, "gloo-xr0"), ("SH1", 3, "gloo-xf0"), ("LED", 2, "gloo-xs0"), ("SH1", 3, "gloo-xh0"), ("LED", 2, "gloo"), ("SH1", 3, "gloo"), ("SH1", 4, "gloo"), ("SH2", 2, "gloo"),
