@@ -218,18 +218,18 @@ int psgsdf_debug_frame_system(psgsdf_ctx* c, int block, double* H, double* b) {
     HIPCHK(c, hipSetDevice(c->device));
     SweepArgs a = make_args(c, 0);
     const bool led = c->set.model == PSGSDF_LED;
-    int n, nb, nh;
-    int launched = 0;
-    if (block == PSGSDF_LIGHT) { launched = launch_sweep_light(a, c->stream); n = led ? 3 : (c->set.model == PSGSDF_SH2 ? 9 : 4); nb = led ? 1 : c->F; nh = led ? 3 : n * (n + 1) / 2; }
-    else if (block == PSGSDF_POSE) { launched = launch_sweep_pose(a, c->stream); n = 6; nb = c->F; nh = 21; }
+    int nb, launched = 0;
+    if (block == PSGSDF_LIGHT) { launched = launch_sweep_light(a, c->stream); nb = led ? 1 : c->F; }
+    else if (block == PSGSDF_POSE) { launched = launch_sweep_pose(a, c->stream); nb = c->F; }
     else return fail(c, PSGSDF_ERR_ARG, "block must be LIGHT or POSE");
+    const int kind = block == PSGSDF_POSE ? 1 : 0, n = frame_row_nb(c->set.model, kind), nh = frame_row_nh(c->set.model, kind);
     if (!launched) HIPCHK(c, hipMemsetAsync(c->acc_frame, 0, sizeof(double) * c->acc_frame_n, c->stream));
     std::vector<double> acc(c->acc_frame_n);
     HIPCHK(c, hipMemcpyAsync(acc.data(), c->acc_frame, sizeof(double) * c->acc_frame_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (led && block == PSGSDF_LIGHT) {   // one global system: sum the per-frame rows
         for (int i = 0; i < 9; ++i) H[i] = 0;
-        for (int i = 0; i < 3; ++i) { b[i] = 0; for (int f = 0; f < c->F; ++f) { H[i * 3 + i] += acc[(size_t)f * kFrameRow + i]; b[i] += acc[(size_t)f * kFrameRow + 3 + i]; } }
+        for (int i = 0; i < 3; ++i) { b[i] = 0; for (int f = 0; f < c->F; ++f) { H[i * 3 + i] += acc[(size_t)f * kFrameRow + i]; b[i] += acc[(size_t)f * kFrameRow + nh + i]; } }
         return PSGSDF_OK;
     }
     for (int k = 0; k < nb; ++k) {

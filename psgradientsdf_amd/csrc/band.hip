@@ -328,18 +328,8 @@ void launch_sum_parts(const double* part, int PB, int nblk, const SlotList& slot
 }
 // sum of columns (col, col+1) over the F frame-accumulator rows -> out[0..1]
 __global__ void __launch_bounds__(kBlock) k_frame_cols(const double* __restrict__ frame, int F, int col, double* __restrict__ out, unsigned long long key) {
-    __shared__ double red[kBlock / 64];
-    double a = 0, b = 0;
-    for (int f = threadIdx.x; f < F; f += blockDim.x) { a += frame[(size_t)f * kFrameRow + col]; b += frame[(size_t)f * kFrameRow + col + 1]; }
-    a = wave_sum(a); b = wave_sum(b);
-    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) red[w] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = 0; for (int i = 0; i < kBlock / 64; ++i) t += red[i]; mbox_put(out, 2, 0, t, key); }
-    __syncthreads();
-    if (lane == 0) red[w] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = 0; for (int i = 0; i < kBlock / 64; ++i) t += red[i]; mbox_put(out, 2, 1, t, key); mbox_commit(key); }
+    __shared__ double red[2 * kBlock / 64];
+    frame_cols_sum(frame, F, col, out, key, red);
 }
 void launch_frame_cols(const double* frame, int F, int col, double* out, unsigned long long key, hipStream_t s) {
     hipLaunchKernelGGL(k_frame_cols, dim3(1), dim3(kBlock), 0, s, frame, F, col, out, key);

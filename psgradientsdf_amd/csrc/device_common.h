@@ -83,7 +83,7 @@ template <int NB> __device__ __forceinline__ void SH(const float* n, float* sh) 
     sh[0] = 1.0f; sh[1] = n[0]; sh[2] = n[1]; sh[3] = n[2];
     if (NB == 9) { sh[4] = n[0] * n[1]; sh[5] = n[0] * n[2]; sh[6] = n[1] * n[2]; sh[7] = n[0] * n[0] - n[1] * n[1]; sh[8] = n[0] * n[0] - n[2] * n[2]; }
 }
-template <int MODEL> struct ModelTraits { static constexpr int NB = MODEL == 1 ? 9 : (MODEL == 0 ? 4 : 3); static constexpr bool LED = MODEL == 2; };
+template <int MODEL> struct ModelTraits { static constexpr int NB = frame_row_nb(MODEL, 0); static constexpr bool LED = MODEL == 2; };
 
 // Optimizer.cpp:140-161 / 164-186
 // launches K<model, loss, img>: the three shading models x {Cauchy loss and the image format compiled in, both decided at run time}.
@@ -315,6 +315,28 @@ __device__ __forceinline__ void mbox_put(double* out, int n, int i, double v, un
     if (key) reinterpret_cast<unsigned long long*>(out)[n + i] = (unsigned long long)__double_as_longlong(v) ^ (key + (unsigned long long)i);
 }
 __device__ __forceinline__ void mbox_commit(unsigned long long key) { if (key) __threadfence_system(); }
+// (an element of a frame row: LDS in a frame's own last workgroup, memory -- written by other threads of the workgroup a barrier ago, or by other workgroups of
+// the same launch before their tickets -- in the sweeps' tail; as good as a plain load in a kernel of its own)
+__device__ __forceinline__ double ldrow(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The energy / n_obs columns (col_e, col_e + 1: engine.h frame_row_ecol) of the F final frame rows, summed into the two-value read-back slot `out`: threads
+// stride the frames, wave_sum, the wavefronts added in order by thread 0.  ONE order, whichever kernel ends a frame-major step (the sweep's own tail, the
+// solve kernels, k_frame_cols): that keeps PSGSDF_FM_SOLVE=0/1/2 equal to the bit.  All threads of the workgroup call; lds: 2 doubles per wavefront.
+__device__ __forceinline__ void frame_cols_sum(const double* rows, int F, int col_e, double* out, unsigned long long key, double* lds) {
+    double e = 0, n = 0;
+    for (int f = threadIdx.x; f < F; f += blockDim.x) { e += ldrow(rows + (size_t)f * kFrameRow + col_e); n += ldrow(rows + (size_t)f * kFrameRow + col_e + 1); }
+    e = wave_sum(e); n = wave_sum(n);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();                                       // (lds may be what the caller's threads were still reading: a sweep's wavefront sums)
+    if (lane == 0) { lds[2 * w] = e; lds[2 * w + 1] = n; }
+    __syncthreads();
+    if (threadIdx.x == 0) { double te = 0, tn = 0; for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { te += lds[2 * i]; tn += lds[2 * i + 1]; } mbox_put(out, 2, 0, te, key); mbox_put(out, 2, 1, tn, key); mbox_commit(key); }
+}
+// A speculative light update (loop.hip run_loop) keeps what it overwrites -- the frames' light coefficients [F][9] and the LED light [3] behind them -- so that
+// k_restore_light can put them back if the loop ends on the previous iteration.  All threads call, and meet a barrier before any of them updates a record.
+__device__ __forceinline__ void light_undo_save(float* undo, const FrameP* frames, const float* led_light, int F) {
+    for (int i = threadIdx.x; i < F * 9; i += blockDim.x) undo[i] = frames[i / 9].l[i % 9];
+    if (threadIdx.x < 3) undo[F * 9 + threadIdx.x] = led_light[threadIdx.x];
+}
 // 8-byte write-through store at system scope: the word reaches memory (another device's view) without a later write-back
 __device__ __forceinline__ void store8_system(double* p, double v) { asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory"); }
 // Multi-rank fold (ONE WAVEFRONT, all 64 lanes call; lane 0 holds the slab's n <= 8 sums): they go into slot [parity][rank] of EVERY rank's mailbox

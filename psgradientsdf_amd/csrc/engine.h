@@ -90,6 +90,14 @@ struct Accum {
     int* fdone;               // [F] arrival counters, zero outside a sweep
 };
 constexpr int kFrameRow = 64;        // doubles per frame accumulator row (SH2: 45 + 9 + 2 = 56)
+// THE layout of a frame row, [NH entries of H | NB rhs | energy | n_obs], per model (0 SH1, 1 SH2, 2 LED: psgsdf_model) and sweep kind (0 light, 1 pose).
+// NB unknowns: the frame's SH coefficients / the LED's RGB intensity / the 6 pose parameters; H: the upper triangle -- the LED light's is diagonal (3).
+__host__ __device__ constexpr int frame_row_nb(int model, int kind) { return kind == 1 ? 6 : model == 1 ? 9 : model == 2 ? 3 : 4; }
+__host__ __device__ constexpr int frame_row_nh(int model, int kind) { return (kind == 0 && model == 2) ? 3 : frame_row_nb(model, kind) * (frame_row_nb(model, kind) + 1) / 2; }
+__host__ __device__ constexpr int frame_row_ecol(int model, int kind) { return frame_row_nh(model, kind) + frame_row_nb(model, kind); }      // energy; n_obs follows
+__host__ __device__ constexpr int frame_row_len(int model, int kind) { return frame_row_ecol(model, kind) + 2; }
+// (the longest row is the SH2 light's; <= 64: one wavefront carries a row through the sweeps' hand-off, sweeps.hip frame_rows_publish)
+static_assert(frame_row_len(1, 0) <= kFrameRow && frame_row_len(1, 0) <= 64 && frame_row_len(1, 0) >= frame_row_len(0, 1), "a frame row fits kFrameRow and one wavefront");
 constexpr int kPcgMaxBlocks = 2048;  // workgroups of one PCG pass (grid-stride)
 constexpr int kCgfMaxBlocks = 768;   // workgroups of one fused PCG pass: at most 3 partials per thread and sum (pcg.hip)
 

@@ -121,12 +121,11 @@ __global__ void __launch_bounds__(kEigThreads) k_frames_eigen(SweepArgs a, Frame
     __shared__ EigRed red;
     __shared__ float s_dl[3];
     const int T = blockDim.x, n = nb * NB;
-    if (KIND == 0 && undo) {
-        for (int i = threadIdx.x; i < a.F * 9; i += T) undo[i] = frames[i / 9].l[i % 9];
-        if (threadIdx.x < 3) undo[a.F * 9 + threadIdx.x] = led_light[threadIdx.x];
-    }
+    if (KIND == 0 && undo) light_undo_save(undo, frames, led_light, a.F);      // (the solver's barriers come before any update)
     float Hrow[kEigK][NB], bu[kEigK], xu[kEigK];
-    constexpr int NH = (KIND == 0 && LED) ? 3 : NB * (NB + 1) / 2;
+    constexpr int MODEL = LED ? 2 : NB == 9 ? 1 : 0;      // whose rows KIND 0 / 1 read (engine.h frame_row_*)
+    constexpr int NH = KIND == 2 ? 0 : frame_row_nh(MODEL, KIND), col_e = KIND == 2 ? 0 : frame_row_ecol(MODEL, KIND);
+    static_assert(KIND == 2 || NB == frame_row_nb(MODEL, KIND), "one unknown per rhs column of the row");
 #pragma unroll
     for (int k = 0; k < kEigK; ++k) {
         const int u = (int)threadIdx.x + k * T;
@@ -183,8 +182,7 @@ __global__ void __launch_bounds__(kEigThreads) k_frames_eigen(SweepArgs a, Frame
         if (applied) for (int ff = threadIdx.x; ff < a.F; ff += T) { float xi[6]; for (int i = 0; i < 6; ++i) xi[i] = sp[ff * 6 + i]; pose_update(frames, ff, xi); }
     }
     if (threadIdx.x == 0 && stats) { stats[0] = (double)iters; stats[1] = err; stats[2] = (double)ok; stats[3] = (double)applied; }
-    if (KIND != 2 && e_out) {      // the energy / n_obs columns of the rows over the frames (sweeps.hip frame_rows_finish's order: threads striding the frames, wavefront sums in order)
-        constexpr int col_e = KIND == 1 ? 27 : NH + NB;
+    if (KIND != 2 && e_out) {      // the energy / n_obs columns of the rows over the frames (threads striding the frames, wavefront sums in order; its own tree: this workgroup is not frame_cols_sum's 256 threads)
         __syncthreads();
         double e = 0, nn = 0;
         for (int f = threadIdx.x; f < a.F; f += T) { e += a.acc.frame[(size_t)f * kFrameRow + col_e]; nn += a.acc.frame[(size_t)f * kFrameRow + col_e + 1]; }

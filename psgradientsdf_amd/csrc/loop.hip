@@ -333,9 +333,8 @@ int step_begin(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* s
             if (block == PSGSDF_LIGHT) {
                 take_fold(c, a, 0u);
                 timed(c, "sweep_light", [&] { launched = launch_sweep_light(a, c->stream); });
-                const int n = led ? 3 : (c->set.model == PSGSDF_SH2 ? 9 : 4), nh = led ? 3 : n * (n + 1) / 2;
-                col = nh + n;
-            } else { take_fold(c, a, 0u); timed(c, "sweep_pose", [&] { launched = launch_sweep_pose(a, c->stream); }); col = 27; }
+                col = frame_row_ecol(c->set.model, 0);
+            } else { take_fold(c, a, 0u); timed(c, "sweep_pose", [&] { launched = launch_sweep_pose(a, c->stream); }); col = frame_row_ecol(c->set.model, 1); }
             if (fuse) {
                 if (launched) { c->fm_solved = true; return 0; }
                 c->frame_e_slot = fm_slot; c->frame_e_key = fm_key;      // (nothing was launched: the solve kernel of step_finish fills the slot)

@@ -3,13 +3,6 @@
 // Shared device helpers: device_common.h; the launchers are declared in engine.h.
 #include "device_common.h"
 
-#ifndef PSG_FM_PIPE
-#define PSG_FM_PIPE 3      // (development: bit 0 = k_sweep_light, bit 1 = k_sweep_pose run the three-stage observation pipeline of device_common.h fm_for_each_obs)
-#endif
-#ifndef PSG_POSE_WAVES
-#define PSG_POSE_WAVES 1
-#endif
-
 namespace psg {
 
 // Optimizer.cpp:50-81 initAlbedo
@@ -212,17 +205,37 @@ static int fm_rows(const SweepArgs& a, int slots_per_cu) {
     return (int)std::min<long long>(std::max<long long>(r, 4), 64);
 }
 
-// small dense solves and SO3::exp (defined below)
-template <int N> __device__ void solve_spd(const double* Hin, const double* bin, double* x);
+// ------------------------------------------------------------------------------------------
+// small dense solves: LDL^T in double, zero step on non-positive pivots
+// ------------------------------------------------------------------------------------------
+template <int N>
+__device__ void solve_spd(const double* Hin, const double* bin, double* x) {
+    double L[N * N], D[N], y[N];
+    double scale = 0;
+    for (int i = 0; i < N; ++i) scale = fmax(scale, fabs(Hin[i * N + i]));
+    const double tiny = scale * 1e-12;
+    for (int i = 0; i < N * N; ++i) L[i] = 0;
+    for (int j = 0; j < N; ++j) {
+        double d = Hin[j * N + j];
+        for (int k = 0; k < j; ++k) d -= L[j * N + k] * L[j * N + k] * D[k];
+        D[j] = d; L[j * N + j] = 1.0;
+        for (int i = j + 1; i < N; ++i) {
+            double s = Hin[i * N + j];
+            for (int k = 0; k < j; ++k) s -= L[i * N + k] * L[j * N + k] * D[k];
+            L[i * N + j] = (d > tiny) ? s / d : 0.0;
+        }
+    }
+    for (int i = 0; i < N; ++i) { double s = bin[i]; for (int k = 0; k < i; ++k) s -= L[i * N + k] * y[k]; y[i] = s; }
+    for (int i = 0; i < N; ++i) y[i] = (D[i] > tiny) ? y[i] / D[i] : 0.0;
+    for (int i = N - 1; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < N; ++k) s -= L[k * N + i] * x[k]; x[i] = s; }
+}
 
 // One frame's light step (optimizeLightAll, PsOptimizer.cpp:175-203: no damping; SH models: NB x NB per frame) from its final row `acc`, and one
 // frame's pose step (optimizePosesAll PsOptimizer.cpp:207-234 + updatePose OptimizerAux.cpp:190-205).  Shared by the one-workgroup solve kernels
 // below and by the sweeps' own epilogue (fm_solve: the last workgroup of a frame to arrive solves that frame at once -- no solve launch).
-// (a row element: LDS in a frame's own last workgroup, memory -- written by other threads of the workgroup a barrier ago -- in the multi-rank tail)
-__device__ __forceinline__ double ldrow(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <int NB>
+template <int MODEL>      // an SH model (the LED instances of the callers name SH1 in the branch they never take)
 __device__ __forceinline__ void frame_solve_light_sh(FrameP* frames, int f, const double* acc, float* undo) {
-    constexpr int NH = NB * (NB + 1) / 2;
+    constexpr int NB = frame_row_nb(MODEL, 0), NH = frame_row_nh(MODEL, 0);
     if (undo) for (int i = 0; i < 9; ++i) undo[f * 9 + i] = frames[f].l[i];      // (a speculative update keeps what it overwrites: loop.hip run_loop)
     double Hd[NB * NB], bd[NB], xd[NB];
     int q = 0;
@@ -239,69 +252,58 @@ __device__ __forceinline__ void frame_solve_pose(const SweepArgs& a, FrameP* fra
         if (i == k && a.damping != 0.0f) v += a.damping * v;
         Hd[i * 6 + k] = (double)v; Hd[k * 6 + i] = (double)v;
     }
-    for (int i = 0; i < 6; ++i) bd[i] = (double)(float)ldrow(acc + 21 + i);
+    for (int i = 0; i < 6; ++i) bd[i] = (double)(float)ldrow(acc + frame_row_nh(0, 1) + i);      // (the pose row is the same for every model)
     solve_spd<6>(Hd, bd, xd);
     float xi[6];
     for (int i = 0; i < 6; ++i) xi[i] = (float)xd[i];
     pose_update(frames, f, xi);
 }
 
+// LED: ONE light vector over all frames (LedOptimizer.cpp:128-160; damped), from the final rows of all frames: double sums over the frames in frame order,
+// cast to float, damping, three scalar equations, every frame's copy updated and frame 0's also written to `led_light`.  All threads of ONE workgroup call, once
+// no other workgroup reads a frame record any more (a kernel of its own, or the last workgroup of the whole sweep).  The six columns are staged in LDS by all
+// threads at once: summed straight from memory, 2 x F dependent loads per summing thread made k_solve_light 21.7 us at F = 50.
+__device__ __forceinline__ void led_light_step(const SweepArgs& a, FrameP* frames, float* led_light) {
+    constexpr int NH = frame_row_nh(2, 0);
+    __shared__ float s_dl[3];
+    __shared__ double srow[6 * kMaxFramesLds];      // (F <= kMaxFramesLds: psgsdf_set_keyframes)
+    for (int i = threadIdx.x; i < 6 * a.F; i += blockDim.x) { const int ff = i / 6, c6 = i % 6; srow[c6 * kMaxFramesLds + ff] = ldrow(a.acc.frame + (size_t)ff * kFrameRow + (c6 < 3 ? c6 : NH + c6 - 3)); }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int ch = threadIdx.x;
+        double hs = 0, bs = 0;
+        for (int ff = 0; ff < a.F; ++ff) { hs += srow[ch * kMaxFramesLds + ff]; bs += srow[(3 + ch) * kMaxFramesLds + ff]; }
+        float h = (float)hs; const float bb = (float)bs;
+        if (a.damping != 0.0f) h += a.damping * h;
+        double Hd[1] = {(double)h}, bd[1] = {(double)bb}, xd[1];
+        solve_spd<1>(Hd, bd, xd);
+        s_dl[ch] = (float)xd[0];
+    }
+    __syncthreads();
+    for (int ff = threadIdx.x; ff < a.F; ff += blockDim.x) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) { const float nl = frames[ff].l[ch] - s_dl[ch]; frames[ff].l[ch] = nl; if (ff == 0) led_light[ch] = nl; }
+    }
+}
+
 // What the LAST workgroup of a frame-major launch does once every frame's final row is in a.acc.frame: (multi-rank: the per-frame solves, one lane per
 // frame --) the LED light vector over all frames, and the energy / n_obs sums over the frames into the mailbox.  Shared by the sweeps' own epilogue
 // (single rank: the frames were solved by their own last workgroups) and by k_frame_gather (multi-rank).
-template <int NV, int KIND, int MODEL>
+template <int KIND, int MODEL>
 __device__ __forceinline__ void frame_tail(const SweepArgs& a, double* lds, bool solve_all) {
     if (solve_all) {
         for (int ff = threadIdx.x; ff < a.F; ff += blockDim.x) {
             const double* row = a.acc.frame + (size_t)ff * kFrameRow;
-            if (KIND == 0) { if (!ModelTraits<MODEL>::LED) frame_solve_light_sh<ModelTraits<MODEL>::NB == 3 ? 4 : ModelTraits<MODEL>::NB>(a.fm_frames, ff, row, a.fm_undo); }
+            if (KIND == 0) { if (!ModelTraits<MODEL>::LED) frame_solve_light_sh<ModelTraits<MODEL>::LED ? 0 : MODEL>(a.fm_frames, ff, row, a.fm_undo); }
             else frame_solve_pose(a, a.fm_frames, ff, row);
         }
         __syncthreads();
     }
     if (KIND == 0 && ModelTraits<MODEL>::LED) {
-        // LED: ONE light vector over all frames (LedOptimizer.cpp:128-160): this workgroup is the last of the whole sweep, every frame's final row is
-        // in place and no workgroup reads a frame record any more -- k_solve_light's arithmetic (sums over the frames in frame order, three
-        // scalar equations, every frame's copy updated), thread 0 solving, all threads updating
-        constexpr int NHL = 3;
-        __shared__ float s_dl[3];
-        if (a.fm_undo) {
-            for (int i = threadIdx.x; i < a.F * 9; i += blockDim.x) a.fm_undo[i] = a.fm_frames[i / 9].l[i % 9];
-            if (threadIdx.x < 3) a.fm_undo[a.F * 9 + threadIdx.x] = a.fm_led_light[threadIdx.x];
-        }
-        __shared__ double srow[6 * kMaxFramesLds];      // the six columns staged by all threads at once (summed straight from memory: 2 x F dependent loads per thread)
-        for (int i = threadIdx.x; i < 6 * a.F; i += blockDim.x) { const int ff = i / 6, c6 = i % 6; srow[c6 * kMaxFramesLds + ff] = __hip_atomic_load(a.acc.frame + (size_t)ff * kFrameRow + (c6 < 3 ? c6 : NHL + c6 - 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            const int ch = threadIdx.x;
-            double hs = 0, bs = 0;
-            for (int ff = 0; ff < a.F; ++ff) { hs += srow[ch * kMaxFramesLds + ff]; bs += srow[(3 + ch) * kMaxFramesLds + ff]; }
-            float h = (float)hs; const float bb = (float)bs;
-            if (a.damping != 0.0f) h += a.damping * h;
-            double Hd[1] = {(double)h}, bd[1] = {(double)bb}, xd[1];
-            solve_spd<1>(Hd, bd, xd);
-            s_dl[ch] = (float)xd[0];
-        }
-        __syncthreads();
-        for (int ff = threadIdx.x; ff < a.F; ff += blockDim.x) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) { const float nl = a.fm_frames[ff].l[ch] - s_dl[ch]; a.fm_frames[ff].l[ch] = nl; if (ff == 0) a.fm_led_light[ch] = nl; }
-        }
+        if (a.fm_undo) light_undo_save(a.fm_undo, a.fm_frames, a.fm_led_light, a.F);
+        led_light_step(a, a.fm_frames, a.fm_led_light);
     }
-    if (a.fm_e_out) {      // energy / n_obs over the frames, in frame_rows_finish's order (one 256-thread workgroup, threads striding the frames)
-        constexpr int col_e = NV - 2;
-        double e = 0, n = 0;
-        for (int ff = threadIdx.x; ff < a.F; ff += blockDim.x) {
-            e += __hip_atomic_load(a.acc.frame + (size_t)ff * kFrameRow + col_e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            n += __hip_atomic_load(a.acc.frame + (size_t)ff * kFrameRow + col_e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        e = wave_sum(e); n = wave_sum(n);
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        __syncthreads();
-        if (lane == 0) { lds[2 * w] = e; lds[2 * w + 1] = n; }
-        __syncthreads();
-        if (threadIdx.x == 0) { double te = 0, tn = 0; for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { te += lds[2 * i]; tn += lds[2 * i + 1]; } mbox_put(a.fm_e_out, 2, 0, te, a.fm_e_key); mbox_put(a.fm_e_out, 2, 1, tn, a.fm_e_key); mbox_commit(a.fm_e_key); }
-    }
+    if (a.fm_e_out) frame_cols_sum(a.acc.frame, a.F, frame_row_ecol(MODEL, KIND), a.fm_e_out, a.fm_e_key, lds);
 }
 
 // Epilogue of the frame-major sweeps: every workgroup stores ITS partial row of frame f (plain stores, no floating-point atomics) and
@@ -309,10 +311,11 @@ __device__ __forceinline__ void frame_tail(const SweepArgs& a, double* lds, bool
 // into the final row -- reproducible from run to run, and done while the other frames' workgroups are still sweeping.
 // fm_solve (single rank, the deferred path of the alternation loop): that last workgroup also SOLVES the frame -- KIND 0: the SH light block
 // (the LED light is one vector over all frames: k_solve_light keeps it), KIND 1: the pose block -- and takes a second ticket on the sweep's
-// frame counter; the last FRAME to finish sums the energy / n_obs columns of all rows in frame order into the mailbox (what the solve kernels'
-// frame_rows_finish does).  The frame's record is only read by the frame's own workgroups, all of which have finished; same arithmetic, same bits.
-template <int NV, int KIND, int MODEL>
+// frame counter; the last FRAME to finish sums the energy / n_obs columns of all rows in frame order into the mailbox (what the solve kernels
+// do: frame_cols_sum).  The frame's record is only read by the frame's own workgroups, all of which have finished; same arithmetic, same bits.
+template <int KIND, int MODEL>
 __device__ __forceinline__ void frame_rows_publish(const SweepArgs& a, int cx, int f, double* lds /*[kBlock/64][NV] wavefront sums*/) {
+    constexpr int NV = frame_row_len(MODEL, KIND);
     // Hand-off without fences (an agent-scope release fence in every workgroup's tail writes back the XCD's L2 each time: light sweep
     // 46 -> 82 us): the row goes out with write-through (sc1) stores, the wave drains them, then takes the ticket; the last arriver reads
     // the rows with sc1 loads (MI355X_MICROARCH.md: "sc1 payload -> vmcnt(0) -> sc1 flag", "sc1 loads may replace the acquire").
@@ -363,7 +366,7 @@ __device__ __forceinline__ void frame_rows_publish(const SweepArgs& a, int cx, i
     if (a.xf) return;      // multi-rank: this frame's slab row is out; k_frame_gather (launched behind the sweep) forms the global rows and solves
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (KIND == 0) { if (!ModelTraits<MODEL>::LED) frame_solve_light_sh<ModelTraits<MODEL>::NB == 3 ? 4 : ModelTraits<MODEL>::NB>(a.fm_frames, f, lds, a.fm_undo); }
+        if (KIND == 0) { if (!ModelTraits<MODEL>::LED) frame_solve_light_sh<ModelTraits<MODEL>::LED ? 0 : MODEL>(a.fm_frames, f, lds, a.fm_undo); }
         else frame_solve_pose(a, a.fm_frames, f, lds);
     }
     if (threadIdx.x < 64) {
@@ -373,7 +376,7 @@ __device__ __forceinline__ void frame_rows_publish(const SweepArgs& a, int cx, i
     __syncthreads();
     if (!s_last) return;
     if (threadIdx.x == 0) __hip_atomic_store(a.acc.fdone + a.F, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    frame_tail<NV, KIND, MODEL>(a, lds, false);
+    frame_tail<KIND, MODEL>(a, lds, false);
 }
 
 // Multi-rank: the slabs' rows of a frame meet here, not inside the sweep.  The sweep's workgroups publish their slab's row of every frame into all
@@ -387,6 +390,7 @@ __device__ __forceinline__ void frame_rows_publish(const SweepArgs& a, int cx, i
 constexpr int kGatherFrames = 16;
 template <int NV, int KIND, int MODEL>
 __global__ void __launch_bounds__(kBlock) k_frame_gather(SweepArgs a) {
+    static_assert(NV == frame_row_len(MODEL, KIND), "NV is the row length of the instance's model and sweep kind");
     __shared__ double lds[(kBlock / 64) * NV > 2 * (kBlock / 64) ? (kBlock / 64) * NV : 2 * (kBlock / 64)];
     __shared__ unsigned char s_late[kGatherFrames];
     __shared__ int s_last;
@@ -432,21 +436,14 @@ __global__ void __launch_bounds__(kBlock) k_frame_gather(SweepArgs a) {
     __syncthreads();
     if (!s_last) return;
     if (threadIdx.x == 0) __hip_atomic_store(a.acc.fdone + a.F, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    frame_tail<NV, KIND, MODEL>(a, lds, true);
+    frame_tail<KIND, MODEL>(a, lds, true);
 }
 template <int KIND>
 static void launch_frame_gather(const SweepArgs& a, hipStream_t s) {
     const dim3 g((a.F + kGatherFrames - 1) / kGatherFrames), bl(kBlock);
-    constexpr int NVP = 21 + 6 + 2;
-    if (KIND == 1) {
-        if (a.model == 0) hipLaunchKernelGGL((k_frame_gather<NVP, 1, 0>), g, bl, 0, s, a);
-        else if (a.model == 1) hipLaunchKernelGGL((k_frame_gather<NVP, 1, 1>), g, bl, 0, s, a);
-        else hipLaunchKernelGGL((k_frame_gather<NVP, 1, 2>), g, bl, 0, s, a);
-    } else {      // light rows: NH + NB + 2 (SH1: 10 + 4 + 2, SH2: 45 + 9 + 2, LED: 3 + 3 + 2)
-        if (a.model == 0) hipLaunchKernelGGL((k_frame_gather<16, 0, 0>), g, bl, 0, s, a);
-        else if (a.model == 1) hipLaunchKernelGGL((k_frame_gather<56, 0, 1>), g, bl, 0, s, a);
-        else hipLaunchKernelGGL((k_frame_gather<8, 0, 2>), g, bl, 0, s, a);
-    }
+    if (a.model == 0) hipLaunchKernelGGL((k_frame_gather<frame_row_len(0, KIND), KIND, 0>), g, bl, 0, s, a);
+    else if (a.model == 1) hipLaunchKernelGGL((k_frame_gather<frame_row_len(1, KIND), KIND, 1>), g, bl, 0, s, a);
+    else hipLaunchKernelGGL((k_frame_gather<frame_row_len(2, KIND), KIND, 2>), g, bl, 0, s, a);
 }
 
 // light normal equations: lightJacobian PsOptimizerJa.cpp:132-143,323-371 (per frame NBxNB),
@@ -456,8 +453,7 @@ __global__ void __launch_bounds__(kBlock) k_sweep_light(SweepArgs a, int rows) {
     { __shared__ double fred[kBlock / 64]; fold_pending(a, fred); }
     constexpr int NB = ModelTraits<MODEL>::NB;
     constexpr bool LED = ModelTraits<MODEL>::LED;
-    constexpr int NH = LED ? 3 : NB * (NB + 1) / 2;
-    constexpr int NV = NH + NB + 2;   // + energy, n_obs
+    constexpr int NH = frame_row_nh(MODEL, 0), NV = frame_row_len(MODEL, 0);
     __shared__ FrameP sfp;
     __shared__ double lds[(kBlock / 64) * NV];
     int cx, f; fm_ids(a, cx, f);
@@ -522,7 +518,7 @@ __global__ void __launch_bounds__(kBlock) k_sweep_light(SweepArgs a, int rows) {
         acc[NH + NB] += (obs_acc_t)l; acc[NH + NB + 1] += 1;
     };
     const int e0 = beg + cx * (kBlock * rows) + threadIdx.x;
-    if constexpr (IMG >= 0 && !(PSG_STRICT & 4) && (PSG_FM_PIPE & 1)) {
+    if constexpr (IMG >= 0 && !(PSG_STRICT & 4)) {
         // three-stage software pipeline over the thread's observations (device_common.h fm_for_each_obs; rows <= 64: fm_rows)
         fm_for_each_obs<IMG>(b, fp, a.cam, img, e0, end, rows, [&](const ObsPend<IMG>& P) {
             float I[3];
@@ -555,11 +551,11 @@ __global__ void __launch_bounds__(kBlock) k_sweep_light(SweepArgs a, int rows) {
     const int w = threadIdx.x >> 6;
     wave_sums_to<NV>(acc, lds + w * NV);   // double: SH2 light blocks are ill-conditioned
     __syncthreads();
-    frame_rows_publish<NV, 0, MODEL>(a, cx, f, lds);
+    frame_rows_publish<0, MODEL>(a, cx, f, lds);
 }
 int launch_sweep_light(const SweepArgs& a, hipStream_t s) {
     if (a.b.S <= 0 || a.F <= 0 || a.b.obs_max <= 0) return 0;
-    const int rows = fm_rows(a, a.model == 1 ? 3 : ((PSG_FM_PIPE & 1) ? 4 : 5));           // resident workgroups per CU at this kernel's register count (pipelined: 108-120 VGPRs, SH2 161-168)
+    const int rows = fm_rows(a, a.model == 1 ? 3 : 4);           // resident workgroups per CU at this kernel's register count (pipelined: 108-120 VGPRs, SH2 161-168)
     const int chunk = kBlock * rows;
     dim3 g((a.b.obs_max + chunk - 1) / chunk, a.F), bl(kBlock);
     PSG_LAUNCH_SWEEP(k_sweep_light, a, true, g, bl, 0, s, a, rows);
@@ -569,11 +565,12 @@ int launch_sweep_light(const SweepArgs& a, hipStream_t s) {
 
 // pose normal equations: poseJacobian PsOptimizerJa.cpp:61-115,427-475 / LedOptimizerJa.cpp:32-81,351-399
 template <int MODEL, int LOSS, int IMG>
-__global__ void __launch_bounds__(kBlock, PSG_POSE_WAVES) k_sweep_pose(SweepArgs a, int rows) {
+__global__ void __launch_bounds__(kBlock, 1) k_sweep_pose(SweepArgs a, int rows) {
     { __shared__ double fred[kBlock / 64]; fold_pending(a, fred); }
     constexpr int NB = ModelTraits<MODEL>::NB;
     constexpr bool LED = ModelTraits<MODEL>::LED;
-    constexpr int NV = 21 + 6 + 2;
+    constexpr int NV = frame_row_len(MODEL, 1);
+    static_assert(frame_row_nh(MODEL, 1) == 21 && frame_row_ecol(MODEL, 1) == 27, "accumulate below writes the pose row's columns by number");
     __shared__ FrameP sfp;
     __shared__ double lds[(kBlock / 64) * NV];
     int cx, f; fm_ids(a, cx, f);
@@ -693,7 +690,7 @@ __global__ void __launch_bounds__(kBlock, PSG_POSE_WAVES) k_sweep_pose(SweepArgs
         acc[27] += (obs_acc_t)l; acc[28] += 1;
     };
     const int e0 = beg + cx * (kBlock * rows) + threadIdx.x;
-    if constexpr (IMG >= 0 && !(PSG_STRICT & 4) && (PSG_FM_PIPE & 2)) {
+    if constexpr (IMG >= 0 && !(PSG_STRICT & 4)) {
         // three-stage software pipeline over the thread's observations (device_common.h fm_for_each_obs; rows <= 64: fm_rows); an observation whose
         // gradient needs taps outside its cell (image border, the Jacobian's projection in the neighbouring cell) is evaluated behind the loop
         fm_for_each_obs<IMG>(b, fp, a.cam, img, e0, end, rows, [&](const ObsPend<IMG>& P) {
@@ -733,11 +730,11 @@ __global__ void __launch_bounds__(kBlock, PSG_POSE_WAVES) k_sweep_pose(SweepArgs
     const int w = threadIdx.x >> 6;
     wave_sums_to<NV>(acc, lds + w * NV);   // row layout: [21 H | 6 rhs | energy | n_obs]
     __syncthreads();
-    frame_rows_publish<NV, 1, MODEL>(a, cx, f, lds);
+    frame_rows_publish<1, MODEL>(a, cx, f, lds);
 }
 int launch_sweep_pose(const SweepArgs& a, hipStream_t s) {
     if (a.b.S <= 0 || a.F <= 0 || a.b.obs_max <= 0) return 0;
-    const int rows = fm_rows(a, ((PSG_FM_PIPE & 2) && PSG_POSE_WAVES < 4) ? 3 : 4);      // (pipelined: 131-145 VGPRs)
+    const int rows = fm_rows(a, 3);      // (resident workgroups per CU; pipelined: 131-145 VGPRs)
     const int chunk = kBlock * rows;
     dim3 g((a.b.obs_max + chunk - 1) / chunk, a.F), bl(kBlock);
     PSG_LAUNCH_SWEEP(k_sweep_pose, a, true, g, bl, 0, s, a, rows);
@@ -745,92 +742,17 @@ int launch_sweep_pose(const SweepArgs& a, hipStream_t s) {
     return (int)g.x;
 }
 
-// ------------------------------------------------------------------------------------------
-// small dense solves: LDL^T in double, zero step on non-positive pivots
-// ------------------------------------------------------------------------------------------
-template <int N>
-__device__ void solve_spd(const double* Hin, const double* bin, double* x) {
-    double L[N * N], D[N], y[N];
-    double scale = 0;
-    for (int i = 0; i < N; ++i) scale = fmax(scale, fabs(Hin[i * N + i]));
-    const double tiny = scale * 1e-12;
-    for (int i = 0; i < N * N; ++i) L[i] = 0;
-    for (int j = 0; j < N; ++j) {
-        double d = Hin[j * N + j];
-        for (int k = 0; k < j; ++k) d -= L[j * N + k] * L[j * N + k] * D[k];
-        D[j] = d; L[j * N + j] = 1.0;
-        for (int i = j + 1; i < N; ++i) {
-            double s = Hin[i * N + j];
-            for (int k = 0; k < j; ++k) s -= L[i * N + k] * L[j * N + k] * D[k];
-            L[i * N + j] = (d > tiny) ? s / d : 0.0;
-        }
-    }
-    for (int i = 0; i < N; ++i) { double s = bin[i]; for (int k = 0; k < i; ++k) s -= L[i * N + k] * y[k]; y[i] = s; }
-    for (int i = 0; i < N; ++i) y[i] = (D[i] > tiny) ? y[i] / D[i] : 0.0;
-    for (int i = N - 1; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < N; ++k) s -= L[k * N + i] * x[k]; x[i] = s; }
-}
-
 // The per-frame solves run as ONE workgroup (a thread takes frames tid, tid+256, ...), which lets the same kernel also sum the
-// energy / n_obs columns of the rows over the frames (e_out, may be host-mapped) in a fixed order.  The rows are final when it runs:
+// energy / n_obs columns of the rows over the frames (e_out, may be host-mapped) in a fixed order (frame_cols_sum).  The rows are final when it runs:
 // the last workgroup of every frame of the sweep has summed that frame's partial rows (frame_rows_publish).
-__device__ __forceinline__ void frame_rows_finish(const SweepArgs& a, int col_e, double* e_out, unsigned long long e_key, double* red) {
-    __syncthreads();                                       // every thread has read the rows it solves from
-    if (e_out) {
-        double e = 0, n = 0;
-        for (int f = threadIdx.x; f < a.F; f += blockDim.x) { e += a.acc.frame[(size_t)f * kFrameRow + col_e]; n += a.acc.frame[(size_t)f * kFrameRow + col_e + 1]; }
-        e = wave_sum(e); n = wave_sum(n);
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        if (lane == 0) { red[2 * w] = e; red[2 * w + 1] = n; }
-        __syncthreads();
-        if (threadIdx.x == 0) { double te = 0, tn = 0; for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { te += red[2 * i]; tn += red[2 * i + 1]; } mbox_put(e_out, 2, 0, te, e_key); mbox_put(e_out, 2, 1, tn, e_key); mbox_commit(e_key); }
-        __syncthreads();
-    }
-}
-
-// optimizeLightAll: PsOptimizer.cpp:175-203 (no damping) / LedOptimizer.cpp:134-160 (damped, one RGB vector)
+// optimizeLightAll: PsOptimizer.cpp:175-203 (no damping) / LedOptimizer.cpp:134-160 (damped, one RGB vector); undo (nullable): light_undo_save
 template <int MODEL>
-// undo (nullable): a speculative light update (loop.hip run_loop) keeps what it overwrites -- the frames' light coefficients [F][9] and the LED light [3] behind them --
-// so that k_restore_light can put them back if the loop ends on the previous iteration
 __global__ void __launch_bounds__(kBlock) k_solve_light(SweepArgs a, FrameP* frames, float* led_light, double* e_out, unsigned long long e_key, float* undo) {
-    if (undo) {
-        for (int i = threadIdx.x; i < a.F * 9; i += blockDim.x) undo[i] = frames[i / 9].l[i % 9];
-        if (threadIdx.x < 3) undo[a.F * 9 + threadIdx.x] = led_light[threadIdx.x];
-        __syncthreads();
-    }
-    constexpr int NB = ModelTraits<MODEL>::NB;
-    constexpr bool LED = ModelTraits<MODEL>::LED;
-    constexpr int NH = LED ? 3 : NB * (NB + 1) / 2;
     __shared__ double red[2 * kBlock / 64];
-    if (LED) {
-        // every thread sums the per-frame rows (frame order), solves the same 3 scalar equations and updates its own records.  The six columns
-        // are staged in LDS first: summed straight from memory, 2 x 3 x F dependent global loads per thread made this kernel 21.7 us at F = 50
-        constexpr int kStage = 512;
-        __shared__ double srow[6 * kStage];
-        const bool staged = a.F <= kStage;
-        if (staged) {
-            for (int i = threadIdx.x; i < 6 * a.F; i += blockDim.x) { const int ff = i / 6, c6 = i % 6; srow[c6 * kStage + ff] = a.acc.frame[(size_t)ff * kFrameRow + (c6 < 3 ? c6 : NH + c6 - 3)]; }
-            __syncthreads();
-        }
-        float dl[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            double hs = 0, bs = 0;
-            if (staged) { for (int ff = 0; ff < a.F; ++ff) { hs += srow[ch * kStage + ff]; bs += srow[(3 + ch) * kStage + ff]; } }
-            else for (int ff = 0; ff < a.F; ++ff) { hs += a.acc.frame[(size_t)ff * kFrameRow + ch]; bs += a.acc.frame[(size_t)ff * kFrameRow + NH + ch]; }
-            float h = (float)hs, bb = (float)bs;
-            if (a.damping != 0.0f) h += a.damping * h;
-            double Hd[1] = {(double)h}, bd[1] = {(double)bb}, xd[1];
-            solve_spd<1>(Hd, bd, xd);
-            dl[ch] = (float)xd[0];
-        }
-        for (int f = threadIdx.x; f < a.F; f += blockDim.x) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) { const float nl = frames[f].l[ch] - dl[ch]; frames[f].l[ch] = nl; if (f == 0) led_light[ch] = nl; }
-        }
-    } else {
-        for (int f = threadIdx.x; f < a.F; f += blockDim.x) frame_solve_light_sh<NB>(frames, f, a.acc.frame + (size_t)f * kFrameRow, nullptr);      // (undo: copied above)
-    }
-    frame_rows_finish(a, NH + NB, e_out, e_key, red);
+    if (undo) { light_undo_save(undo, frames, led_light, a.F); __syncthreads(); }
+    if (ModelTraits<MODEL>::LED) led_light_step(a, frames, led_light);
+    else for (int f = threadIdx.x; f < a.F; f += blockDim.x) frame_solve_light_sh<ModelTraits<MODEL>::LED ? 0 : MODEL>(frames, f, a.acc.frame + (size_t)f * kFrameRow, nullptr);      // (undo: copied above)
+    if (e_out) frame_cols_sum(a.acc.frame, a.F, frame_row_ecol(MODEL, 0), e_out, e_key, red);
 }
 __global__ void __launch_bounds__(kBlock) k_restore_light(int F, FrameP* frames, float* led_light, const float* undo) {
     for (int i = threadIdx.x; i < F * 9; i += blockDim.x) frames[i / 9].l[i % 9] = undo[i];
@@ -849,7 +771,7 @@ void launch_solve_light(const SweepArgs& a, FrameP* frames, float* led_light, do
 __global__ void __launch_bounds__(kBlock) k_solve_pose(SweepArgs a, FrameP* frames, double* e_out, unsigned long long e_key) {
     __shared__ double red[2 * kBlock / 64];
     for (int f = threadIdx.x; f < a.F; f += blockDim.x) frame_solve_pose(a, frames, f, a.acc.frame + (size_t)f * kFrameRow);
-    frame_rows_finish(a, 27, e_out, e_key, red);
+    if (e_out) frame_cols_sum(a.acc.frame, a.F, frame_row_ecol(0, 1), e_out, e_key, red);
 }
 void launch_solve_pose(const SweepArgs& a, FrameP* frames, double* e_out, unsigned long long e_key, hipStream_t s) {
     if (a.F > 0) hipLaunchKernelGGL(k_solve_pose, dim3(1), dim3(kBlock), 0, s, a, frames, e_out, e_key);
