@@ -10,10 +10,9 @@ namespace psge {
 int host_stage(psgsdf_ctx* c, size_t bytes, void** p) {
     if (c->pin_bytes < bytes) {
         HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing may still be reading the old buffer)
-        if (c->pin_stage) hipHostFree(c->pin_stage);
-        c->pin_stage = nullptr; c->pin_bytes = 0;
+        c->pin_stage.reset(); c->pin_bytes = 0;
         const size_t want = bytes + bytes / 4;
-        HIPCHK(c, hipHostMalloc(&c->pin_stage, want, hipHostMallocDefault));
+        HIPCHK(c, c->pin_stage.alloc(want));
         c->pin_bytes = want;
     }
     *p = c->pin_stage;
@@ -57,11 +56,13 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     if (const char* e = getenv("PSGSDF_FUSE_ALBEDO")) c->fuse_albedo = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_FUSE_PCG_INIT")) c->fuse_pcg_init = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_PCG_PERSIST")) c->pcg_persist = atoi(e) != 0;
+    if (const char* e = getenv("PSGSDF_PCG_FUSE_APPLY")) c->pcg_fuse_apply = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_AREG_DEVICE")) c->areg_device = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_PCG_WINDOW")) c->pcg_window = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_PCG_SOLVE_ROWS")) { const int v = atoi(e); if (v > 0) c->pcg_solve_rows = v; }
     if (const char* e = getenv("PSGSDF_FM_SOLVE")) { c->fm_solve = atoi(e) != 0; c->fm_solve_led = atoi(e) == 1; }
     if (const char* e = getenv("PSGSDF_FRAME_SOLVE")) c->frame_solve = (!strcmp(e, "eigen") || !strcmp(e, "1")) ? 1 : 0;
+    if (const char* e = getenv("PSGSDF_XR")) c->xr_enable = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_XF")) c->xf_enable = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_XS")) c->xs_enable = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_XH")) c->xh_enable = atoi(e) != 0;
@@ -84,7 +85,6 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
         c->tuning_ignored.emplace_back(k, e);      // (set, but this build does not know it: reported, never silently honoured)
 #endif
     }
-    if (const char* e = getenv("PSGSDF_PCG_FUSE_APPLY")) c->pcg_fuse_apply = atoi(e) != 0;
     if (hipDeviceGetAttribute(&c->num_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) c->num_cu = 0;
     c->set = *settings; c->reg_n = settings->reg_weight_n; c->reg_l = settings->reg_weight_l; c->reg_r = settings->reg_weight_rho;
     GridP& g = c->grid;
@@ -95,7 +95,6 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     g.vs = grid->voxel_size; g.vs_inv = 1.f / g.vs; g.T = grid->truncation;
     for (int a = 0; a < 3; ++a) g.origin[a] = c->shift[a] - (float)(0.5 * (double)g.vs) * (float)g.dim[a];   // VoxelGrid.h:130
     c->cam.fx = K[0]; c->cam.fy = K[4]; c->cam.cx = K[2]; c->cam.cy = K[5];
-    if (const char* e = getenv("PSGSDF_XR")) c->xr_enable = atoi(e) != 0;
     bool stream_ok;
     if (const char* e = getenv("PSGSDF_CU_MASK")) {      // "lo:hi": the context's stream runs on CUs [lo, hi) only -- two ranks sharing ONE GPU with half the CUs each (tests of the cross-rank persistent solve)
         int lo = 0, hi = 0;
@@ -106,16 +105,16 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
         c->cu_mask_lo = lo; c->cu_mask_hi = hi; c->num_cu = hi - lo;
     } else stream_ok = hipStreamCreate(&c->stream) == hipSuccess;
     bool ok = stream_ok
-        && hipMalloc(&c->pcg_sc, sizeof(double) * (16 + 8 * (size_t)kPcgMaxBlocks)) == hipSuccess   // fs[0..1] + stage stamps of the timing hook
-        && hipMalloc(&c->pcg_part, sizeof(double) * 14 * kPcgMaxBlocks) == hipSuccess
-        && hipMalloc(&c->pcg_gran, sizeof(double) * 2 * kSolveGranPlanes * kSolveMaxBlocksHost) == hipSuccess
-        && hipMalloc(&c->mg_scal, sizeof(double) * kMgScal) == hipSuccess && hipMalloc(&c->mg_ext, sizeof(double) * 8) == hipSuccess
-        && hipMalloc(&c->d_need, 2 * sizeof(int)) == hipSuccess
-        && hipMalloc(&c->d_total, sizeof(int)) == hipSuccess
-        && hipMalloc(&c->led_light, sizeof(float) * 3) == hipSuccess
-        && hipMalloc(&c->fs_stats, sizeof(double) * 8) == hipSuccess && hipMemset(c->fs_stats, 0, sizeof(double) * 8) == hipSuccess
+        && c->pcg_sc.alloc(16 + 8 * (size_t)kPcgMaxBlocks) == hipSuccess   // fs[0..1] + stage stamps of the timing hook
+        && c->pcg_part.alloc(14 * kPcgMaxBlocks) == hipSuccess
+        && c->pcg_gran.alloc(2 * kSolveGranPlanes * kSolveMaxBlocksHost) == hipSuccess
+        && c->mg_scal.alloc(kMgScal) == hipSuccess && c->mg_ext.alloc(8) == hipSuccess
+        && c->d_need.alloc(2) == hipSuccess
+        && c->d_total.alloc(1) == hipSuccess
+        && c->led_light.alloc(3) == hipSuccess
+        && c->fs_stats.alloc(8) == hipSuccess && hipMemset(c->fs_stats, 0, sizeof(double) * 8) == hipSuccess
         && hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess;
-    if (!ok) { delete c; return PSGSDF_ERR_DEVICE; }
+    if (!ok) { delete c; return PSGSDF_ERR_DEVICE; }      // (whatever was allocated goes with its owner)
     *out = c;
     return PSGSDF_OK;
 }
@@ -132,21 +131,10 @@ void psgsdf_destroy(psgsdf_ctx* c) {
         c->leak_exported = true;
         fprintf(stderr, "psgsdf: rank %d: a peer did not close its mappings of this rank's exchange memory within %.0f s (failed or still running?): that memory is leaked, not freed\n", c->rank, qt);
     }
-    free_dense(c);
-    hipFree(c->vis_seq); hipFree(c->frame_idx); hipFree(c->img); hipFree(c->img8); hipFree(c->frames); hipFree(c->frames_undo); hipFree(c->led_light); hipFree(c->fs_stats);
-    hipFree(c->band_mem); if (!c->leak_exported) hipFree(c->rec_mem); hipFree(c->obs_mem); hipFree(c->stage);
-    hipFree(c->ncache); hipFree(c->ntmp); hipFree(c->nout); hipFree(c->ndepth); hipFree(c->track_part); if (c->track_host) hipHostFree(c->track_host); hipFree(c->acc_frame); hipFree(c->frame_part); hipFree(c->frame_done); hipFree(c->part); hipFree(c->pcg_sc); hipFree(c->pcg_part); hipFree(c->pcg_gran); hipFree(c->win_tab); hipFree(c->d_total);
-    for (void* p : c->xo_host) if (p) hipHostFree(p);
-    if (c->pin_stage) hipHostFree(c->pin_stage);
-    if (c->host_buf) hipHostFree(c->host_buf);
-    if (c->mbox) hipHostFree(c->mbox);
-    if (c->ev0) hipEventDestroy(c->ev0); if (c->ev1) hipEventDestroy(c->ev1);
-    for (auto& pr : c->watch_pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    if (!c->leak_exported) { hipFree(c->xr); hipFree(c->hx_mem); }
-    hipFree(c->xf_table); hipFree(c->vm_order);
+    if (c->leak_exported) { (void)c->rec_mem.release(); (void)c->xr.release(); (void)c->hx_mem.release(); }
     comm_destroy(c);
-    hipFree(c->areg_mem); hipFree(c->mg_scal); hipFree(c->mg_ext); hipFree(c->mbox_shadow); hipFree(c->d_need);
-    if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
+    // everything else the context holds goes with its members, in no particular order: the stream is idle, the peers' mappings of the exported
+    // memory are closed (or that memory was given up above), and the communicator, which reduced in mg_scal / mg_ext / the mailbox shadow, is gone
     delete c;
 }
 
@@ -165,13 +153,12 @@ static int cut_slabs(psgsdf_ctx* c, std::vector<double>& cnt, int* z0, int* z1) 
     const int nz = c->gdim[2], n = c->n_ranks;
     if (nz < n) return fail(c, PSGSDF_ERR_UNSUPPORTED, "%d z-planes cannot be cut into %d slabs", nz, n);
     if (n > 1) {
-        double* d_cnt = nullptr;
-        HIPCHK(c, hipMalloc(&d_cnt, sizeof(double) * nz));
+        DevMem mem(c); double* d_cnt = nullptr;
+        if (!mem.get(&d_cnt, nz)) return fail(c, PSGSDF_ERR_DEVICE, "slab histogram: out of device memory");
         int rc = 0;
         if (hipMemcpyAsync(d_cnt, cnt.data(), sizeof(double) * nz, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "slab histogram upload");
         if (!rc) rc = comm_allreduce(c, d_cnt, nz);
         if (!rc && (hipMemcpyAsync(cnt.data(), d_cnt, sizeof(double) * nz, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = fail(c, PSGSDF_ERR_DEVICE, "slab histogram download");
-        hipFree(d_cnt);
         if (rc) return rc;
     }
     double total = 0; for (double x : cnt) total += x;
@@ -198,9 +185,9 @@ static int upload_planes(psgsdf_ctx* c, int z0, int z1, size_t src_n, size_t src
     { int rc = set_local_grid(c, z0, z1); if (rc) return rc; }
     const long long n = c->grid.nvox;
     free_dense(c);
-    if (c->vis_seq) { hipFree(c->vis_seq); c->vis_seq = nullptr; }
+    c->vis_seq.reset();
     int rc = alloc_dense(c, c->dense, n, 0, true); if (rc) return rc;
-    HIPCHK(c, hipMalloc(&c->vis_seq, sizeof(uint64_t) * n * words_per_voxel));
+    HIPCHK(c, c->vis_seq.alloc(n * words_per_voxel));
     c->wpv_seq = words_per_voxel;
     HIPCHK(c, hipMemcpyAsync(c->dense.dist, dist + src_off, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
     for (int a = 0; a < 3; ++a) {
@@ -254,10 +241,10 @@ int psgsdf_volume_init(psgsdf_ctx* c, int max_frames) {
     HIPCHK(c, hipSetDevice(c->device));
     const long long n = c->grid.nvox;
     free_dense(c);
-    if (c->vis_seq) { hipFree(c->vis_seq); c->vis_seq = nullptr; }
+    c->vis_seq.reset();
     int rc = alloc_dense(c, c->dense, n, 0, true); if (rc) return rc;
     c->wpv_seq = (max_frames + 63) / 64;
-    HIPCHK(c, hipMalloc(&c->vis_seq, sizeof(uint64_t) * n * c->wpv_seq));
+    HIPCHK(c, c->vis_seq.alloc(n * c->wpv_seq));
     launch_fill_f32(c->dense.dist, c->grid.T, n, c->stream);
     for (int a = 0; a < 3; ++a) { HIPCHK(c, hipMemsetAsync(c->dense.g[a], 0, sizeof(float) * n, c->stream)); HIPCHK(c, hipMemsetAsync(c->dense.rho[a], 0, sizeof(float) * n, c->stream)); }
     HIPCHK(c, hipMemsetAsync(c->dense.weight, 0, sizeof(float) * n, c->stream));
@@ -292,19 +279,17 @@ int psgsdf_rebalance_slabs(psgsdf_ctx* c) {
     std::vector<double> cuts((size_t)4 * R, 0.0);
     cuts[4 * c->rank] = oz0; cuts[4 * c->rank + 1] = oz1; cuts[4 * c->rank + 2] = nz0; cuts[4 * c->rank + 3] = nz1;
     { int rc = host_allreduce(c, cuts, "rebalance_slabs"); if (rc) return rc; }
-    // the new local grid and its arrays.  The new arrays are allocated BEFORE the context lets go of the old ones, and every error path frees what it
-    // allocated and leaves the context as it was (a failed allocation used to leak both sets and leave have_volume = true over empty arrays)
-    DenseView od = c->dense; uint64_t* ovis = c->vis_seq;
+    // the new local grid and its arrays.  The new arrays are allocated BEFORE the context lets go of the old ones, and an error path leaves the
+    // context as it was: the new arrays go with their owners (a failed allocation used to leak both sets and leave have_volume = true over empty arrays)
     const int nzlo = std::max(0, nz0 - 1), nzhi = std::min(nz, nz1 + 1);
     const long long n = (long long)(nzhi - nzlo) * (long long)plane;
-    DenseView nd{};
-    uint64_t* nvis = nullptr;
-    auto free_new = [&] { hipFree(nd.dist); for (int a = 0; a < 3; ++a) { hipFree(nd.g[a]); hipFree(nd.rho[a]); } hipFree(nd.weight); hipFree(nd.vis); hipFree(nd.row_of); hipFree(nvis); (void)hipGetLastError(); };
+    DensePlanes nd;
+    DevBuf<uint64_t> nvis;
     int rc = alloc_dense(c, nd, n, 0, true);
-    if (!rc && hipMalloc(&nvis, sizeof(uint64_t) * n * wpv) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "rebalance_slabs: out of memory");
-    if (rc) { free_new(); return rc; }
-    { int rc2 = set_local_grid(c, nz0, nz1); if (rc2) { free_new(); set_local_grid(c, oz0, oz1); return rc2; } }
-    c->dense = DenseView{}; c->vis_seq = nullptr;
+    if (!rc && nvis.alloc(n * wpv) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "rebalance_slabs: out of memory");
+    if (rc) { (void)hipGetLastError(); return rc; }
+    { int rc2 = set_local_grid(c, nz0, nz1); if (rc2) { set_local_grid(c, oz0, oz1); return rc2; } }
+    DensePlanes od = std::move(c->dense); DevBuf<uint64_t> ovis = std::move(c->vis_seq);
     float* oarr[8] = {od.dist, od.g[0], od.g[1], od.g[2], od.rho[0], od.rho[1], od.rho[2], od.weight};
     float* narr[8] = {nd.dist, nd.g[0], nd.g[1], nd.g[2], nd.rho[0], nd.rho[1], nd.rho[2], nd.weight};
     std::vector<psgsdf_comm_xfer> sends, recvs;
@@ -336,9 +321,8 @@ int psgsdf_rebalance_slabs(psgsdf_ctx* c) {
     }
     if (!rc) rc = comm_xfer(c, sends, recvs);      // (every rank enters the exchange unless its own local copies failed)
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "rebalance_slabs: exchange");
-    for (int q = 0; q < 8; ++q) hipFree(oarr[q]);
-    hipFree(od.vis); hipFree(od.row_of); hipFree(ovis); hipFree(c->block_sums); c->block_sums = nullptr;
-    c->dense = nd; c->vis_seq = nvis;
+    od.reset(); ovis.reset(); c->block_sums.reset();
+    c->dense = std::move(nd); c->vis_seq = std::move(nvis);
     c->inited = false;
     if (rc) c->have_volume = false;      // (a failed exchange leaves planes missing: the volume must be uploaded / fused again)
     return rc;
@@ -351,17 +335,17 @@ int psgsdf_integrate_frame(psgsdf_ctx* c, const float* rgb, const float* depth, 
     if (counter >= 64 * c->wpv_seq) {   // the sequence is longer than volume_init was told (the reference's vector<bool> simply grows): widen the per-voxel words
         const long long n = c->grid.nvox;
         const int wnew = std::max(2 * c->wpv_seq, counter / 64 + 1);
-        uint64_t* grown = nullptr;
-        HIPCHK(c, hipMalloc(&grown, sizeof(uint64_t) * n * wnew));
+        DevBuf<uint64_t> grown;
+        HIPCHK(c, grown.alloc(n * wnew));
         HIPCHK(c, hipMemsetAsync(grown, 0, sizeof(uint64_t) * n * wnew, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(grown, sizeof(uint64_t) * wnew, c->vis_seq, sizeof(uint64_t) * c->wpv_seq, sizeof(uint64_t) * c->wpv_seq, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->vis_seq); c->vis_seq = grown; c->wpv_seq = wnew;
+        c->vis_seq = std::move(grown); c->wpv_seq = wnew;
     }
     const size_t npx = (size_t)width * height;
     if (c->stage_px < npx) {
-        hipFree(c->stage); c->stage = nullptr; c->stage_px = 0;
-        HIPCHK(c, hipMalloc(&c->stage, sizeof(float) * npx * 7));
+        c->stage.reset(); c->stage_px = 0;
+        HIPCHK(c, c->stage.alloc(npx * 7));
         c->stage_px = npx;
     }
     float* d_rgb = c->stage; float* d_depth = c->stage + 3 * npx; float* d_nrm = c->stage + 4 * npx;
@@ -394,19 +378,18 @@ static int set_keyframes_impl(psgsdf_ctx* c, int n_frames, const int32_t* frame_
     if (n_frames > kMaxFramesLds) return fail(c, PSGSDF_ERR_UNSUPPORTED, "at most %d keyframes", kMaxFramesLds);
     if (rgb_u8 && ((size_t)n_frames * width * height >= ((size_t)1 << 30) || (size_t)n_frames * height >= ((size_t)1 << 24))) return fail(c, PSGSDF_ERR_UNSUPPORTED, "8-bit keyframes: at most 2^30 pixels and 2^24 image rows");
     HIPCHK(c, hipSetDevice(c->device));
-    hipFree(c->frame_idx); hipFree(c->img); hipFree(c->img8); hipFree(c->frames); hipFree(c->frames_undo); hipFree(c->acc_frame);
-    c->frame_idx = nullptr; c->img = nullptr; c->img8 = nullptr; c->frames = nullptr; c->frames_undo = nullptr; c->acc_frame = nullptr;
+    c->frame_idx.reset(); c->img.reset(); c->img8.reset(); c->frames.reset(); c->frames_undo.reset(); c->acc_frame.reset();
     c->F = n_frames; c->cam.W = width; c->cam.H = height;
     const size_t npix = (size_t)n_frames * width * height;
-    HIPCHK(c, hipMalloc(&c->frame_idx, sizeof(int) * n_frames));
-    HIPCHK(c, hipMalloc(&c->frames, sizeof(FrameP) * n_frames));
-    HIPCHK(c, hipMalloc(&c->frames_undo, sizeof(FrameP) * n_frames + 16));
+    HIPCHK(c, c->frame_idx.alloc(n_frames));
+    HIPCHK(c, c->frames.alloc(n_frames));
+    HIPCHK(c, c->frames_undo.alloc(sizeof(FrameP) / sizeof(float) * n_frames + 4));
     c->acc_frame_n = (size_t)n_frames * 64;
-    HIPCHK(c, hipMalloc(&c->acc_frame, sizeof(double) * c->acc_frame_n));
+    HIPCHK(c, c->acc_frame.alloc(c->acc_frame_n));
     HIPCHK(c, hipMemsetAsync(c->acc_frame, 0, sizeof(double) * c->acc_frame_n, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->frame_idx, frame_idx, sizeof(int) * n_frames, hipMemcpyHostToDevice, c->stream));
     if (rgb_f32 || rgb_f32_frames) {
-        HIPCHK(c, hipMalloc(&c->img, sizeof(float) * npix * 3));
+        HIPCHK(c, c->img.alloc(npix * 3));
         const size_t per = (size_t)width * height * 3;
         if (rgb_f32) HIPCHK(c, hipMemcpyAsync(c->img, rgb_f32, sizeof(float) * npix * 3, hipMemcpyHostToDevice, c->stream));
         else for (int f = 0; f < n_frames; ++f) HIPCHK(c, hipMemcpyAsync(c->img + per * f, rgb_f32_frames[f], sizeof(float) * per, hipMemcpyHostToDevice, c->stream));      // one image per allocation (the reference's std::vector<cv::Mat>): no gather on the host
@@ -416,34 +399,34 @@ static int set_keyframes_impl(psgsdf_ctx* c, int n_frames, const int32_t* frame_
         if (c->img_compact && npix < ((size_t)1 << 30) && (size_t)n_frames * height < ((size_t)1 << 24)) {
             const float scale = 1.0f / 255.0f;
             // a sample first (every 61st pixel, nothing written: data that is not 8-bit at all is recognised in microseconds), the full pass only behind a clean sample
-            int* d_flags = nullptr; std::vector<int> h_flags(kTryPackFlags);
-            HIPCHK(c, hipMalloc(&d_flags, sizeof(int) * kTryPackFlags));
-            auto any_miss = [&](unsigned* out, size_t stride, int* bad) -> int {
-                if (hipMemsetAsync(d_flags, 0, sizeof(int) * kTryPackFlags, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: 8-bit check");
-                launch_try_pack_f32(c->img, out, npix, stride, scale, d_flags, c->stream);
-                if (hipMemcpyAsync(h_flags.data(), d_flags, sizeof(int) * kTryPackFlags, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: 8-bit check");
-                *bad = 0; for (int v : h_flags) *bad |= v;
-                return 0;
-            };
-            int bad = 1;
-            int prc = any_miss(nullptr, 61, &bad);
-            if (!prc && !bad) {
-                if (hipMalloc(&c->img8, sizeof(unsigned) * npix) != hipSuccess) prc = fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: out of memory");
-                else prc = any_miss(c->img8, 1, &bad);
+            int bad = 1, prc;
+            {
+                DevMem mem(c); int* d_flags = nullptr; std::vector<int> h_flags(kTryPackFlags);      // (the flags go before either copy of the images does)
+                if (!mem.get(&d_flags, kTryPackFlags)) return fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: out of memory");
+                auto any_miss = [&](unsigned* out, size_t stride, int* bad) -> int {
+                    if (hipMemsetAsync(d_flags, 0, sizeof(int) * kTryPackFlags, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: 8-bit check");
+                    launch_try_pack_f32(c->img, out, npix, stride, scale, d_flags, c->stream);
+                    if (hipMemcpyAsync(h_flags.data(), d_flags, sizeof(int) * kTryPackFlags, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: 8-bit check");
+                    *bad = 0; for (int v : h_flags) *bad |= v;
+                    return 0;
+                };
+                prc = any_miss(nullptr, 61, &bad);
+                if (!prc && !bad) {
+                    if (c->img8.alloc(npix) != hipSuccess) prc = fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: out of memory");
+                    else prc = any_miss(c->img8, 1, &bad);
+                }
             }
-            hipFree(d_flags);
             if (prc) return prc;
-            if (bad) { hipFree(c->img8); c->img8 = nullptr; }
-            else { hipFree(c->img); c->img = nullptr; c->img_scale = scale; c->img_compacted = true; }
+            if (bad) c->img8.reset();
+            else { c->img.reset(); c->img_scale = scale; c->img_compacted = true; }
         }
     } else {
-        uint8_t* tmp = nullptr;
-        HIPCHK(c, hipMalloc(&c->img8, sizeof(unsigned) * npix));
-        HIPCHK(c, hipMalloc(&tmp, npix * 3));
+        DevMem mem(c); uint8_t* tmp = nullptr;
+        HIPCHK(c, c->img8.alloc(npix));
+        if (!mem.get(&tmp, npix * 3)) return fail(c, PSGSDF_ERR_DEVICE, "set_keyframes: out of memory");
         HIPCHK(c, hipMemcpyAsync(tmp, rgb_u8, npix * 3, hipMemcpyHostToDevice, c->stream));
         launch_pack_rgb8(tmp, c->img8, npix, c->stream);
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(tmp);
         c->img_scale = scale;
     }
     c->frames_h.assign(n_frames, FrameP{});
@@ -471,9 +454,7 @@ int psgsdf_init(psgsdf_ctx* c) {
     if (!c->vis_seq) return fail(c, PSGSDF_ERR_STATE, "init: volume was refined; upload it again");
     HIPCHK(c, hipSetDevice(c->device));
     const int KW = (c->F + 63) / 64;
-    if (c->dense.vis) { hipFree(c->dense.vis); c->dense.vis = nullptr; }
-    HIPCHK(c, hipMalloc(&c->dense.vis, sizeof(uint64_t) * c->grid.nvox * KW));
-    c->dense.KW = KW;
+    HIPCHK(c, c->dense.alloc_vis(c->grid.nvox, KW));
     timed(c, "select_vis", [&] { launch_select_vis(c->vis_seq, c->wpv_seq, c->dense.vis, KW, c->frame_idx, c->F, c->grid.nvox, c->stream); });
     int rc = build_band(c); if (rc) return rc;
     // light initialisation: PsOptimizer.cpp:30-37 l = SH(R*(0,0,-1)), l[0] = 0.02 ; LED: ones, then intensity ratio

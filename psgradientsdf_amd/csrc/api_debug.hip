@@ -196,18 +196,15 @@ int psgsdf_debug_frame_cg(psgsdf_ctx* c, int nb, int n, const float* H, const fl
     if (!c || !H || !b || !x || nb <= 0) return fail(c, PSGSDF_ERR_ARG, "null argument");
     if ((n != 3 && n != 4 && n != 6 && n != 9) || (long long)nb * n > 2048) return fail(c, PSGSDF_ERR_UNSUPPORTED, "block size %d x %d blocks", n, nb);
     HIPCHK(c, hipSetDevice(c->device));
+    DevMem mem(c);
     float *dH = nullptr, *db = nullptr, *dx = nullptr; double* ds = nullptr;
     const size_t nH = (size_t)nb * n * n, nv = (size_t)nb * n;
-    int rc = PSGSDF_OK;
-    if (hipMalloc(&dH, sizeof(float) * nH) != hipSuccess || hipMalloc(&db, sizeof(float) * nv) != hipSuccess || hipMalloc(&dx, sizeof(float) * nv) != hipSuccess || hipMalloc(&ds, sizeof(double) * 4) != hipSuccess)
-        rc = fail(c, PSGSDF_ERR_DEVICE, "out of device memory");
+    if (!mem.get(&dH, nH) || !mem.get(&db, nv) || !mem.get(&dx, nv) || !mem.get(&ds, 4)) return fail(c, PSGSDF_ERR_DEVICE, "out of device memory");
     double st[4] = {0, 0, 0, 0};
-    if (!rc && (hipMemcpy(dH, H, sizeof(float) * nH, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(db, b, sizeof(float) * nv, hipMemcpyHostToDevice) != hipSuccess)) rc = fail(c, PSGSDF_ERR_DEVICE, "upload failed");
-    if (!rc && launch_frames_eigen_raw(nb, n, dH, db, dx, ds, max_it, c->stream)) rc = fail(c, PSGSDF_ERR_UNSUPPORTED, "shape");
-    if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(x, dx, sizeof(float) * nv, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(st, ds, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess))
-        rc = fail(c, PSGSDF_ERR_DEVICE, "%s", hipGetErrorString(hipGetLastError()));
-    hipFree(dH); hipFree(db); hipFree(dx); hipFree(ds);
-    if (rc) return rc;
+    if (hipMemcpy(dH, H, sizeof(float) * nH, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(db, b, sizeof(float) * nv, hipMemcpyHostToDevice) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "upload failed");
+    if (launch_frames_eigen_raw(nb, n, dH, db, dx, ds, max_it, c->stream)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "shape");
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(x, dx, sizeof(float) * nv, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(st, ds, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(c, PSGSDF_ERR_DEVICE, "%s", hipGetErrorString(hipGetLastError()));
     if (iterations) *iterations = (int32_t)st[0];
     if (error) *error = st[1];
     if (converged) *converged = (int32_t)st[2];

@@ -9,15 +9,14 @@ namespace {
 int normals_cache(psgsdf_ctx* c, int W, int H) {
     if (c->ncache && c->ncache_w == W && c->ncache_h == H) return 0;
     const size_t n = (size_t)W * H;
-    hipFree(c->ncache); hipFree(c->ntmp); hipFree(c->nout); hipFree(c->ndepth); c->ncache = nullptr; c->ntmp = nullptr; c->nout = nullptr; c->ndepth = nullptr;
+    c->ncache.reset(); c->ntmp.reset(); c->nout.reset(); c->ndepth.reset();
     // on the device (round 5; frontend.hip k_ncache_*): the same doubles in the same order as the host loop this replaces
-    HIPCHK(c, hipMalloc(&c->ncache, sizeof(float) * 9 * n)); HIPCHK(c, hipMalloc(&c->ntmp, sizeof(double) * 3 * n));
-    HIPCHK(c, hipMalloc(&c->nout, sizeof(float) * 3 * n)); HIPCHK(c, hipMalloc(&c->ndepth, sizeof(float) * n));
-    double* work = nullptr;
-    HIPCHK(c, hipMalloc(&work, sizeof(double) * 12 * n));
+    HIPCHK(c, c->ncache.alloc(9 * n)); HIPCHK(c, c->ntmp.alloc(3 * n));
+    HIPCHK(c, c->nout.alloc(3 * n)); HIPCHK(c, c->ndepth.alloc(n));
+    DevMem mem(c); double* work = nullptr;
+    if (!mem.get(&work, 12 * n)) return fail(c, PSGSDF_ERR_DEVICE, "normals cache: out of memory");
     timed(c, "normals_cache", [&] { launch_normals_cache(W, H, 5, 1. / (double)c->cam.fx, 1. / (double)c->cam.fy, (double)c->cam.cx, (double)c->cam.cy, work, c->ncache, c->stream); });
     const hipError_t e = hipStreamSynchronize(c->stream);
-    hipFree(work);
     if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "normals cache: %s", hipGetErrorString(e));
     c->ncache_w = W; c->ncache_h = H;
     return 0;
@@ -63,7 +62,7 @@ extern "C" int psgsdf_track(psgsdf_ctx* c, const float* depth, int width, int he
     const size_t n = (size_t)width * height;
     int rc = normals_cache(c, width, height); if (rc) return rc;   // (allocates the depth staging buffer)
     const int nblk = 256;
-    if (!c->track_part) { HIPCHK(c, hipMalloc(&c->track_part, sizeof(double) * nblk * 29)); HIPCHK(c, hipHostMalloc(&c->track_host, sizeof(double) * nblk * 29)); }
+    if (!c->track_part) { HIPCHK(c, c->track_part.alloc(nblk * 29)); HIPCHK(c, c->track_host.alloc(nblk * 29)); }
     { void* hs = nullptr; int src = host_stage(c, sizeof(float) * n, &hs); if (src) return src; memcpy(hs, depth, sizeof(float) * n);
       HIPCHK(c, hipMemcpyAsync(c->ndepth, hs, sizeof(float) * n, hipMemcpyHostToDevice, c->stream)); }
     Cam cam = c->cam; cam.W = width; cam.H = height;

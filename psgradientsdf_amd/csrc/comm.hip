@@ -325,13 +325,12 @@ __global__ void __launch_bounds__(256) k_xr_probe(double* myF, const float4* myP
 }  // namespace
 // all-reduce (sum over the ranks) of a host vector of doubles through a scratch device buffer
 int host_allreduce(psgsdf_ctx* c, std::vector<double>& buf, const char* what) {
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(double) * buf.size()));
+    DevMem mem(c); double* d = nullptr;
+    if (!mem.get(&d, buf.size())) return fail(c, PSGSDF_ERR_DEVICE, "%s: out of device memory", what);
     int rc = 0;
     if (hipMemcpyAsync(d, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: upload", what);
     if (!rc) rc = comm_allreduce(c, d, (int)buf.size());
     if (!rc && (hipMemcpyAsync(buf.data(), d, sizeof(double) * buf.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = fail(c, PSGSDF_ERR_DEVICE, "%s: download", what);
-    hipFree(d);
     return rc;
 }
 namespace {
@@ -355,12 +354,14 @@ int xr_probe(psgsdf_ctx* c) {
     constexpr int kSlice = 64 + 64 + 2;
     for (int kind = 1; kind <= 2; ++kind) {
         if (want == 1 || want == 2) { if (kind != want) continue; }
-        double* F = nullptr; float4* P = nullptr; double* out = nullptr;
+        DevBuf<double> F, out; DevBuf<float4> P;      // (go at the end of this round: after the mappings are closed and the barrier below)
         hipIpcMemHandle_t hF{}, hP{};
-        bool ok = c->xr_enable
-            && hipExtMallocWithFlags((void**)&F, sizeof(double) * kProbeFlagDoubles, hipDeviceMallocUncached) == hipSuccess
-            && (want == 3 ? hipMalloc((void**)&P, sizeof(float4) * kProbeRecs) : hipExtMallocWithFlags((void**)&P, sizeof(float4) * kProbeRecs, kind == 1 ? hipDeviceMallocFinegrained : hipDeviceMallocUncached)) == hipSuccess
-            && hipMalloc((void**)&out, sizeof(double) * 4) == hipSuccess
+        // the kind under test: flags always uncached, the payload fine-grained (kind 1) or uncached (kind 2) -- or plain memory if PSGSDF_XR_MEM=coarse asks for it
+        auto probe_mem = [&](size_t bytes, int k) { void* q = nullptr; const hipError_t e = k == 3 ? hipMalloc(&q, bytes) : hipExtMallocWithFlags(&q, bytes, k == 1 ? hipDeviceMallocFinegrained : hipDeviceMallocUncached); return e == hipSuccess ? q : nullptr; };
+        bool ok = c->xr_enable;
+        if (ok) { F.adopt(probe_mem(sizeof(double) * kProbeFlagDoubles, 2)); ok = F != nullptr; }
+        if (ok) { P.adopt(probe_mem(sizeof(float4) * kProbeRecs, want == 3 ? 3 : kind)); ok = P != nullptr; }
+        ok = ok && out.alloc(4) == hipSuccess
             && hipMemsetAsync(F, 0, sizeof(double) * kProbeFlagDoubles, c->stream) == hipSuccess && hipMemsetAsync(P, 0, sizeof(float4) * kProbeRecs, c->stream) == hipSuccess
             && hipMemsetAsync(out, 0, sizeof(double) * 4, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess
             && hipIpcGetMemHandle(&hF, F) == hipSuccess && hipIpcGetMemHandle(&hP, P) == hipSuccess;
@@ -386,7 +387,7 @@ int xr_probe(psgsdf_ctx* c) {
         }
         std::vector<double> res(3, 0.0);
         if (!rc && ok) {
-            hipLaunchKernelGGL(k_xr_probe, dim3(2), dim3(256), 0, c->stream, F, (const float4*)P, loF, hiF, hiP, me > 0 ? 1 : 0, me < R - 1 ? 1 : 0, out);
+            hipLaunchKernelGGL(k_xr_probe, dim3(2), dim3(256), 0, c->stream, (double*)F, (const float4*)P, loF, hiF, hiP, me > 0 ? 1 : 0, me < R - 1 ? 1 : 0, (double*)out);
             double o[4] = {0, 0, 0, 0};
             if (hipMemcpyAsync(o, out, sizeof(o), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PSGSDF_ERR_DEVICE, "cross-rank probe: kernel");
             res[0] = o[0]; res[1] = o[1] + o[2]; res[2] = 1.0;
@@ -397,7 +398,7 @@ int xr_probe(psgsdf_ctx* c) {
         // close before anybody frees: mappings first, then a barrier, then the allocations
         for (void* p : opened) hipIpcCloseMemHandle(p);
         if (!rc) { std::vector<double> bar(1, 1.0); rc = host_allreduce(c, bar, "cross-rank probe"); }
-        hipFree(F); hipFree(P); hipFree(out);
+        F.reset(); P.reset(); out.reset();
         (void)hipGetLastError();
         if (rc) return rc;
         if (ok && res[2] == (double)R && res[0] == 0.0 && res[1] == 0.0) { c->xr_mem_kind = want == 3 ? 3 : kind; break; }
@@ -476,12 +477,13 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     const size_t want = (size_t)kXrDoubles + frows * kFrameRow + frows + (size_t)2 * R * 8 + (size_t)2 * R + 8 + (size_t)R;      // (+ 4 flags of the halo pushes, comm_halo; + one "closed" slot per rank, xr_release / xr_quiesce)
     // halo staging: what the two neighbours push of their cut-side rows (comm_halo): [2 parities][lower side: need_lo rows | upper side: need_hi rows] x kHxWords words
     const size_t hx_par = sizeof(unsigned) * kHxWords * ((size_t)c->need[0] + c->need[1]);
-    if (c->hx_mem) { hipFree(c->hx_mem); c->hx_mem = nullptr; }
-    if (ok && c->xh_enable && hx_par) { if (xr_alloc(c, &c->hx_mem, 2 * hx_par, false)) { (void)hipGetLastError(); c->hx_mem = nullptr; } }
+    c->hx_mem.reset();
+    if (ok && c->xh_enable && hx_par) { void* q = nullptr; if (xr_alloc(c, &q, 2 * hx_par, false)) (void)hipGetLastError(); c->hx_mem.adopt(q); }
     const bool hx_ok = ok && c->hx_mem && hipIpcGetMemHandle(&hh, c->hx_mem) == hipSuccess;
-    if (ok && c->xr && c->xr_doubles < want) { hipFree(c->xr); c->xr = nullptr; c->xr_doubles = 0; }
+    if (ok && c->xr && c->xr_doubles < want) { c->xr.reset(); c->xr_doubles = 0; }
     if (ok && !c->xr) {
-        if (xr_alloc(c, (void**)&c->xr, sizeof(double) * want, true) || hipMemsetAsync(c->xr, 0, sizeof(double) * want, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
+        void* q = nullptr; const int arc = xr_alloc(c, &q, sizeof(double) * want, true); c->xr.adopt(q);
+        if (arc || hipMemsetAsync(c->xr, 0, sizeof(double) * want, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
         else c->xr_doubles = want;
     }
     ok = ok && cgf_solve_shape(c, &Gs, &Rs, true)      // (this slab fits the persistent kernel at all)
@@ -502,7 +504,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     }
     double* mine = buf.data() + (size_t)me * kSlice;
     handle_to_doubles(hx, mine); handle_to_doubles(hb, mine + 64);
-    mine[128] = (double)((char*)c->band.rec[0] - (char*)c->rec_mem); mine[129] = (double)((char*)c->band.rec[1] - (char*)c->rec_mem);
+    mine[128] = (double)((char*)c->band.rec[0] - (char*)(float4*)c->rec_mem); mine[129] = (double)((char*)c->band.rec[1] - (char*)(float4*)c->rec_mem);
     mine[130] = (double)getpid(); mine[131] = ok ? 1.0 : 0.0; mine[133] = nonce;
     mine[132] = (hx_ok || (ok && c->xh_enable && !hx_par)) ? 1.0 : 0.0;      // (a rank that needs no halo rows has nothing to stage and is fine with the pushes)
     if (hx_ok) handle_to_doubles(hh, mine + 136);
@@ -576,7 +578,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     if (ok) {      // the frame rows' exchange table (the flags carry the exchange's number, which only grows: the zeroed region matches none)
         XfTable t{}; t.n_ranks = R; t.rank = me; t.F = std::max(c->F, 1); t.spin_max = c->xwait_spins; t.pay = kXrDoubles; t.flg = (long long)kXrDoubles + (long long)frows * kFrameRow; t.spay = t.flg + (long long)frows; t.sflg = t.spay + (long long)2 * R * 8;
         for (int r = 0; r < R; ++r) t.region[r] = c->xr_peer[r];
-        if (!c->xf_table && hipMalloc(&c->xf_table, sizeof(XfTable)) != hipSuccess) ok = false;
+        if (!c->xf_table && c->xf_table.alloc(1) != hipSuccess) ok = false;
         if (ok && hipMemcpyAsync(c->xf_table, &t, sizeof(t), hipMemcpyHostToDevice, c->stream) != hipSuccess) ok = false;
         if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
     }

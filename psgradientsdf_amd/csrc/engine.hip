@@ -233,27 +233,14 @@ int reserve_frame_energy_deferred(psgsdf_ctx* c, std::function<void(double, doub
 }
 int ensure_host_buf(psgsdf_ctx* c, size_t n) {
     if (n <= c->host_buf_n) return 0;
-    if (c->host_buf) hipHostFree(c->host_buf);
-    c->host_buf = nullptr; c->host_buf_n = 0;
-    HIPCHK(c, hipHostMalloc(&c->host_buf, sizeof(double) * n));
+    c->host_buf.reset(); c->host_buf_n = 0;
+    HIPCHK(c, c->host_buf.alloc(n));
     c->host_buf_n = n;
     return 0;
 }
 
-void free_dense(psgsdf_ctx* c) {
-    hipFree(c->dense.dist); for (int a = 0; a < 3; ++a) { hipFree(c->dense.g[a]); hipFree(c->dense.rho[a]); }
-    hipFree(c->dense.weight); hipFree(c->dense.vis); hipFree(c->dense.row_of); hipFree(c->block_sums);
-    c->dense = DenseView{}; c->block_sums = nullptr;
-}
-int alloc_dense(psgsdf_ctx* c, DenseView& d, long long nvox, int KW, bool with_rowof) {
-    HIPCHK(c, hipMalloc(&d.dist, sizeof(float) * nvox));
-    for (int a = 0; a < 3; ++a) { HIPCHK(c, hipMalloc(&d.g[a], sizeof(float) * nvox)); HIPCHK(c, hipMalloc(&d.rho[a], sizeof(float) * nvox)); }
-    HIPCHK(c, hipMalloc(&d.weight, sizeof(float) * nvox));
-    d.KW = KW;
-    if (KW > 0) HIPCHK(c, hipMalloc(&d.vis, sizeof(uint64_t) * nvox * KW));
-    if (with_rowof) HIPCHK(c, hipMalloc(&d.row_of, sizeof(int) * nvox));
-    return 0;
-}
+void free_dense(psgsdf_ctx* c) { c->dense.reset(); c->block_sums.reset(); }
+int alloc_dense(psgsdf_ctx* c, DensePlanes& d, long long nvox, int KW, bool with_rowof) { HIPCHK(c, d.alloc(nvox, KW, with_rowof)); return 0; }
 
 // (re)build the band from the dense grid: flags -> scan -> compact planes -> neighbour tables
 int build_band(psgsdf_ctx* c) {
@@ -265,7 +252,7 @@ int build_band(psgsdf_ctx* c) {
     c->persist_off = false;          // a persistent solve that gave up did so on the previous band's launch shape / mappings: this band tries again
     const long long nvox = c->grid.nvox;
     const int KW = c->dense.KW;
-    if (!c->block_sums) HIPCHK(c, hipMalloc(&c->block_sums, sizeof(int) * ((nvox + 1023) / 1024 + 1)));
+    if (!c->block_sums) HIPCHK(c, c->block_sums.alloc((nvox + 1023) / 1024 + 1));
     timed(c, "band_flags", [&] { launch_band_flags(c->dense.dist, c->dense.vis, KW, c->grid.vs, nvox, c->dense.row_of, c->stream); });
     timed(c, "band_scan", [&] { launch_band_scan(c->dense.row_of, nvox, c->block_sums, c->d_total, c->stream); });
     int S = 0;
@@ -275,19 +262,18 @@ int build_band(psgsdf_ctx* c) {
     // planes (4-byte units per row): see Band
     const size_t n4 = 1 + 1 + 3 + 3 + 6 + 6 + kNQ + 12 + 6 + 14 + kNQ + 4 + 9 + 1 + 3;   // (xs, gn, nfd live in the packed planes vp: 12 instead of 9 words; the two record planes are an allocation of their own)
     const size_t bytes = (n4 * 4 + (size_t)KW * 8) * Spad + 256;
-    if (c->band_mem) { hipFree(c->band_mem); c->band_mem = nullptr; }
-    if (c->rec_mem) { hipFree(c->rec_mem); c->rec_mem = nullptr; }
-    HIPCHK(c, hipMalloc(&c->band_mem, bytes));
+    c->band_mem.reset(); c->rec_mem.reset();      // (both old arenas go before either new one is allocated)
+    HIPCHK(c, c->band_mem.alloc(bytes));
     HIPCHK(c, hipMemsetAsync(c->band_mem, 0, bytes, c->stream));
-    { int rc = xr_alloc(c, &c->rec_mem, 2 * sizeof(float4) * (size_t)Spad, false); if (rc) return rc; }      // (fine-grained / uncached on a multi-rank context: the neighbours' kernels write its halo rows)
+    { void* rec = nullptr; int rc = xr_alloc(c, &rec, 2 * sizeof(float4) * (size_t)Spad, false); c->rec_mem.adopt(rec); if (rc) return rc; }      // (fine-grained / uncached on a multi-rank context: the neighbours' kernels write its halo rows)
     HIPCHK(c, hipMemsetAsync(c->rec_mem, 0, 2 * sizeof(float4) * (size_t)Spad, c->stream));
     c->band_bytes = bytes;
-    char* p = (char*)c->band_mem;
+    char* p = c->band_mem;
     auto take = [&](size_t elems, size_t esz) { void* r = p; p += elems * esz * Spad; return r; };
     Band& b = c->band;
     b.S = S; b.Spad = Spad; b.KW = KW;
     b.vis = (uint64_t*)take(KW, 8);
-    b.rec[0] = (float4*)c->rec_mem; b.rec[1] = b.rec[0] + Spad;
+    b.rec[0] = c->rec_mem; b.rec[1] = b.rec[0] + Spad;
     b.lin = (int*)take(1, 4);
     b.dist = (float*)take(1, 4);
     for (int a = 0; a < 3; ++a) b.g[a] = (float*)take(1, 4);
@@ -348,12 +334,12 @@ int build_band(psgsdf_ctx* c) {
             if ((hrc = xr_setup(c, info))) return hrc;      // cross-rank persistent solve: map the neighbours' halo rows and every rank's mailbox region
         } else c->S_global = S;
     }
-    if (c->areg_mem) { hipFree(c->areg_mem); c->areg_mem = nullptr; c->ar = AlbedoReg{}; }
+    if (c->areg_mem) { c->areg_mem.reset(); c->ar = AlbedoReg{}; }
     if (c->reg_r != 0.f) {   // "reg albedo": stencil tables + matrix-free CG vectors over the 3S unknowns
         const size_t planes = 3 + 1 + 9 + 12 + 3 + 8 * 3 + 1;      // (+ 1: the device-driven CG's scalars)
-        HIPCHK(c, hipMalloc(&c->areg_mem, planes * 4 * (size_t)Spad));
+        HIPCHK(c, c->areg_mem.alloc(planes * 4 * (size_t)Spad));
         HIPCHK(c, hipMemsetAsync(c->areg_mem, 0, planes * 4 * (size_t)Spad, c->stream));
-        char* q = (char*)c->areg_mem;
+        char* q = c->areg_mem;
         auto tk = [&](size_t n) { void* r = q; q += n * 4 * (size_t)Spad; return r; };
         AlbedoReg& ar = c->ar;
         ar.anb = (int*)tk(3); ar.back = (int*)tk(1); ar.anrho = (float*)tk(9); ar.J = (float*)tk(12); ar.res = (float*)tk(3);
@@ -366,11 +352,11 @@ int build_band(psgsdf_ctx* c) {
     // per-frame observation lists of the owned rows (counts -> host prefix -> fill)
     {
         const int nch = (c->row1 - c->row0 + kObsChunk - 1) / kObsChunk, F = c->F;
-        if (c->obs_mem) { hipFree(c->obs_mem); c->obs_mem = nullptr; }
+        c->obs_mem.reset();
         b.obs_ptr = nullptr; b.obs_rows = nullptr; b.obs_max = 0; b.obs_ptr_total = 0;
         if (nch > 0 && F > 0) {
-            int* d_counts = nullptr;
-            HIPCHK(c, hipMalloc(&d_counts, sizeof(int) * (size_t)nch * F));
+            DevMem mem(c); int* d_counts = nullptr;
+            if (!mem.get(&d_counts, (size_t)nch * F)) return fail(c, PSGSDF_ERR_DEVICE, "observation lists: out of memory");
             launch_obs_count(b, F, c->row0, c->row1, d_counts, c->stream);
             std::vector<int> cnt((size_t)nch * F), off((size_t)nch * F), ptr(F + 1);
             HIPCHK(c, hipMemcpyAsync(cnt.data(), d_counts, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, c->stream));
@@ -378,39 +364,37 @@ int build_band(psgsdf_ctx* c) {
             int run = 0, mx = 0;
             for (int f = 0; f < F; ++f) { ptr[f] = run; for (int k = 0; k < nch; ++k) { off[(size_t)f * nch + k] = run; run += cnt[(size_t)f * nch + k]; } mx = std::max(mx, run - ptr[f]); }
             ptr[F] = run;
-            HIPCHK(c, hipMalloc(&c->obs_mem, sizeof(int) * ((size_t)run + F + 2)));
-            b.obs_ptr = (int*)c->obs_mem; b.obs_rows = b.obs_ptr + (F + 1); b.obs_max = mx; b.obs_ptr_total = run;
+            HIPCHK(c, c->obs_mem.alloc((size_t)run + F + 2));
+            b.obs_ptr = c->obs_mem; b.obs_rows = b.obs_ptr + (F + 1); b.obs_max = mx; b.obs_ptr_total = run;
             HIPCHK(c, hipMemcpyAsync(b.obs_ptr, ptr.data(), sizeof(int) * (F + 1), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(d_counts, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, c->stream));
             launch_obs_fill(b, F, c->row0, c->row1, d_counts, c->stream);
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            hipFree(d_counts);
         }
     }
     {   // dispatch order of the voxel-major distance sweep: blocks sorted by their work, heaviest first (the sweep needs 1.3 generations of resident
         // workgroups: what is dispatched last should be short).  Logical ids carry rows and partial-sum slots: results do not depend on the order.
-        if (c->vm_order) { hipFree(c->vm_order); c->vm_order = nullptr; }
+        c->vm_order.reset();
         const int nb = (c->row1 - c->row0 + kBlock - 1) / kBlock;
         if (nb > 1) {
-            int* d_work = nullptr;
-            HIPCHK(c, hipMalloc(&d_work, sizeof(int) * nb));
+            DevMem mem(c); int* d_work = nullptr;
+            if (!mem.get(&d_work, (size_t)nb)) return fail(c, PSGSDF_ERR_DEVICE, "dispatch order: out of memory");
             launch_block_work(b, c->row0, c->row1, d_work, c->stream);
             std::vector<int> work(nb), order(nb);
             HIPCHK(c, hipMemcpyAsync(work.data(), d_work, sizeof(int) * nb, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             for (int i = 0; i < nb; ++i) order[i] = i;
             std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return work[x] > work[y]; });
-            HIPCHK(c, hipMalloc(&c->vm_order, sizeof(int) * nb));
+            HIPCHK(c, c->vm_order.alloc(nb));
             HIPCHK(c, hipMemcpyAsync(c->vm_order, order.data(), sizeof(int) * nb, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            hipFree(d_work);
         }
     }
     {   // the LDS windows of the persistent solve's partition: the band is fixed until it is rebuilt, and so is what every workgroup's rows reference
         c->win_G = c->win_rows = c->win_max = 0;
         int Gs = 0, Rs = 0;
         if (c->pcg_window && c->n_ranks <= 1 && cgf_solve_shape(c, &Gs, &Rs)) {
-            if (!c->win_tab) HIPCHK(c, hipMalloc(&c->win_tab, sizeof(int) * (6 * kSolveMaxBlocksHost + 1)));
+            if (!c->win_tab) HIPCHK(c, c->win_tab.alloc(6 * kSolveMaxBlocksHost + 1));
             int* d_max = c->win_tab + 6 * kSolveMaxBlocksHost;
             launch_solve_windows(b, c->row0, c->row1, Gs, Rs, c->win_tab, d_max, c->stream);
             int mx = 0;
@@ -428,30 +412,27 @@ int build_band(psgsdf_ctx* c) {
         c->any_empty_slab = e[0] != 0.0;
     }
     {   // partial rows of the frame-major sweeps: one per workgroup and frame; a sweep uses at most ceil(obs_max / (256 * 4)) workgroups per frame
-        if (c->frame_part) { hipFree(c->frame_part); c->frame_part = nullptr; }
-        if (c->frame_done) { hipFree(c->frame_done); c->frame_done = nullptr; }
+        c->frame_part.reset(); c->frame_done.reset();
         c->frame_cap = (b.obs_max + kBlock * 4 - 1) / (kBlock * 4) + 1;
         const int F = std::max(c->F, 1);
-        HIPCHK(c, hipMalloc(&c->frame_part, sizeof(double) * (size_t)F * c->frame_cap * kFrameRow));
-        HIPCHK(c, hipMalloc(&c->frame_done, sizeof(int) * (F + 1)));      // (+ 1: the sweep's finished-frames counter, frame_rows_publish fm_solve)
+        HIPCHK(c, c->frame_part.alloc((size_t)F * c->frame_cap * kFrameRow));
+        HIPCHK(c, c->frame_done.alloc(F + 1));      // (+ 1: the sweep's finished-frames counter, frame_rows_publish fm_solve)
         HIPCHK(c, hipMemsetAsync(c->frame_done, 0, sizeof(int) * (F + 1), c->stream));
     }
-    if (c->part) { hipFree(c->part); c->part = nullptr; }
     c->PB = Spad / kBlock + 1;
-    HIPCHK(c, hipMalloc(&c->part, sizeof(double) * SC_COUNT * c->PB));
+    HIPCHK(c, c->part.alloc((size_t)SC_COUNT * c->PB));
     HIPCHK(c, hipMemsetAsync(c->part, 0, sizeof(double) * SC_COUNT * c->PB, c->stream));
     {
         const size_t need = 4096;
         if (need > c->mbox_alloc) {
-            if (c->mbox) hipHostFree(c->mbox);
-            c->mbox = nullptr; c->mbox_n = 0; c->mbox_alloc = 0;
-            HIPCHK(c, hipHostMalloc(&c->mbox, sizeof(double) * need, hipHostMallocMapped));
+            c->mbox.reset(); c->mbox_n = 0; c->mbox_alloc = 0;
+            HIPCHK(c, c->mbox.alloc(need, hipHostMallocMapped));
             HIPCHK(c, hipHostGetDevicePointer((void**)&c->mbox_dev, c->mbox, 0));
             c->mbox_alloc = need; c->mbox_n = need - 2;      // [mbox_n] = flush marker, [mbox_n + 1] = the "a halo pull gave up" word (comm.hip k_halo_pull)
             memset(c->mbox, 0, sizeof(double) * need); c->flush_seq = 0;
         }
         if (slab_mode(c) && !c->mbox_shadow) {
-            HIPCHK(c, hipMalloc(&c->mbox_shadow, sizeof(double) * c->mbox_alloc));
+            HIPCHK(c, c->mbox_shadow.alloc(c->mbox_alloc));
             HIPCHK(c, hipMemsetAsync(c->mbox_shadow, 0, sizeof(double) * c->mbox_alloc, c->stream));
         }
         c->mbox_used = 0; c->deferred.clear(); c->mg_segs.clear();

@@ -12,9 +12,13 @@
 //   extract_compare.hip  the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h)
 //   extract_curvature.hip  curvature per voxel, per vertex of the welded mesh and as a map of the bake (include/psgsdf_curvature.h)
 //   extract_fill.hip  unobserved voxels filled from their neighbours, and the welded mesh and components of the filled state (include/psgsdf_fill.h)
+// Who frees what: every device or pinned allocation has ONE owner (device_own.h).  What lives as long as the context is a DevBuf / PinBuf /
+// DensePlanes member of psgsdf_ctx and goes with `delete c`; what lives for one call is handed out by a DevMem of that call.  A raw pointer in
+// the context points INTO something (an arena, a mapping, the mailbox): its comment says what.
 // Internal: nothing here is part of the boundary (include/psgsdf.h).
 #pragma once
 #include "engine.h"
+#include "device_own.h"
 #include "../../include/psgsdf.h"
 
 #include <math.h>
@@ -63,6 +67,8 @@ enum XoSlot {
 }  // namespace psge
 using psge::KTime;
 using namespace psg;   // the layout structs of engine.h
+using psge::DevBuf; using psge::PinBuf;
+using DensePlanes = psge::DensePlanesOf<DenseView>;   // the dense planes and the kernels' view of them
 
 struct psgsdf_ctx {
     int device = 0;
@@ -77,54 +83,54 @@ struct psgsdf_ctx {
     float shift[3]{};
     Cam cam{};
     // dense
-    DenseView dense{};
-    uint64_t* vis_seq = nullptr; int wpv_seq = 0;
-    int* block_sums = nullptr; int* d_total = nullptr;
+    DensePlanes dense;
+    DevBuf<uint64_t> vis_seq; int wpv_seq = 0;
+    DevBuf<int> block_sums, d_total;
     bool have_volume = false;
     // frames
     int F = 0;
-    int* frame_idx = nullptr;
-    float* img = nullptr;
-    FrameP* frames = nullptr;            // device
+    DevBuf<int> frame_idx;
+    DevBuf<float> img;
+    DevBuf<FrameP> frames;               // device
     std::vector<FrameP> frames_h;        // host mirror of the initial records
-    float* led_light = nullptr;          // device [3]
+    DevBuf<float> led_light;             // device [3]
     bool have_frames = false;
     // band
-    void* band_mem = nullptr; size_t band_bytes = 0;
-    void* rec_mem = nullptr;             // the two PCG record planes (Band::rec): an allocation of their own, fine-grained on a multi-rank context (the neighbours' solve kernels write its halo rows while this rank's kernel reads them)
-    void* obs_mem = nullptr;
-    float* stage = nullptr; size_t stage_px = 0;   // device staging of one RGB-D frame (integrate_frame)
-    void* pin_stage = nullptr; size_t pin_bytes = 0;   // pinned host staging of the caller's frame (host_stage): the DMA never has to pin the caller's pages
+    DevBuf<char> band_mem; size_t band_bytes = 0;   // the arena the planes of `band` point into
+    DevBuf<float4> rec_mem;              // the two PCG record planes (Band::rec): an allocation of their own, fine-grained on a multi-rank context (the neighbours' solve kernels write its halo rows while this rank's kernel reads them)
+    DevBuf<int> obs_mem;                 // Band::obs_ptr | obs_rows
+    DevBuf<float> stage; size_t stage_px = 0;   // device staging of one RGB-D frame (integrate_frame)
+    PinBuf<char> pin_stage; size_t pin_bytes = 0;   // pinned host staging of the caller's frame (host_stage): the DMA never has to pin the caller's pages
     // front end: FALS cache (9 float planes), box-filter scratch, tracker partials
-    float* ncache = nullptr; double* ntmp = nullptr; float* nout = nullptr; float* ndepth = nullptr; int ncache_w = 0, ncache_h = 0;
-    double* track_part = nullptr; double* track_host = nullptr;
-    Band band{};
+    DevBuf<float> ncache; DevBuf<double> ntmp; DevBuf<float> nout, ndepth; int ncache_w = 0, ncache_h = 0;
+    DevBuf<double> track_part; PinBuf<double> track_host;
+    Band band{};                         // its members point into band_mem, rec_mem and obs_mem
     bool inited = false;
     // accumulators
-    double* acc_frame = nullptr; size_t acc_frame_n = 0;
-    double* frame_part = nullptr; int frame_cap = 0;   // [F][frame_cap][kFrameRow] per-workgroup partial rows of the frame-major sweeps
-    int* frame_done = nullptr;                         // [F] arrival counters
-    double* part = nullptr; int PB = 0;  // [SC_COUNT][PB] per-workgroup partials
-    double* pcg_sc = nullptr; int pcg_cap = 4096;
-    double* pcg_part = nullptr;          // [2][7][kPcgMaxBlocks]
-    double* pcg_gran = nullptr;          // persistent solve: [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums
+    DevBuf<double> acc_frame; size_t acc_frame_n = 0;
+    DevBuf<double> frame_part; int frame_cap = 0;   // [F][frame_cap][kFrameRow] per-workgroup partial rows of the frame-major sweeps
+    DevBuf<int> frame_done;                            // [F] arrival counters
+    DevBuf<double> part; int PB = 0;  // [SC_COUNT][PB] per-workgroup partials
+    DevBuf<double> pcg_sc; int pcg_cap = 4096;
+    DevBuf<double> pcg_part;             // [2][7][kPcgMaxBlocks]
+    DevBuf<double> pcg_gran;             // persistent solve: [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums
     unsigned pcg_solve_serial = 0;       // distance solves launched on this context (SweepArgs::pcg_epoch)
     int pcg_ablate = 0;                  // PSGSDF_PCG_ABLATE: timing ablations of the persistent solve, bits 1 and 4 (wrong results; tools only)
     bool pcg_fuse_apply = true;          // PSGSDF_PCG_FUSE_APPLY=0: k_apply_dist behind it
     bool pcg_persist = true;             // PSGSDF_PCG_PERSIST=0: always the per-pass kernels
     bool pcg_window = true;              // PSGSDF_PCG_WINDOW=0: the single-rank pipelined solve gathers per thread instead of reading an LDS window (pcg_solve.h k_cgp_solve<.., WIN>)
     int pcg_solve_rows = 0;              // PSGSDF_PCG_SOLVE_ROWS: rows per workgroup of the persistent solve on one rank (0: as many workgroups as CUs); tests shape the partition with it
-    int* win_tab = nullptr;              // [6 kSolveMaxBlocksHost + 1] window table of this band and partition (pcg.hip k_solve_windows) + its largest total
+    DevBuf<int> win_tab;                 // [6 kSolveMaxBlocksHost + 1] window table of this band and partition (pcg.hip k_solve_windows) + its largest total
     int win_G = 0, win_rows = 0, win_max = 0;      // ... the partition it was computed for (0: no table) and the largest window in doubles
     int last_solve_windowed = -1;        // the last persistent distance solve ran the windowed instance (1) or not (0); -1: none yet
     bool persist_off = false;            // a persistent solve gave up on this band (bounded wait expired): per-pass kernels until the next band is built (build_band re-arms)
     int num_cu = 0;
     int last_cg_iters = 0;
     bool want_counts = true;             // read back the accepted-update counts (debug statistic of the reference)
-    double* host_buf = nullptr; size_t host_buf_n = 0;   // pinned readback
+    PinBuf<double> host_buf; size_t host_buf_n = 0;   // pinned readback
     // deferred read-backs: small fold kernels write into a host-mapped pinned mailbox (no D2H copies), consumed at the
     // next host sync
-    double* mbox = nullptr; double* mbox_dev = nullptr; size_t mbox_n = 0, mbox_used = 0;
+    PinBuf<double> mbox; double* mbox_dev = nullptr; size_t mbox_n = 0, mbox_used = 0;   // mbox_dev: the device address of mbox (the same mapped memory)
     size_t mbox_alloc = 0; double flush_seq = 0;    // the last slot of the allocation is the flush marker
     std::vector<psge::Deferred> deferred;
     unsigned long long mbox_serial = 0;  // key generator of the read-back slots
@@ -135,7 +141,7 @@ struct psgsdf_ctx {
     int on_iter_period = 1;              // psgsdf_set_on_iter_period
     bool speculate = true;               // PSGSDF_SPECULATE=0: always wait for the decision first (round 2)
     bool spec_undo = false, spec_albedo_saved = false, spec_light_saved = false;
-    FrameP* frames_undo = nullptr;       // device [F] + 3 floats (LED light)
+    DevBuf<float> frames_undo;           // device: the [F] frame records as floats + 4 floats (LED light)
     long long spec_windows = 0, spec_undos = 0;
     int fault_solve = 0, solves_seen = 0;   // PSGSDF_FAULT_SOLVE=n: fault injection into the n-th persistent solve of this context
     long long persist_fallbacks = 0;     // distance steps re-run on the per-pass kernels after the persistent solve gave up (loop.hip)
@@ -150,7 +156,7 @@ struct psgsdf_ctx {
     // neighbours' band arenas mapped through IPC handles; rebuilt with every band
     bool xr_enable = true;               // PSGSDF_XR=0: multi-rank contexts always use the per-pass kernels + RCCL all-reduce (round 2)
     bool xr_ready = false; long long xr_solves = 0;
-    double* xr = nullptr;
+    DevBuf<double> xr;
     int xr_mem_kind = -1;                // memory kind of xr / rec_mem chosen by xr_probe: 1 fine-grained records + uncached region, 2 both uncached, 0 none passed (cross-rank solve off); -1 not probed yet
     long long xr_probe_stale = 0, xr_probe_timeouts = 0;   // what the probe saw (all ranks, all kinds tried)
     long long xr_probe_local[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // [memory kind 1 / 2][stale records read from the lower neighbour, expired waits towards the lower, towards the upper neighbour, tried]: this rank's own view (psgsdf_get_tuning)
@@ -158,25 +164,25 @@ struct psgsdf_ctx {
     std::shared_ptr<void> comm_keep;     // what a built-in caller-side transport (psgsdf_comm_init_sockets) needs for the life of the context
     unsigned long long xr_openers = 0;   // bit r: rank r opened this rank's region at the last set-up (agreed there); xr_quiesce waits for exactly those
     long long xr_serial = 0, xr_closed_off = 0;   // number of the last set-up (the same on every rank) and where the R "closed" slots of a region sit
-    void* xo_host[psge::XO_COUNT] = {}; size_t xo_bytes[psge::XO_COUNT] = {};   // pinned host results of the extraction calls, one slot per array (psge::XoSlot); the three indexed-mesh calls share XO_IMESH_*: a result is valid until the next extraction
+    PinBuf<char> xo_host[psge::XO_COUNT]; size_t xo_bytes[psge::XO_COUNT] = {};   // pinned host results of the extraction calls, one slot per array (psge::XoSlot); the three indexed-mesh calls share XO_IMESH_*: a result is valid until the next extraction
     long long xr_stale_maps = 0;         // mappings that did not show their owner's nonce (xr_setup)
     bool leak_exported = false;          // a peer never reported its mappings closed: xr / rec_mem / hx_mem are never freed by this context
-    std::vector<double*> xr_peer;        // [n_ranks] (own entry = xr)
-    void* band_peer[2] = {nullptr, nullptr};   // lower / upper neighbour's band arena
-    std::vector<void*> xr_opened;        // IPC mappings to close
+    std::vector<double*> xr_peer;        // [n_ranks] every rank's region: IPC mappings (own entry = xr)
+    void* band_peer[2] = {nullptr, nullptr};   // lower / upper neighbour's record planes: IPC mappings
+    std::vector<void*> xr_opened;        // every IPC mapping this context opened: closed, not freed (comm.hip xr_release)
     XrArgs xr_args{};
     int cu_mask_lo = -1, cu_mask_hi = -1;      // PSGSDF_CU_MASK=lo:hi: the context's stream only uses CUs [lo, hi) (two ranks sharing one GPU)
-    double* mg_scal = nullptr;           // [kMgScal] set-up exchange (what each slab needs of its neighbours)
-    double* mg_ext = nullptr;            // [8] PCG: local sums of a pass out, globally reduced sums in
+    DevBuf<double> mg_scal;              // [kMgScal] set-up exchange (what each slab needs of its neighbours)
+    DevBuf<double> mg_ext;               // [8] PCG: local sums of a pass out, globally reduced sums in
     // multi-rank: deferred scalar read-backs are folded into a DEVICE shadow of the mailbox; before the host waits on the mailbox the
     // segments written since the last commit are all-reduced in ONE collective and copied to their mailbox slots (engine.hip: mg_commit)
-    double* mbox_shadow = nullptr;
+    DevBuf<double> mbox_shadow;
     std::vector<psge::MgSeg> mg_segs;
     int give[2] = {0, 0};                // rows the lower / upper neighbour needs of this slab
     bool halo_active = false;            // any stencil of any slab crosses a cut
     long long n_collectives = 0;
     float reg_r = 0.f;                   // "reg albedo" (never normalised, PsOptimizer.cpp:279)
-    void* areg_mem = nullptr; AlbedoReg ar{};   // planes of the albedo regulariser, allocated with the band when reg_r != 0
+    DevBuf<char> areg_mem; AlbedoReg ar{};   // planes of the albedo regulariser (ar points into areg_mem), allocated with the band when reg_r != 0
     bool areg_device = true; int areg_last_iters = 0;      // PSGSDF_AREG_DEVICE=0: the regularised albedo solve driven by the host (two read-backs per CG iteration: what multi-rank contexts run)
     double er_sum = 0;                   // sum over the band of sum_c ||grad rho_c|| at the last evaluation
     FoldReq pending_fold{};              // scalar fold waiting for the next kernel (read_parts_deferred / take_fold)
@@ -186,15 +192,15 @@ struct psgsdf_ctx {
     int xwait_spins = 1 << 24;           // polls of a wait inside a kernel for a peer's flag (PSGSDF_XWAIT_LOG2)
     long long fault_halo = 0;            // PSGSDF_FAULT_HALO
     bool xh_enable = true;               // PSGSDF_XH=0: halo rows through RCCL send / recv (round 3)
-    void* hx_mem = nullptr;              // halo staging the two neighbours push into (fine-grained, IPC-exported): [2 parities][lower | upper side]
-    char* hx_peer[2] = {nullptr, nullptr};   // the neighbours' stagings (lower, upper), mapped
+    DevBuf<char> hx_mem;                 // halo staging the two neighbours push into (fine-grained, IPC-exported): [2 parities][lower | upper side]
+    char* hx_peer[2] = {nullptr, nullptr};   // the neighbours' stagings (lower, upper): IPC mappings
     size_t hx_peer_par[2] = {0, 0}, hx_peer_off[2] = {0, 0}, hx_par = 0;
     long long hx_flag_off = 0, hx_epoch = 0, n_halo_pushes = 0;
     bool hx_ready = false;
     bool xs_enable = true;               // PSGSDF_XS=0: multi-rank scalar read-backs staged in the mailbox shadow and all-reduced over RCCL (round 3)
     long long xs_epoch = 0;              // scalar folds exchanged so far (the same on every rank)
     bool xf_enable = true;               // PSGSDF_XF=0: multi-rank frame rows through an RCCL all-reduce + solve kernels (round 3)
-    XfTable* xf_table = nullptr;         // device copy of the exchange table (valid while xr_ready)
+    DevBuf<XfTable> xf_table;            // device copy of the exchange table (valid while xr_ready)
     long long xf_epoch = 0;              // exchanges so far (the same on every rank)
     size_t xr_doubles = 0;               // size of this rank's mailbox region
     bool any_empty_slab = false;         // some rank's slab has no observation at all (agreed at band build)
@@ -202,23 +208,23 @@ struct psgsdf_ctx {
     bool img_compact = true;             // PSGSDF_IMG_COMPACT=0: float keyframes stay float even when every value is (float)byte / 255
     bool img_compacted = false;          // the float keyframes of this context are held as RGBA8 words
     bool speculate_mr = true;            // PSGSDF_SPECULATE_MR=0: no speculative start of the next iteration on multi-rank contexts (round 3's loop)
-    int* vm_order = nullptr;             // distance sweep: physical workgroup -> logical block, heaviest first (build_band)
+    DevBuf<int> vm_order;                // distance sweep: physical workgroup -> logical block, heaviest first (build_band)
     int xcd_map = 163;                   // PSGSDF_XCD_MAP: logical workgroup ids -- bit 0 frame-major sweeps XCD-contiguous, bit 1 k_sweep_albedo / k_energy / k_derive XCD-contiguous, bit 2 k_sweep_dist XCD-contiguous (off: 68 -> 76 us), bit 5 (32) k_sweep_dist heaviest block first (70 -> 62 us), bit 6 (64) albedo / energy heaviest first (no gain), bit 7 (128) the per-pass distance solve k_cgf_pass XCD-contiguous (round 6); PSGSDF_XCD_STRIPE=T: stripes of T ids instead of eighths
     bool fm_solve = true;                // PSGSDF_FM_SOLVE=0: k_solve_light / k_solve_pose as kernels of their own behind the frame-major sweeps
     bool fm_solve_led = true;            // ... also the LED light vector (by the sweep's very last workgroup); PSGSDF_FM_SOLVE=2 keeps k_solve_light for it
     bool fm_solved = false;              // the sweep just launched solves its frames itself (step_begin -> step_finish)
     int frame_solve = 0;                 // PSGSDF_FRAME_SOLVE / psgsdf_set_frame_solver: 0 = LDL^T per frame in double (default), 1 = the reference's solver: ONE Eigen-style float Jacobi-PCG over the block-diagonal system of all frames (frame_solve.hip)
-    double* fs_stats = nullptr;          // device [2][4]: {iterations, ||r||/||b||, Success, applied} of the last eigen light / pose solve
+    DevBuf<double> fs_stats;             // device [2][4]: {iterations, ||r||/||b||, Success, applied} of the last eigen light / pose solve
     double fs_last[2][4] = {{0, 0, 1, 1}, {0, 0, 1, 1}};   // host copy, refreshed by the synchronous steps (psgsdf_step, psgsdf_get_frame_solver_stats)
     bool albedo_applied = false;         // the last albedo sweep already applied its update (step_begin -> step_finish)
-    unsigned* img8 = nullptr; float img_scale = 0.f;   // keyframes uploaded as 8-bit RGB (psgsdf_set_keyframes_u8): RGBA8 words, c->img stays null
-    double* frame_e_slot = nullptr; unsigned long long frame_e_key = 0;   // mailbox slot (and its key) the next per-frame solve writes its sweep's energy sums to
+    DevBuf<unsigned> img8; float img_scale = 0.f;   // keyframes uploaded as 8-bit RGB (psgsdf_set_keyframes_u8): RGBA8 words, c->img stays null
+    double* frame_e_slot = nullptr; unsigned long long frame_e_key = 0;   // slot of mbox, as the device addresses it (and its key), the next per-frame solve writes its sweep's energy sums to
     bool ao_cut = true;                  // PSGSDF_AO_CUT=0: the rays of include/psgsdf_occlusion.h walk on past their radius (what the cut buys: tools/time_mesh.py; the same bits)
     long long compare_chunk = 1ll << 24; // PSGSDF_COMPARE_CHUNK: queries per launch of include/psgsdf_compare.h's search (1 .. 2^24; the same bits)
     long long cmp_pairs[2] = {0, 0}, cmp_queries[2] = {0, 0};   // the last psgsdf_compare_reference: candidate pairs evaluated and queries, per direction (psgsdf_get_tuning "last_compare"; tools/time_compare.py)
     long long aln_evals = 0, aln_iters = 0, aln_pairs[2] = {0, 0}, aln_queries[2] = {0, 0};   // the last psgsdf_align_reference: evaluations, steps, and per direction the queries searched and candidate pairs evaluated over all evaluations (psgsdf_get_tuning "last_align"; tools/time_align.py)
     bool pcg_poll = true;                // PCG stop test by watching the mapped mailbox (PSGSDF_PCG_POLL=0: drain the stream instead)
-    int need[2] = {0, 0}; int* d_need = nullptr;   // halo rows needed below row0 / from row1 up
+    int need[2] = {0, 0}; DevBuf<int> d_need;   // halo rows needed below row0 / from row1 up
     bool own_stream = true;
     // profiling
     bool profiling = false;
@@ -231,6 +237,12 @@ struct psgsdf_ctx {
     size_t watch_used = 0; int watch_every = 1; size_t watch_seen = 0;
     std::vector<std::pair<std::string, std::string>> tuning_env, tuning_ignored;   // environment knobs as they stood when the context was created / dev-only ones this build ignores (psgsdf_get_tuning)
     char err[512] = {0};
+    // the memory goes with its members; what is left are the runtime's own objects
+    ~psgsdf_ctx() {
+        if (stream && own_stream) hipStreamDestroy(stream);
+        if (ev0) hipEventDestroy(ev0); if (ev1) hipEventDestroy(ev1);
+        for (auto& pr : watch_pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+    }
 };
 
 namespace psge {
@@ -331,7 +343,7 @@ void fold_by_kernel(psgsdf_ctx* c, FoldReq& f);   // the fold as a kernel of its
 void take_fold(psgsdf_ctx* c, SweepArgs& a, unsigned writes);
 int ensure_host_buf(psgsdf_ctx* c, size_t n);
 void free_dense(psgsdf_ctx* c);
-int alloc_dense(psgsdf_ctx* c, DenseView& d, long long nvox, int KW, bool with_rowof);
+int alloc_dense(psgsdf_ctx* c, DensePlanes& d, long long nvox, int KW, bool with_rowof);   // every plane or none
 int build_band(psgsdf_ctx* c);
 int derive(psgsdf_ctx* c, int update_grad);
 int ps_energy(psgsdf_ctx* c, double* E, int64_t* nobs);

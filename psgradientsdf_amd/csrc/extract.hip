@@ -246,9 +246,8 @@ int scan_counts(psgsdf_ctx* c, int* v, long long n, int* sums, int* total_host) 
 }
 int host_out(psgsdf_ctx* c, XoSlot slot, size_t bytes, void** p) {
     if (c->xo_bytes[slot] < bytes) {
-        if (c->xo_host[slot]) hipHostFree(c->xo_host[slot]);
-        c->xo_host[slot] = nullptr; c->xo_bytes[slot] = 0;
-        HIPCHK(c, hipHostMalloc(&c->xo_host[slot], std::max<size_t>(bytes, 4096), hipHostMallocDefault));
+        c->xo_host[slot].reset(); c->xo_bytes[slot] = 0;
+        HIPCHK(c, c->xo_host[slot].alloc(std::max<size_t>(bytes, 4096)));
         c->xo_bytes[slot] = std::max<size_t>(bytes, 4096);
     }
     *p = c->xo_host[slot];

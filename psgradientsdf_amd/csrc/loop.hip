@@ -656,13 +656,13 @@ int do_upsample(psgsdf_ctx* c) {
     if ((rc = comm_halo(c, c->band.rho[0], 3, 1))) return rc;
     if ((rc = comm_halo(c, c->band.g[0], 3, 1))) return rc;
     timed(c, "band_scatter", [&] { launch_band_scatter(c->dense, c->band, c->stream); });
-    DenseView nd{};
+    DensePlanes nd;
     const long long nn = 8 * c->grid.nvox;
     if ((rc = alloc_dense(c, nd, nn, c->dense.KW, true))) return rc;
     timed(c, "upsample", [&] { launch_upsample(c->dense, nd, c->grid, c->stream); });
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_dense(c);
-    if (c->vis_seq) { hipFree(c->vis_seq); c->vis_seq = nullptr; }
+    c->vis_seq.reset();
     const int old_zlo = c->zlo;
     for (int a = 0; a < 3; ++a) c->gdim[a] *= 2;
     c->gnvox *= 8;
@@ -671,10 +671,10 @@ int do_upsample(psgsdf_ctx* c) {
     for (int a = 0; a < 3; ++a) g.origin[a] = c->shift[a] - (float)(0.5 * (double)g.vs) * (float)c->gdim[a] - (float)(0.5 * (double)g.vs) * 1.0f;   // VoxelGrid.h:143-149
     g.vs_inv = (float)(1.0 / (double)g.vs);
     if ((rc = set_local_grid(c, 2 * c->z0, 2 * c->z1))) return rc;
-    if (g.nvox == nn) c->dense = nd;                                  // one rank, or a slab without halo planes: the refined grid is the local grid
+    if (g.nvox == nn) c->dense = std::move(nd);                       // one rank, or a slab without halo planes: the refined grid is the local grid
     else {                                                            // drop the outer child plane of each refined halo plane
         const size_t plane = (size_t)g.dim[0] * g.dim[1], skip = (size_t)(c->zlo - 2 * old_zlo) * plane, n = (size_t)g.nvox;
-        DenseView td{};
+        DensePlanes td;
         if ((rc = alloc_dense(c, td, g.nvox, nd.KW, true))) return rc;
         HIPCHK(c, hipMemcpyAsync(td.dist, nd.dist + skip, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(td.weight, nd.weight + skip, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
@@ -684,9 +684,8 @@ int do_upsample(psgsdf_ctx* c) {
         }
         HIPCHK(c, hipMemcpyAsync(td.vis, nd.vis + skip * nd.KW, sizeof(uint64_t) * n * nd.KW, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(nd.dist); hipFree(nd.weight); hipFree(nd.vis); hipFree(nd.row_of);
-        for (int a = 0; a < 3; ++a) { hipFree(nd.g[a]); hipFree(nd.rho[a]); }
-        c->dense = td;
+        nd.reset();
+        c->dense = std::move(td);
     }
     if ((rc = build_band(c))) return rc;
     return derive(c, 0);

@@ -270,3 +270,21 @@ def test_voxelps_gpus_n_without_a_device_fails_loudly_and_ends_every_rank(built,
         assert "stopping the other ranks" in r.stderr or "no RCCL on this node" in r.stderr, r.stderr[-800:]
     r = subprocess.run([os.path.join(ROOT, "psgradientsdf_amd", "host", "voxelPS"), "--config_file", out + "config.json", "--gpus", "2", "--host-writers"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 1 and "single-process cross-check" in r.stderr
+
+
+def test_memory_owners_on_their_failure_paths(tmp_path):
+    """csrc/device_own.h (DevBuf, PinBuf, the dense planes' owner) where no green run goes: a failed allocation returns its error and leaves the owner
+    empty, reset / destruction / release of an empty owner are harmless, a move transfers and empties its source, and the dense owner whose first
+    plane cannot be allocated holds nothing.  tests/own_check.hip is a program of its own, built with the host's address and undefined-behaviour
+    sanitizers and run directly, with every device hidden from it: all allocations fail (and the sizes it asks for, 2^62 bytes, would anyway)."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "own_check")
+    b = subprocess.run([hipcc, "-std=c++17", "--offload-arch=gfx950", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-g",
+                        "-I", os.path.join(ROOT, "psgradientsdf_amd", "csrc"), os.path.join(ROOT, "tests", "own_check.hip"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-2000:]
+    # (no device for the sanitized program, wherever this runs: it is about the paths on which allocations fail)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1"))
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-500:], r.stderr[-2000:])
