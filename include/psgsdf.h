@@ -431,6 +431,8 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* ctx, int64_t out[8]);
  *   PSGSDF_WAIT_TIMEOUT_S*, PSGSDF_DESTROY_TIMEOUT_S*, PSGSDF_SOLVE_DUMP*                                                           host waits / diagnostics
  *   PSGSDF_AO_CUT (0: the rays of psgsdf_occlusion.h walk on past their radius; the same bits)                                     ambient occlusion
  *   PSGSDF_COMPARE_CHUNK (queries per launch of psgsdf_compare.h's search, 1 .. 2^24, default 2^24; the same bits)                  comparison with a reference
+ *   PSGSDF_QUERY_CHUNK (queries per launch of psgsdf_query.h's kernels, a multiple of 64 up to 2^30, default 2^30; anything else makes
+ *   psgsdf_create return PSGSDF_ERR_ARG; the same bits)                                                                             field queries
  * DESIGN.md section 4 has the table with defaults and measured effects.
  * NOT in libpsgsdf.so: PSGSDF_FAULT_SOLVE, PSGSDF_FAULT_HALO (fault injection), PSGSDF_PCG_ABLATE (timing ablations: results are WRONG),
  * PSGSDF_MBOX_CHECK=0 (re-opens a race fixed in round 3).  They exist only in the development build libpsgsdf_dev.so (-DPSGSDF_DEV) the tests and

@@ -99,6 +99,31 @@ class BakeAo(C.Structure):      # psgsdf_bake_ao
                 ("n_dirs", C.c_int32), ("reserved", C.c_int32), ("counts", AoCounts)]
 
 
+class QueryCounts(C.Structure):      # psgsdf_query_counts (include/psgsdf_query.h)
+    _fields_ = [(k, C.c_int64) for k in ("n", "n_ok", "n_outside", "n_unobserved", "n_invalid")]
+
+
+class ProjectParams(C.Structure):      # psgsdf_project_params
+    _fields_ = [("model", C.c_int32), ("max_iters", C.c_int32), ("tol", C.c_double), ("reserved", C.c_double)]
+
+
+class ProjectCounts(C.Structure):      # psgsdf_project_counts
+    _fields_ = [(k, C.c_int64) for k in ("n", "n_converged", "n_left", "n_not_converged", "n_invalid")]
+
+
+class RayParams(C.Structure):      # psgsdf_ray_params
+    _fields_ = [("t_min", C.c_double), ("t_max", C.c_double)]
+
+
+class RayCounts(C.Structure):      # psgsdf_ray_counts
+    _fields_ = [(k, C.c_int64) for k in ("n", "n_valid", "n_hits", "n_buried")]
+
+
+QUERY_MODELS = {"cell": 0, "trilinear": 1}
+Q_OK, Q_OUTSIDE, Q_UNOBSERVED, Q_INVALID, Q_NOT_CONVERGED = 0, 1, 2, 3, 4
+RAY_HIT, RAY_MISS, RAY_BURIED, RAY_INVALID = 0, 1, 2, 3
+
+
 class BakeCurvature(C.Structure):      # psgsdf_bake_curvature (include/psgsdf_curvature.h)
     _fields_ = [("bake", Bake), ("mean", C.POINTER(C.c_float)), ("valid", C.POINTER(C.c_uint8)), ("n_valid", C.c_int64)]
 
@@ -691,6 +716,56 @@ class Api:
         H, W = out["height"], out["width"]
         out.update(occlusion=_owned(b.occlusion, (H, W), np.uint8), mask=_owned(b.mask, (H, W), np.uint64), dirs=_owned(b.dirs, (b.n_dirs, 3), np.float64), counts=_counts(b.counts))
         return out
+
+    # -- the field at the caller's points and along the caller's rays (include/psgsdf_query.h)
+    @staticmethod
+    def _query_model(model):
+        return QUERY_MODELS[model] if isinstance(model, str) else int(model)
+
+    def query_points(self, xyz, model="trilinear"):
+        """The field at the caller's points xyz [n, 3] (float32, the mesh's units; psgsdf_query_points) under `model`: "cell", the renderer's
+        first-order model of the point's cell, or "trilinear", the cell the mesher cuts (or the header's 0 / 1).  dict of status [n] uint8 (0 ok,
+        1 outside the grid, 2 unobserved, 3 not finite), dist [n], normal [n, 3], rgb [n, 3], weight [n] float32 (zeros unless the status is 0),
+        voxel [n] int64 (-1: none) and counts, a dict of n, n_ok, n_outside, n_unobserved, n_invalid.  Single contexts only."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        st = _U8P(); dist, nrm, rgb, wgt = _F32P(), _F32P(), _F32P(), _F32P(); vox = C.POINTER(C.c_int64)(); cnt = QueryCounts()
+        self._check(self._fn("query_points")(self.ctx, xyz.ctypes.data_as(_F32P) if n else None, C.c_int64(n), C.c_int32(self._query_model(model)), C.byref(st), C.byref(dist),
+                                             C.byref(nrm), C.byref(rgb), C.byref(wgt), C.byref(vox), C.byref(cnt)), "query_points")
+        return dict(status=_owned(st, (n,), np.uint8), dist=_owned(dist, (n,), np.float32), normal=_owned(nrm, (n, 3), np.float32), rgb=_owned(rgb, (n, 3), np.float32),
+                    weight=_owned(wgt, (n,), np.float32), voxel=_owned(vox, (n,), np.int64), counts=_counts(cnt))
+
+    def project_points(self, xyz, model="trilinear", tol=None, max_iters=16, reserved=0.0):
+        """The caller's points moved onto the model's zero set by steps of phi along the model's normal (psgsdf_project_points) until |phi| <= tol
+        (None: 1e-3 voxel), the point leaves the observed grid, or max_iters (1 .. 64) moves are made.  dict of status [n] uint8 (as query_points;
+        4: not converged), xyz [n, 3] float32 the point at the stop, residual [n] float32 the model there, normal [n, 3] float32, voxel [n] int64,
+        iterations [n] uint8 the moves made, distance [n] float32 the length moved, negative for a point that started inside, and counts, a dict
+        of n, n_converged, n_left, n_not_converged, n_invalid.  Single contexts only."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        p = ProjectParams(self._query_model(model), int(max_iters), float(1e-3 * self._vs() if tol is None else tol), float(reserved))
+        st, it = _U8P(), _U8P(); out, res, nrm, moved = _F32P(), _F32P(), _F32P(), _F32P(); vox = C.POINTER(C.c_int64)(); cnt = ProjectCounts()
+        self._check(self._fn("project_points")(self.ctx, xyz.ctypes.data_as(_F32P) if n else None, C.c_int64(n), C.byref(p), C.byref(st), C.byref(out), C.byref(res), C.byref(nrm),
+                                               C.byref(vox), C.byref(it), C.byref(moved), C.byref(cnt)), "project_points")
+        return dict(status=_owned(st, (n,), np.uint8), xyz=_owned(out, (n, 3), np.float32), residual=_owned(res, (n,), np.float32), normal=_owned(nrm, (n, 3), np.float32),
+                    voxel=_owned(vox, (n,), np.int64), iterations=_owned(it, (n,), np.uint8), distance=_owned(moved, (n,), np.float32), counts=_counts(cnt))
+
+    def cast_rays(self, origins, directions, t_min=0.0, t_max=None):
+        """What the caller's rays hit (psgsdf_cast_rays): origins, directions [n, 3] float32 (the mesh's units; a direction of any length > 0), each
+        walked through the renderer's cells from t_min to t_max (None: no limit), lengths along the ray in mesh units.  dict of status [n] uint8
+        (0 hit, 1 miss, 2 buried: the ray starts at or below the surface, a hit at t_min, 3 invalid), t [n], xyz [n, 3], normal [n, 3], rgb [n, 3]
+        float32 (zeros unless the ray hits), voxel [n] int64 the hit cell (-1: none) and counts, a dict of n, n_valid, n_hits, n_buried.
+        Single contexts only."""
+        origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3); directions = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(origins) != len(directions):
+            raise ValueError("cast_rays: origins and directions differ in length")
+        n = len(origins)
+        p = RayParams(float(t_min), float("inf") if t_max is None else float(t_max))
+        st = _U8P(); t, xyz, nrm, rgb = _F32P(), _F32P(), _F32P(), _F32P(); vox = C.POINTER(C.c_int64)(); cnt = RayCounts()
+        self._check(self._fn("cast_rays")(self.ctx, origins.ctypes.data_as(_F32P) if n else None, directions.ctypes.data_as(_F32P) if n else None, C.c_int64(n), C.byref(p),
+                                          C.byref(st), C.byref(t), C.byref(xyz), C.byref(nrm), C.byref(rgb), C.byref(vox), C.byref(cnt)), "cast_rays")
+        return dict(status=_owned(st, (n,), np.uint8), t=_owned(t, (n,), np.float32), xyz=_owned(xyz, (n, 3), np.float32), normal=_owned(nrm, (n, 3), np.float32),
+                    rgb=_owned(rgb, (n, 3), np.float32), voxel=_owned(vox, (n,), np.int64), counts=_counts(cnt))
 
     # -- curvature of the reconstructed surface (include/psgsdf_curvature.h)
     def curvature_voxels(self, lin):

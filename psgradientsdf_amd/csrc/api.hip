@@ -36,7 +36,7 @@ static const char* const kKnobs[] = {
     "PSGSDF_PCG_FUSE_APPLY", "PSGSDF_PCG_WINDOW", "PSGSDF_PCG_SOLVE_ROWS", "PSGSDF_PCG_COL16", "PSGSDF_PCG_ROWS", "PSGSDF_PCG_BLOCKS",
     "PSGSDF_FM_SOLVE", "PSGSDF_FRAME_SOLVE", "PSGSDF_FM_ROWS", "PSGSDF_IMG_COMPACT", "PSGSDF_XCD_MAP", "PSGSDF_XCD_STRIPE",
     "PSGSDF_XR", "PSGSDF_XF", "PSGSDF_XS", "PSGSDF_XH", "PSGSDF_XR_MEM", "PSGSDF_XWAIT_LOG2", "PSGSDF_SPECULATE_MR", "PSGSDF_CU_MASK",
-    "PSGSDF_WAIT_TIMEOUT_S", "PSGSDF_DESTROY_TIMEOUT_S", "PSGSDF_SOLVE_DUMP", "PSGSDF_AO_CUT", "PSGSDF_COMPARE_CHUNK"};
+    "PSGSDF_WAIT_TIMEOUT_S", "PSGSDF_DESTROY_TIMEOUT_S", "PSGSDF_SOLVE_DUMP", "PSGSDF_AO_CUT", "PSGSDF_COMPARE_CHUNK", "PSGSDF_QUERY_CHUNK"};
 static const char* const kDevKnobs[] = {"PSGSDF_PCG_ABLATE", "PSGSDF_FAULT_SOLVE", "PSGSDF_FAULT_HALO", "PSGSDF_MBOX_CHECK"};
 const char* psgsdf_last_error(const psgsdf_ctx* c) { return c ? c->err : "null context"; }
 
@@ -46,8 +46,15 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PSGSDF_ERR_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return PSGSDF_ERR_DEVICE;
+    long long query_chunk = 1ll << 30;
+    if (const char* e = getenv("PSGSDF_QUERY_CHUNK")) {      // a multiple of 64 up to 2^30 (no wavefront may straddle two launches); anything else is refused, never rounded
+        char* end = nullptr;
+        query_chunk = strtoll(e, &end, 10);
+        if (end == e || *end || query_chunk < 64 || query_chunk > (1ll << 30) || query_chunk % 64) return PSGSDF_ERR_ARG;
+    }
     psgsdf_ctx* c = new psgsdf_ctx();
     c->device = device;
+    c->query_chunk = query_chunk;
     if (const char* e = getenv("PSGSDF_PCG_POLL")) c->pcg_poll = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_AO_CUT")) c->ao_cut = atoi(e) != 0;
     if (const char* e = getenv("PSGSDF_COMPARE_CHUNK")) c->compare_chunk = std::min(std::max(atoll(e), 1ll), 1ll << 24);

@@ -277,11 +277,11 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
     char buf[1024];
     snprintf(buf, sizeof(buf), "\"pcg_poll\": %d, \"speculate\": %d, \"speculate_mr\": %d, \"fold_in_next\": %d, \"fuse_albedo\": %d, \"fuse_pcg_init\": %d, \"pcg_persist\": %d, "
              "\"pcg_fuse_apply\": %d, \"fm_solve\": %d, \"fm_solve_led\": %d, \"frame_solve\": \"%s\", \"img_compact\": %d, \"xcd_map\": %d, "
-             "\"xr\": %d, \"xf\": %d, \"xs\": %d, \"xh\": %d, \"xr_mem_kind\": %d, \"xwait_log2\": %d, \"cu_mask\": [%d, %d], \"mbox_check\": %d, \"pcg_ablate\": %d, \"fault_solve\": %d, \"fault_halo\": %lld, \"ao_cut\": %d, \"compare_chunk\": %lld",
+             "\"xr\": %d, \"xf\": %d, \"xs\": %d, \"xh\": %d, \"xr_mem_kind\": %d, \"xwait_log2\": %d, \"cu_mask\": [%d, %d], \"mbox_check\": %d, \"pcg_ablate\": %d, \"fault_solve\": %d, \"fault_halo\": %lld, \"ao_cut\": %d, \"compare_chunk\": %lld, \"query_chunk\": %lld",
              (int)c->pcg_poll, (int)c->speculate, (int)c->speculate_mr, (int)c->fold_in_next, (int)c->fuse_albedo, (int)c->fuse_pcg_init, (int)c->pcg_persist,
              (int)c->pcg_fuse_apply, (int)c->fm_solve, (int)c->fm_solve_led, c->frame_solve == 1 ? "eigen" : "ldlt", (int)c->img_compact, c->xcd_map,
              (int)c->xr_enable, (int)c->xf_enable, (int)c->xs_enable, (int)c->xh_enable, c->xr_mem_kind, (int)lround(log2((double)c->xwait_spins)), c->cu_mask_lo, c->cu_mask_hi,
-             (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut, c->compare_chunk);
+             (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut, c->compare_chunk, c->query_chunk);
     o += buf;
     {   // the LDS window of the single-rank persistent solve: the knob, what this band's partition needs and may hold, and what the last solve ran.
         // "fallback" names why a context with the knob on gathers per thread all the same -- never silently

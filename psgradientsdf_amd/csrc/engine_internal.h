@@ -12,6 +12,7 @@
 //   extract_compare.hip  the comparison with a reference (include/psgsdf_compare.h) and its alignment (include/psgsdf_align.h)
 //   extract_curvature.hip  curvature per voxel, per vertex of the welded mesh and as a map of the bake (include/psgsdf_curvature.h)
 //   extract_fill.hip  unobserved voxels filled from their neighbours, and the welded mesh and components of the filled state (include/psgsdf_fill.h)
+//   extract_query.hip  the field at the caller's points, their projections onto the surface and the caller's rays (include/psgsdf_query.h)
 // Who frees what: every device or pinned allocation has ONE owner (device_own.h).  What lives as long as the context is a DevBuf / PinBuf /
 // DensePlanes member of psgsdf_ctx and goes with `delete c`; what lives for one call is handed out by a DevMem of that call.  A raw pointer in
 // the context points INTO something (an arena, a mapping, the mailbox): its comment says what.
@@ -62,6 +63,8 @@ enum XoSlot {
     XO_BAKE_CURV_MEAN, XO_BAKE_CURV_VALID,                           // psgsdf_bake_lod_curvature (everything else: psgsdf_bake_lod's slots)
     XO_FILL_LIN, XO_FILL_DIST, XO_FILL_GRAD, XO_FILL_RGB, XO_FILL_ROUND,   // psgsdf_fill_voxels
     XO_FILL_VERTEX,                                                  // psgsdf_extract_mesh_filled (everything else: psgsdf_extract_mesh_components' slots)
+    XO_QUERY_STATUS, XO_QUERY_DIST, XO_QUERY_NORMAL, XO_QUERY_RGB, XO_QUERY_WEIGHT, XO_QUERY_VOXEL,   // psgsdf_query_points; psgsdf_cast_rays (its t: _DIST) and ...
+    XO_QUERY_XYZ, XO_QUERY_ITERS, XO_QUERY_MOVED,                    // ... psgsdf_project_points (its residual: _DIST) share them
     XO_COUNT
 };
 }  // namespace psge
@@ -221,6 +224,7 @@ struct psgsdf_ctx {
     double* frame_e_slot = nullptr; unsigned long long frame_e_key = 0;   // slot of mbox, as the device addresses it (and its key), the next per-frame solve writes its sweep's energy sums to
     bool ao_cut = true;                  // PSGSDF_AO_CUT=0: the rays of include/psgsdf_occlusion.h walk on past their radius (what the cut buys: tools/time_mesh.py; the same bits)
     long long compare_chunk = 1ll << 24; // PSGSDF_COMPARE_CHUNK: queries per launch of include/psgsdf_compare.h's search (1 .. 2^24; the same bits)
+    long long query_chunk = 1ll << 30;   // PSGSDF_QUERY_CHUNK: queries per launch of include/psgsdf_query.h's kernels (a multiple of 64 up to 2^30; the same bits)
     long long cmp_pairs[2] = {0, 0}, cmp_queries[2] = {0, 0};   // the last psgsdf_compare_reference: candidate pairs evaluated and queries, per direction (psgsdf_get_tuning "last_compare"; tools/time_compare.py)
     long long aln_evals = 0, aln_iters = 0, aln_pairs[2] = {0, 0}, aln_queries[2] = {0, 0};   // the last psgsdf_align_reference: evaluations, steps, and per direction the queries searched and candidate pairs evaluated over all evaluations (psgsdf_get_tuning "last_align"; tools/time_align.py)
     bool pcg_poll = true;                // PCG stop test by watching the mapped mailbox (PSGSDF_PCG_POLL=0: drain the stream instead)

@@ -26,6 +26,7 @@
 #include "../../include/psgsdf_align.h"
 #include "../../include/psgsdf_curvature.h"
 #include "../../include/psgsdf_fill.h"
+#include "../../include/psgsdf_query.h"
 #include "../../include/psgsdf_relight.h"
 #include "dump_queue.hpp"
 #include "obj_writer.hpp"
@@ -42,6 +43,12 @@ namespace psgsdf_host {
 // both directions, the filter flags applied, the radius of --compare-max, at most K = 30 steps), the comparison runs on the aligned points, and a
 // <name>_align.txt is written next to <name>_compare.txt: the status word, one line per iteration, the final evaluation, the 4x4 transform with %.17g
 struct CompareRef { bool on = false; std::string file; std::vector<float> xyz; std::vector<int32_t> faces; double tau_voxels = 1.0, max_voxels = 8.0; bool align = false; int align_iters = 30; };
+// --query-ply FILE [--query-model cell|trilinear] [--query-project]: next to every <name>_mesh.ply a <name>_query.ply, the vertices of FILE (read by
+// the reader of --compare-ply; coordinates as in <name>_mesh_indexed.ply) with the field there (psgsdf_query_points: float distance nx ny nz red green
+// blue weight, uchar status) or, with --query-project, moved onto the surface (psgsdf_project_points, tolerance 1e-3 voxel, at most 16 moves: the
+// projected positions with float distance -- signed, the length moved -- and residual, uchar iterations and status); the model defaults to trilinear;
+// single process only
+struct QueryRef { bool on = false; std::string file; std::vector<float> xyz; int model = PSGSDF_Q_TRILINEAR; bool project = false; };
 // --relight FILE: the lights of the file (include/psgsdf_relight.h), bias and reach in voxels
 struct RelightSpec { bool on = false; double bias_voxels = 1.0, reach_voxels = 0.0; std::vector<psgsdf_light> lights; };
 
@@ -84,6 +91,7 @@ struct DumpOptions {
     // apply to it) and how many of every vertex's end voxels are filled; -1: off; single process only
     int fill_rounds = -1, fill_sweeps = 4;
     CompareRef compare;
+    QueryRef query;
     RelightSpec relight;
     // voxelPS reads nothing of the refined volume after alternatingOptimize (main_ps.cpp:330-343 ends there): the executable skips the whole-volume download
     // that mirrors the reference's in-place mutation of tSDF_ (a host that goes on using tSDF_ keeps it: the default)
@@ -376,6 +384,52 @@ inline bool device_mesh_compare(psgsdf_ctx* ctx, const std::string& mesh_file) {
     });
     return true;
 }
+// <name>_query.ply: the points of --query-ply with the field there, or projected onto the surface (the columns: ply_io.hpp)
+inline bool device_query(psgsdf_ctx* ctx, const std::string& mesh_file) {
+    PSG_STAGE("dump: field queries (device) + binary PLY");
+    const std::string base = dump_base(mesh_file);
+    const QueryRef& q = dump_options().query;
+    psgsdf_info info{}; psgsdf_get_info(ctx, &info);
+    const int64_t n = (int64_t)(q.xyz.size() / 3);
+    const size_t N = (size_t)n;
+    struct Cloud { std::vector<float> xyz; std::vector<std::vector<float>> f; std::vector<std::vector<uint8_t>> b; std::vector<PlyColumn> columns; std::array<float, 3> origin; float vs; };
+    auto cloud = std::make_shared<Cloud>();
+    cloud->origin = {info.origin[0], info.origin[1], info.origin[2]}; cloud->vs = info.voxel_size;
+    // one float column of an [n][stride] array / one byte column; the float columns go first in the file, in the order they are added
+    std::vector<const char*> fnames, bnames;
+    auto column_f = [&](const char* name, const float* src, size_t stride) {
+        fnames.push_back(name); cloud->f.emplace_back(N);
+        for (size_t i = 0; i < N; ++i) cloud->f.back()[i] = src[i * stride];
+    };
+    auto column_b = [&](const char* name, const uint8_t* src) { bnames.push_back(name); cloud->b.emplace_back(src, src + N); };
+    const char* model = q.model == PSGSDF_Q_CELL ? "cell" : "trilinear";
+    char line[300];
+    if (q.project) {
+        psgsdf_project_params p{}; p.model = q.model; p.max_iters = 16; p.tol = 1e-3 * (double)info.voxel_size;
+        const uint8_t *st = nullptr, *it = nullptr; const float *xyz = nullptr, *res = nullptr, *nrm = nullptr, *moved = nullptr; const int64_t* vox = nullptr; psgsdf_project_counts c{};
+        if (psgsdf_project_points(ctx, q.xyz.data(), n, &p, &st, &xyz, &res, &nrm, &vox, &it, &moved, &c) != 0) return false;
+        if (n > 0) cloud->xyz.assign(xyz, xyz + 3 * N);
+        column_f("distance", moved, 1); column_f("residual", res, 1); column_b("iterations", it); column_b("status", st);
+        snprintf(line, sizeof line, "comment query project model %s points %lld converged %lld left %lld not_converged %lld invalid %lld\n", model, (long long)c.n, (long long)c.n_converged,
+                 (long long)c.n_left, (long long)c.n_not_converged, (long long)c.n_invalid);
+    } else {
+        const uint8_t* st = nullptr; const float *d = nullptr, *nrm = nullptr, *rgb = nullptr, *w = nullptr; const int64_t* vox = nullptr; psgsdf_query_counts c{};
+        if (psgsdf_query_points(ctx, q.xyz.data(), n, q.model, &st, &d, &nrm, &rgb, &w, &vox, &c) != 0) return false;
+        cloud->xyz = q.xyz;
+        static const char* const nn[3] = {"nx", "ny", "nz"}; static const char* const cc[3] = {"red", "green", "blue"};
+        column_f("distance", d, 1);
+        for (int k = 0; k < 3; ++k) column_f(nn[k], nrm + k, 3);
+        for (int k = 0; k < 3; ++k) column_f(cc[k], rgb + k, 3);
+        column_f("weight", w, 1); column_b("status", st);
+        snprintf(line, sizeof line, "comment query points model %s points %lld ok %lld outside %lld unobserved %lld invalid %lld\n", model, (long long)c.n, (long long)c.n_ok, (long long)c.n_outside,
+                 (long long)c.n_unobserved, (long long)c.n_invalid);
+    }
+    for (size_t k = 0; k < fnames.size(); ++k) cloud->columns.push_back(ply_column(fnames[k], cloud->f[k].data()));
+    for (size_t k = 0; k < bnames.size(); ++k) cloud->columns.push_back(ply_column(bnames[k], cloud->b[k].data()));
+    const std::string comment = line;
+    queue_dump("the queries", base, [=] { return write_points_ply(base + "_query.ply", cloud->xyz.data(), N, cloud->origin.data(), cloud->vs, comment, cloud->columns); });
+    return true;
+}
 // every dump that goes with a <name>_mesh.ply, in the order the engine is to be called in (its results are valid until the next extraction); one that
 // queued nothing: `couldn't save <what> <label>`
 inline void device_mesh_extras(psgsdf_ctx* ctx, const std::string& mesh_file, const std::string& label) {
@@ -383,7 +437,7 @@ inline void device_mesh_extras(psgsdf_ctx* ctx, const std::string& mesh_file, co
     const struct { bool on; bool (*dump)(psgsdf_ctx*, const std::string&); const char* what; } extras[] = {
         {o.indexed_mesh, device_mesh_indexed, "the indexed mesh"}, {o.clean_mesh, device_mesh_clean, "the cleaned mesh"}, {o.lod_voxels > 0, device_mesh_lod, "the level-of-detail mesh"},
         {o.fit, device_mesh_fit, "the mesh with its fit"}, {o.curvature, device_mesh_curvature, "the mesh with its curvature"}, {o.fill_rounds >= 0, device_mesh_filled, "the filled mesh"},
-        {o.compare.on, device_mesh_compare, "the comparison"}};
+        {o.compare.on, device_mesh_compare, "the comparison"}, {o.query.on, device_query, "the queries"}};
     for (const auto& e : extras) if (e.on && !e.dump(ctx, mesh_file)) std::cout << "couldn't save " << e.what << " " << label << std::endl;
 }
 // the reference's own dumps from the device: <name>_mesh.ply (MarchingCubes::savePly's text), the point clouds, the SDF block

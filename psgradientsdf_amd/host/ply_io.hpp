@@ -98,6 +98,24 @@ inline bool write_mesh_indexed_ply(const std::string& file, const MeshView& m, c
 //     boundary edges of the kept components without and with the filling
 //   `--compare-ply` (include/psgsdf_compare.h): float distance (inf: no match within max_dist), char side (-1 inside, +1 outside, 0 on the reference, a
 //     cloud, or no match); the line is the caller's
+//   `--query-ply` (include/psgsdf_query.h; write_points_ply below, a cloud: no normals or colours of its own, no faces): float distance nx ny nz red
+//     green blue weight and uchar status (the field at the points), or with --query-project float distance residual, uchar iterations status (the
+//     projected points); the line names the model and holds the call's counts
+// A cloud as a binary little-endian PLY: x y z (float) and one value of every column per vertex; the comment line of the welded mesh's writer first.
+inline bool write_points_ply(const std::string& file, const float* xyz, size_t n, const float origin[3], float vs, const std::string& comments, const std::vector<PlyColumn>& columns) {
+    char c[160];
+    snprintf(c, sizeof c, "comment grid origin %.9g %.9g %.9g voxel size %.9g\n", (double)origin[0], (double)origin[1], (double)origin[2], (double)vs);
+    std::string h = std::string("ply\nformat binary_little_endian 1.0\n") + c + comments + "element vertex " + std::to_string(n) + "\nproperty float x\nproperty float y\nproperty float z\n";
+    size_t rec = 12;
+    for (const PlyColumn& k : columns) { h += std::string("property ") + k.type + " " + k.name + "\n"; rec += k.bytes; }
+    h += "end_header\n";
+    std::string b(n * rec, '\0'); char* p = &b[0];
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(p, xyz + 3 * i, 12); p += 12;
+        for (const PlyColumn& k : columns) { memcpy(p, (const char*)k.data + i * k.bytes, k.bytes); p += k.bytes; }
+    }
+    return OutFile(file).put(h).put(b).close();
+}
 inline std::string mesh_fit_comment(const float* rms, const int32_t* n_obs, size_t nv) {
     double q = 0.0; long long n = 0;
     for (size_t i = 0; i < nv; ++i) { q += (double)n_obs[i] * ((double)rms[i] * (double)rms[i]); n += n_obs[i]; }

@@ -332,6 +332,7 @@ int main(int argc, char* argv[]) {
     bool fill_flag = false, fill_ok = true, fillk_flag = false, fillk_ok = true;   // --mesh-fill R given / R is a whole number in 0 .. 255; --mesh-fill-sweeps K given / K is a whole number in 0 .. 4096
     std::string cmp_file, cmp_bad;            // --compare-ply FILE given / the --compare-* flag whose number is bad
     bool cmp_tau_flag = false, cmp_max_flag = false, cmp_iters_flag = false, cmp_bad_iters = false;
+    std::string query_file, query_model = "trilinear"; bool query_model_flag = false;   // --query-ply FILE given / --query-model M given
     std::string relight_file;                 // --relight FILE: every keyframe under the lights of FILE (relight/*.png, relight_report.txt; include/psgsdf_relight.h)
     bool render_keyframes = false;            // --render-keyframes: re-render every keyframe from the final state (render/*.png, render_report.txt)
     DumpOptions& opt = dump_options();      // (every dump flag is documented at its member, device_dumps.hpp)
@@ -357,6 +358,9 @@ int main(int argc, char* argv[]) {
             char* end = nullptr; const double v = strtod(argv[++i], &end);
             if (end == argv[i] || *end || !std::isfinite(v) || !(v > 0) || v > 64) cmp_bad = a;
             (a == "--compare-tau" ? opt.compare.tau_voxels : opt.compare.max_voxels) = v; (a == "--compare-tau" ? cmp_tau_flag : cmp_max_flag) = true; }
+        else if (a == "--query-ply" && i + 1 < argc) query_file = argv[++i];
+        else if (a == "--query-model" && i + 1 < argc) { query_model = argv[++i]; query_model_flag = true; }
+        else if (a == "--query-project") opt.query.project = true;
         else if (a == "--compare-align") opt.compare.align = true;
         else if (a == "--compare-align-iters" && i + 1 < argc) { char* end = nullptr; const long v = strtol(argv[++i], &end, 10); if (end == argv[i] || *end || v < 0 || v > 64) cmp_bad_iters = true; opt.compare.align_iters = (int)v; cmp_iters_flag = true; }
         else if (a == "--frame-solver" && i + 1 < argc) { setenv("PSGSDF_FRAME_SOLVE", argv[++i], 1); std::cout << "frame solver: " << argv[i] << std::endl; }      // eigen = the reference's own solver of the light / pose blocks (include/psgsdf.h psgsdf_set_frame_solver); default ldlt.  The ranks of --gpus N inherit the environment.
@@ -400,6 +404,15 @@ int main(int argc, char* argv[]) {
         std::string why;
         if (!read_reference_ply(cmp_file, opt.compare.xyz, opt.compare.faces, why)) { std::cerr << "--compare-ply: " << why << std::endl; return 1; }
         opt.compare.file = cmp_file; opt.compare.on = true;
+    }
+    if (query_model_flag && query_file.empty()) { std::cerr << "--query-model needs --query-ply FILE: the points to ask the field at" << std::endl; return 1; }
+    if (opt.query.project && query_file.empty()) { std::cerr << "--query-project needs --query-ply FILE: the points to project" << std::endl; return 1; }
+    if (!query_file.empty()) {
+        if (query_model != "cell" && query_model != "trilinear") { std::cerr << "--query-model: cell or trilinear, not " << query_model << std::endl; return 1; }
+        if (want_ranks > 1 || multi_rank()) { std::cerr << "--query-ply needs a single process: a slab holds only its own planes of the volume (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
+        std::string why; std::vector<int32_t> faces_unused;
+        if (!read_reference_ply(query_file, opt.query.xyz, faces_unused, why)) { std::cerr << "--query-ply: " << why << std::endl; return 1; }
+        opt.query.file = query_file; opt.query.model = query_model == "cell" ? PSGSDF_Q_CELL : PSGSDF_Q_TRILINEAR; opt.query.on = true;
     }
     if (!relight_file.empty()) {
         if (want_ranks > 1 || multi_rank()) { std::cerr << "--relight needs a single process: a slab holds only its own planes of the volume the shadow rays cross (--gpus " << std::max(want_ranks, rank_info().n) << ")" << std::endl; return 1; }
