@@ -416,9 +416,11 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* ctx, int64_t out[8]);
 
 /* ---- tuning knobs ------------------------------------------------------------------------- */
 
-/* The engine reads the following environment variables when a context is created (a few, marked *, when they are used).  All of them only choose
- * between equivalent execution strategies -- results agree to rounding, most bit for bit (tests/test_knobs_gpu.py) -- and none is needed in
- * normal operation.  psgsdf_get_tuning reports what was set and what it resolved to.
+/* The engine honours the following environment variables; csrc/knobs.h holds them in one table, and a test keeps this list and that table equal.
+ * A variable without a mark is parsed ONCE, when a context is created: changing it afterwards does nothing to that context.  A variable marked *
+ * is read every time it is used (the table's at_use), so a change reaches a live context at its next launch, solve, wait or call.  All of them only
+ * choose between equivalent execution strategies -- results agree to rounding, most bit for bit (tests/test_knobs_gpu.py) -- and none is needed in
+ * normal operation.  psgsdf_get_tuning reports what was set when the context was created (marked or not) and what the unmarked ones resolved to.
  *   PSGSDF_PCG_POLL, PSGSDF_SPECULATE, PSGSDF_SPECULATE_MR, PSGSDF_FOLD_IN_NEXT, PSGSDF_FUSE_ALBEDO, PSGSDF_FUSE_PCG_INIT        (0 / 1) host-side scheduling
  *   PSGSDF_PCG_PERSIST (0: the per-pass kernels with the classic float recurrences instead of the persistent pipelined solve), PSGSDF_PCG_WINDOW (0: the single-rank persistent solve gathers its neighbour values per thread instead of reading them from an LDS window; the same bits;
  *   "effective.solve_window" says whether a band's windows fit and what the last solve ran), PSGSDF_PCG_SOLVE_ROWS (rows per workgroup of the persistent solve on one rank; default: as many workgroups as CUs), PSGSDF_PCG_FUSE_APPLY,
@@ -428,7 +430,10 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* ctx, int64_t out[8]);
  *   PSGSDF_AREG_DEVICE (0: the `reg albedo` CG driven by the host, two read-backs per iteration)                                   regularised albedo solve
  *   PSGSDF_XR, PSGSDF_XF, PSGSDF_XS, PSGSDF_XH (0: that exchange through the communicator instead of IPC-mapped memory), PSGSDF_XR_MEM* (fine | uncached |
  *   coarse), PSGSDF_XWAIT_LOG2 (log2 of the polls an in-kernel wait for another rank may take), PSGSDF_CU_MASK (lo:hi)              multi-rank
- *   PSGSDF_WAIT_TIMEOUT_S*, PSGSDF_DESTROY_TIMEOUT_S*, PSGSDF_SOLVE_DUMP*                                                           host waits / diagnostics
+ *   PSGSDF_WAIT_TIMEOUT_S* (seconds a host wait for something a kernel publishes may take before the call fails; > 0, default 120; evaluated once
+ *   per process, at the first such wait), PSGSDF_DESTROY_TIMEOUT_S* (seconds psgsdf_destroy waits for the peers to close their mappings, default 15),
+ *   PSGSDF_SOCKET_TIMEOUT_S* (send / receive timeout of psgsdf_comm_init_sockets' sockets in seconds, default 120),
+ *   PSGSDF_SOLVE_DUMP* (a file psgsdf_debug_time_pcg_solve writes its per-workgroup times to)                                       host waits / diagnostics
  *   PSGSDF_AO_CUT (0: the rays of psgsdf_occlusion.h walk on past their radius; the same bits)                                     ambient occlusion
  *   PSGSDF_COMPARE_CHUNK (queries per launch of psgsdf_compare.h's search, 1 .. 2^24, default 2^24; the same bits)                  comparison with a reference
  *   PSGSDF_QUERY_CHUNK (queries per launch of psgsdf_query.h's kernels, a multiple of 64 up to 2^30, default 2^30; anything else makes

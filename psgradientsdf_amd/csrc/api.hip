@@ -1,4 +1,5 @@
 // api.hip -- the C ABI of include/psgsdf.h: context, volume, keyframes, init, energies, steps, loops, downloads.
+#define PSGSDF_KNOB_TABLE      // this unit holds the table of knobs.h: the Makefile compiles it with and without -DPSGSDF_DEV
 #include "engine_internal.h"
 
 using namespace psge;
@@ -18,6 +19,7 @@ int host_stage(psgsdf_ctx* c, size_t bytes, void** p) {
     *p = c->pin_stage;
     return 0;
 }
+std::string knobs_effective_json(const psgsdf_ctx* c) { return knobs_effective(c->knob); }
 }  // namespace psge
 
 extern "C" {
@@ -28,16 +30,6 @@ const char* psgsdf_version(void) { return "psgsdf-hip gfx950 r5 dev (fault-injec
 const char* psgsdf_version(void) { return "psgsdf-hip gfx950 r5"; }
 #endif
 
-// Every environment variable the engine reads (include/psgsdf.h lists them with their meaning).  The values are snapshotted when a context is created;
-// psgsdf_get_tuning reports the snapshot and what it resolved to.  kDevKnobs exist only in the development build: they inject faults or make results
-// WRONG on purpose and are compiled out of libpsgsdf.so.
-static const char* const kKnobs[] = {
-    "PSGSDF_PCG_POLL", "PSGSDF_SPECULATE", "PSGSDF_FOLD_IN_NEXT", "PSGSDF_FUSE_ALBEDO", "PSGSDF_FUSE_PCG_INIT", "PSGSDF_PCG_PERSIST",
-    "PSGSDF_PCG_FUSE_APPLY", "PSGSDF_PCG_WINDOW", "PSGSDF_PCG_SOLVE_ROWS", "PSGSDF_PCG_COL16", "PSGSDF_PCG_ROWS", "PSGSDF_PCG_BLOCKS",
-    "PSGSDF_FM_SOLVE", "PSGSDF_FRAME_SOLVE", "PSGSDF_FM_ROWS", "PSGSDF_IMG_COMPACT", "PSGSDF_XCD_MAP", "PSGSDF_XCD_STRIPE",
-    "PSGSDF_XR", "PSGSDF_XF", "PSGSDF_XS", "PSGSDF_XH", "PSGSDF_XR_MEM", "PSGSDF_XWAIT_LOG2", "PSGSDF_SPECULATE_MR", "PSGSDF_CU_MASK",
-    "PSGSDF_WAIT_TIMEOUT_S", "PSGSDF_DESTROY_TIMEOUT_S", "PSGSDF_SOLVE_DUMP", "PSGSDF_AO_CUT", "PSGSDF_COMPARE_CHUNK", "PSGSDF_QUERY_CHUNK"};
-static const char* const kDevKnobs[] = {"PSGSDF_PCG_ABLATE", "PSGSDF_FAULT_SOLVE", "PSGSDF_FAULT_HALO", "PSGSDF_MBOX_CHECK"};
 const char* psgsdf_last_error(const psgsdf_ctx* c) { return c ? c->err : "null context"; }
 
 int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_settings* settings, int device, psgsdf_ctx** out) {
@@ -46,52 +38,11 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PSGSDF_ERR_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return PSGSDF_ERR_DEVICE;
-    long long query_chunk = 1ll << 30;
-    if (const char* e = getenv("PSGSDF_QUERY_CHUNK")) {      // a multiple of 64 up to 2^30 (no wavefront may straddle two launches); anything else is refused, never rounded
-        char* end = nullptr;
-        query_chunk = strtoll(e, &end, 10);
-        if (end == e || *end || query_chunk < 64 || query_chunk > (1ll << 30) || query_chunk % 64) return PSGSDF_ERR_ARG;
-    }
+    Knobs knob; KnobList env_set, env_ignored;
+    if (!knobs_parse(process_env, knob, env_set, env_ignored)) return PSGSDF_ERR_ARG;      // (a refused value leaves no context behind)
     psgsdf_ctx* c = new psgsdf_ctx();
     c->device = device;
-    c->query_chunk = query_chunk;
-    if (const char* e = getenv("PSGSDF_PCG_POLL")) c->pcg_poll = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_AO_CUT")) c->ao_cut = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_COMPARE_CHUNK")) c->compare_chunk = std::min(std::max(atoll(e), 1ll), 1ll << 24);
-    if (const char* e = getenv("PSGSDF_SPECULATE")) c->speculate = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_FOLD_IN_NEXT")) c->fold_in_next = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_FUSE_ALBEDO")) c->fuse_albedo = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_FUSE_PCG_INIT")) c->fuse_pcg_init = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_PCG_PERSIST")) c->pcg_persist = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_PCG_FUSE_APPLY")) c->pcg_fuse_apply = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_AREG_DEVICE")) c->areg_device = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_PCG_WINDOW")) c->pcg_window = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_PCG_SOLVE_ROWS")) { const int v = atoi(e); if (v > 0) c->pcg_solve_rows = v; }
-    if (const char* e = getenv("PSGSDF_FM_SOLVE")) { c->fm_solve = atoi(e) != 0; c->fm_solve_led = atoi(e) == 1; }
-    if (const char* e = getenv("PSGSDF_FRAME_SOLVE")) c->frame_solve = (!strcmp(e, "eigen") || !strcmp(e, "1")) ? 1 : 0;
-    if (const char* e = getenv("PSGSDF_XR")) c->xr_enable = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_XF")) c->xf_enable = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_XS")) c->xs_enable = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_XH")) c->xh_enable = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_XWAIT_LOG2")) { const int l = atoi(e); if (l >= 8 && l <= 30) c->xwait_spins = 1 << l; }
-    if (const char* e = getenv("PSGSDF_IMG_COMPACT")) c->img_compact = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_SPECULATE_MR")) c->speculate_mr = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_XCD_MAP")) c->xcd_map = atoi(e);
-    if (const char* e = getenv("PSGSDF_XCD_STRIPE")) c->xcd_map = (c->xcd_map & 255) | (atoi(e) << 8);
-#ifdef PSGSDF_DEV      // fault injection / ablation / the round-2 race: development build only (libpsgsdf_dev.so)
-    if (const char* e = getenv("PSGSDF_PCG_ABLATE")) c->pcg_ablate = atoi(e) & 5;
-    if (const char* e = getenv("PSGSDF_MBOX_CHECK")) c->mbox_check = atoi(e) != 0;
-    if (const char* e = getenv("PSGSDF_FAULT_SOLVE")) c->fault_solve = atoi(e);
-    if (const char* e = getenv("PSGSDF_FAULT_HALO")) c->fault_halo = atoll(e);
-#endif
-    for (const char* k : kKnobs) if (const char* e = getenv(k)) c->tuning_env.emplace_back(k, e);
-    for (const char* k : kDevKnobs) if (const char* e = getenv(k)) {
-#ifdef PSGSDF_DEV
-        c->tuning_env.emplace_back(k, e);
-#else
-        c->tuning_ignored.emplace_back(k, e);      // (set, but this build does not know it: reported, never silently honoured)
-#endif
-    }
+    c->knob = knob; c->tuning_env = std::move(env_set); c->tuning_ignored = std::move(env_ignored);
     if (hipDeviceGetAttribute(&c->num_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) c->num_cu = 0;
     c->set = *settings; c->reg_n = settings->reg_weight_n; c->reg_l = settings->reg_weight_l; c->reg_r = settings->reg_weight_rho;
     GridP& g = c->grid;
@@ -103,13 +54,13 @@ int psgsdf_create(const psgsdf_grid_desc* grid, const float K[9], const psgsdf_s
     for (int a = 0; a < 3; ++a) g.origin[a] = c->shift[a] - (float)(0.5 * (double)g.vs) * (float)g.dim[a];   // VoxelGrid.h:130
     c->cam.fx = K[0]; c->cam.fy = K[4]; c->cam.cx = K[2]; c->cam.cy = K[5];
     bool stream_ok;
-    if (const char* e = getenv("PSGSDF_CU_MASK")) {      // "lo:hi": the context's stream runs on CUs [lo, hi) only -- two ranks sharing ONE GPU with half the CUs each (tests of the cross-rank persistent solve)
-        int lo = 0, hi = 0;
-        if (sscanf(e, "%d:%d", &lo, &hi) != 2 || lo < 0 || hi <= lo || hi > c->num_cu) { delete c; return PSGSDF_ERR_ARG; }
+    if (c->knob.cu_mask_hi > 0) {      // PSGSDF_CU_MASK=lo:hi: the context's stream runs on CUs [lo, hi) only -- two ranks sharing ONE GPU with half the CUs each (tests of the cross-rank persistent solve)
+        const int lo = c->knob.cu_mask_lo, hi = c->knob.cu_mask_hi;
+        if (hi > c->num_cu) { delete c; return PSGSDF_ERR_ARG; }
         std::vector<uint32_t> mask((size_t)(c->num_cu + 31) / 32, 0u);
         for (int i = lo; i < hi; ++i) mask[i / 32] |= 1u << (i % 32);
         stream_ok = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data()) == hipSuccess;
-        c->cu_mask_lo = lo; c->cu_mask_hi = hi; c->num_cu = hi - lo;
+        c->num_cu = hi - lo;
     } else stream_ok = hipStreamCreate(&c->stream) == hipSuccess;
     bool ok = stream_ok
         && c->pcg_sc.alloc(16 + 8 * (size_t)kPcgMaxBlocks) == hipSuccess   // fs[0..1] + stage stamps of the timing hook
@@ -133,7 +84,7 @@ void psgsdf_destroy(psgsdf_ctx* c) {
     // multi-rank: this rank closes its mappings of the others' record planes / mailbox regions (telling their owners) and frees what IT exported
     // only once every rank that mapped it has reported the same -- bounded, and no collective: a rank that failed, left early or destroys its
     // contexts in another order cannot hang this call.  If a peer never reports, the exported allocations are leaked instead of freed.
-    double qt = 15.0; if (const char* e = getenv("PSGSDF_DESTROY_TIMEOUT_S")) qt = atof(e);
+    const double qt = knob_destroy_timeout_s();
     if (xr_quiesce(c, qt)) {
         c->leak_exported = true;
         fprintf(stderr, "psgsdf: rank %d: a peer did not close its mappings of this rank's exchange memory within %.0f s (failed or still running?): that memory is leaked, not freed\n", c->rank, qt);
@@ -403,7 +354,7 @@ static int set_keyframes_impl(psgsdf_ctx* c, int n_frames, const int32_t* frame_
         // Keyframes that came out of 8-bit files (the reference's loader: imread + convertTo(CV_32FC3, 1.0f / 255.0f)) are kept as RGBA8 words: the
         // samplers give back the SAME floats (device_common.h unpack_rgb8), with two tap loads per observation instead of four and a third of the bytes.
         c->img_compacted = false;
-        if (c->img_compact && npix < ((size_t)1 << 30) && (size_t)n_frames * height < ((size_t)1 << 24)) {
+        if (c->knob.img_compact && npix < ((size_t)1 << 30) && (size_t)n_frames * height < ((size_t)1 << 24)) {
             const float scale = 1.0f / 255.0f;
             // a sample first (every 61st pixel, nothing written: data that is not 8-bit at all is recognised in microseconds), the full pass only behind a clean sample
             int bad = 1, prc;

@@ -101,7 +101,7 @@ int psgsdf_debug_time_pcg_solve(psgsdf_ctx* c, int passes, int reps, double* ms_
     hipEventDestroy(e0); hipEventDestroy(e1);
     *ms_per_launch = (double)total / reps;
     if (stamps) for (int i = 0; i < 16; ++i) stamps[i] = c->mbox[8 + i];      // pass 8 of the last launch: 7 stage stamps of the first and of the last workgroup (100 MHz ticks)
-    if (const char* dump = getenv("PSGSDF_SOLVE_DUMP")) {   // per-workgroup publish / gather-done / sums-seen times (tools/pcg_solve_time.py)
+    if (const char* dump = knob_solve_dump()) {   // per-workgroup publish / gather-done / sums-seen times (tools/pcg_solve_time.py)
         std::vector<double> h(8 * 256);      // columns: workgroup, publish(8), sums seen(9), =, XCC, gathers done(9), publish(9), neighbour tags seen(9), prefetch valid(9)
         HIPCHK(c, hipMemcpy(h.data(), c->pcg_sc + 16, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
         if (FILE* f = fopen(dump, "w")) { for (int i = 0; i < G; ++i) fprintf(f, "%d %.0f %.0f %.0f %.0f %.0f %.0f %.0f %.0f\n", i, h[i], h[256 + i], h[512 + i], h[768 + i], h[1024 + i], h[1280 + i], h[1536 + i], h[1792 + i]); fclose(f); }
@@ -176,7 +176,7 @@ int psgsdf_debug_rare_rows(psgsdf_ctx* c, int64_t* rows, int64_t* waves) {
 int psgsdf_set_frame_solver(psgsdf_ctx* c, int mode) {
     if (!c) return PSGSDF_ERR_ARG;
     if (mode != 0 && mode != 1) return fail(c, PSGSDF_ERR_ARG, "frame solver mode %d (0 = LDL^T per frame, 1 = the reference's global float Jacobi-PCG)", mode);
-    c->frame_solve = mode;
+    c->knob.frame_solve = mode;
     return PSGSDF_OK;
 }
 int psgsdf_get_frame_solver_stats(psgsdf_ctx* c, int block, int32_t* iterations, double* error, int32_t* converged, int32_t* applied) {
@@ -262,7 +262,7 @@ int psgsdf_debug_sync_stats(psgsdf_ctx* c, int64_t out[8]) {
 }
 
 // Which tuning knobs are in force on this context: one JSON object -- "build", "env" (every supported PSGSDF_* variable that was set when the context
-// was created, verbatim), "ignored_dev_only" (fault-injection / ablation variables that were set but are compiled out of this build) and "effective"
+// was created, verbatim; the ones knobs.h marks at_use are read again whenever they are used), "ignored_dev_only" (fault-injection / ablation variables that were set but are compiled out of this build) and "effective"
 // (what the switches resolved to, defaults included).  Returns the length the text needs (excluding the terminator); writes at most cap - 1 characters.
 int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
     if (!c) return PSGSDF_ERR_ARG;
@@ -274,24 +274,19 @@ int psgsdf_get_tuning(psgsdf_ctx* c, char* json, size_t cap) {
     o += "}, \"ignored_dev_only\": {"; first = true;
     for (auto& kv : c->tuning_ignored) { o += (first ? "\"" : ", \"") + kv.first + "\": \"" + esc(kv.second) + "\""; first = false; }
     o += "}, \"effective\": {";
+    o += knobs_effective_json(c);      // (the table of knobs.h, which api.hip holds)
     char buf[1024];
-    snprintf(buf, sizeof(buf), "\"pcg_poll\": %d, \"speculate\": %d, \"speculate_mr\": %d, \"fold_in_next\": %d, \"fuse_albedo\": %d, \"fuse_pcg_init\": %d, \"pcg_persist\": %d, "
-             "\"pcg_fuse_apply\": %d, \"fm_solve\": %d, \"fm_solve_led\": %d, \"frame_solve\": \"%s\", \"img_compact\": %d, \"xcd_map\": %d, "
-             "\"xr\": %d, \"xf\": %d, \"xs\": %d, \"xh\": %d, \"xr_mem_kind\": %d, \"xwait_log2\": %d, \"cu_mask\": [%d, %d], \"mbox_check\": %d, \"pcg_ablate\": %d, \"fault_solve\": %d, \"fault_halo\": %lld, \"ao_cut\": %d, \"compare_chunk\": %lld, \"query_chunk\": %lld",
-             (int)c->pcg_poll, (int)c->speculate, (int)c->speculate_mr, (int)c->fold_in_next, (int)c->fuse_albedo, (int)c->fuse_pcg_init, (int)c->pcg_persist,
-             (int)c->pcg_fuse_apply, (int)c->fm_solve, (int)c->fm_solve_led, c->frame_solve == 1 ? "eigen" : "ldlt", (int)c->img_compact, c->xcd_map,
-             (int)c->xr_enable, (int)c->xf_enable, (int)c->xs_enable, (int)c->xh_enable, c->xr_mem_kind, (int)lround(log2((double)c->xwait_spins)), c->cu_mask_lo, c->cu_mask_hi,
-             (int)c->mbox_check, c->pcg_ablate, c->fault_solve, c->fault_halo, (int)c->ao_cut, c->compare_chunk, c->query_chunk);
+    snprintf(buf, sizeof(buf), ", \"xr_mem_kind\": %d", c->xr_mem_kind);
     o += buf;
     {   // the LDS window of the single-rank persistent solve: the knob, what this band's partition needs and may hold, and what the last solve ran.
         // "fallback" names why a context with the knob on gathers per thread all the same -- never silently
         int Gs = 0, Rs = 0;
         const bool shape = cgf_solve_shape(c, &Gs, &Rs);
         const int budget = (shape && c->n_ranks <= 1) ? cgf_solve_window_budget(Rs) : 0;
-        const char* why = !c->pcg_window ? "" : c->n_ranks > 1 ? "multi-rank" : c->pcg_ablate ? "timing ablation" : !c->inited ? "no band yet"
+        const char* why = !c->knob.pcg_window ? "" : c->n_ranks > 1 ? "multi-rank" : c->knob.pcg_ablate ? "timing ablation" : !c->inited ? "no band yet"
                           : !shape ? "no persistent solve on this band" : (c->win_G != Gs || c->win_rows != Rs) ? "no table for this partition" : c->win_max > budget ? "window does not fit" : "";
-        snprintf(buf, sizeof(buf), ", \"pcg_window\": %d, \"pcg_solve_rows\": %d, \"solve_window\": {\"workgroups\": %d, \"rows_per_workgroup\": %d, \"window_doubles\": %d, \"budget_doubles\": %d, \"fits\": %d, \"fallback\": \"%s\", \"last_solve_windowed\": %d}",
-                 (int)c->pcg_window, c->pcg_solve_rows, shape ? Gs : 0, shape ? Rs : 0, c->win_max, budget, (int)(c->pcg_window && !*why), why, c->last_solve_windowed);
+        snprintf(buf, sizeof(buf), ", \"solve_window\": {\"workgroups\": %d, \"rows_per_workgroup\": %d, \"window_doubles\": %d, \"budget_doubles\": %d, \"fits\": %d, \"fallback\": \"%s\", \"last_solve_windowed\": %d}",
+                 shape ? Gs : 0, shape ? Rs : 0, c->win_max, budget, (int)(c->knob.pcg_window && !*why), why, c->last_solve_windowed);
         o += buf;
     }
     o += "}";

@@ -95,7 +95,7 @@ int psgsdf_comm_init_sockets(psgsdf_ctx* c, const int* peer_fd, int rank, int n_
     for (int r = 0; r < n_ranks; ++r) {
         if (r == rank) continue;
         if (sc->fd[r] < 0) return fail(c, PSGSDF_ERR_ARG, "comm_init_sockets: no socket for rank %d", r);
-        double t = 120.0; if (const char* e = getenv("PSGSDF_SOCKET_TIMEOUT_S")) t = atof(e);      // a peer that died must end the run, not hang it
+        const double t = knob_socket_timeout_s();      // a peer that died must end the run, not hang it
         struct timeval tv; tv.tv_sec = (long)t; tv.tv_usec = (long)((t - (double)tv.tv_sec) * 1e6);
         if (setsockopt(sc->fd[r], SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof tv) != 0 || setsockopt(sc->fd[r], SOL_SOCKET, SO_SNDTIMEO, &tv, sizeof tv) != 0)
             return fail(c, PSGSDF_ERR_COMM, "comm_init_sockets: the socket to rank %d takes no timeout (%s): a lost peer would hang this rank", r, strerror(errno));

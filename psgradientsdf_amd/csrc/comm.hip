@@ -173,7 +173,7 @@ int comm_halo(psgsdf_ctx* c, void* base, int planes, int width) {
         HaloArgs push{}, pull{};
         push.planes = pull.planes = planes; push.width = pull.width = width; push.plane_words = pull.plane_words = (long long)pw; push.tag = pull.tag = (double)ep;
         pull.abort_flag = push.abort_flag = c->xr + kXrLate + 2;
-        pull.host_late = push.host_late = c->mbox_dev ? c->mbox_dev + c->mbox_n + 1 : nullptr; pull.spin_max = push.spin_max = c->xwait_spins;
+        pull.host_late = push.host_late = c->mbox_dev ? c->mbox_dev + c->mbox_n + 1 : nullptr; pull.spin_max = push.spin_max = c->knob.xwait_spins;
         unsigned* arr = (unsigned*)base;
         for (int sd = 0; sd < 2; ++sd) {
             const int nb = sd == 0 ? c->rank - 1 : c->rank + 1;
@@ -192,7 +192,7 @@ int comm_halo(psgsdf_ctx* c, void* base, int planes, int width) {
             }
             pull.s[sd].flag = c->xr + c->hx_flag_off + par * 2 + sd;
         }
-        if (!(c->fault_halo > 0 && ep == c->fault_halo))      // PSGSDF_FAULT_HALO=n: this rank's n-th exchange pushes nothing (the neighbours' bounded waits: tests)
+        if (!(c->knob.fault_halo > 0 && ep == c->knob.fault_halo))      // PSGSDF_FAULT_HALO=n: this rank's n-th exchange pushes nothing (the neighbours' bounded waits: tests)
             hipLaunchKernelGGL(k_halo_push, dim3(2), dim3(1024), 0, c->stream, push);
         hipLaunchKernelGGL(k_halo_pull, dim3(2), dim3(1024), 0, c->stream, pull);
         c->n_halo_pushes++;
@@ -349,8 +349,7 @@ int xr_probe(psgsdf_ctx* c) {
     const int R = c->n_ranks, me = c->rank;
     if (c->xr_mem_kind >= 0 || R <= 1 || !c->comm) return 0;
     c->xr_mem_kind = 0;
-    int want = 0;                    // PSGSDF_XR_MEM=fine|uncached|coarse pins the kind (coarse: plain hipMalloc, round 3's allocation -- for comparison only)
-    if (const char* e = getenv("PSGSDF_XR_MEM")) want = !strcmp(e, "fine") ? 1 : !strcmp(e, "uncached") ? 2 : !strcmp(e, "coarse") ? 3 : 0;
+    const int want = knob_xr_mem();  // PSGSDF_XR_MEM=fine|uncached|coarse pins the kind (coarse: plain hipMalloc, round 3's allocation -- for comparison only)
     constexpr int kSlice = 64 + 64 + 2;
     for (int kind = 1; kind <= 2; ++kind) {
         if (want == 1 || want == 2) { if (kind != want) continue; }
@@ -358,7 +357,7 @@ int xr_probe(psgsdf_ctx* c) {
         hipIpcMemHandle_t hF{}, hP{};
         // the kind under test: flags always uncached, the payload fine-grained (kind 1) or uncached (kind 2) -- or plain memory if PSGSDF_XR_MEM=coarse asks for it
         auto probe_mem = [&](size_t bytes, int k) { void* q = nullptr; const hipError_t e = k == 3 ? hipMalloc(&q, bytes) : hipExtMallocWithFlags(&q, bytes, k == 1 ? hipDeviceMallocFinegrained : hipDeviceMallocUncached); return e == hipSuccess ? q : nullptr; };
-        bool ok = c->xr_enable;
+        bool ok = c->knob.xr_enable;
         if (ok) { F.adopt(probe_mem(sizeof(double) * kProbeFlagDoubles, 2)); ok = F != nullptr; }
         if (ok) { P.adopt(probe_mem(sizeof(float4) * kProbeRecs, want == 3 ? 3 : kind)); ok = P != nullptr; }
         ok = ok && out.alloc(4) == hipSuccess
@@ -406,7 +405,7 @@ int xr_probe(psgsdf_ctx* c) {
                                    kind == 1 ? "fine-grained" : "uncached", (long long)res[0], (long long)res[1], R);
         if (!ok) break;      // (no IPC between these ranks at all: another kind will not help)
     }
-    if (c->xr_mem_kind == 0 && me == 0 && c->xr_enable) fprintf(stderr, "psgsdf: no memory kind carried the in-kernel hand-offs between the %d ranks: the distance solve uses the per-pass kernels + one all-reduce per pass\n", R);
+    if (c->xr_mem_kind == 0 && me == 0 && c->knob.xr_enable) fprintf(stderr, "psgsdf: no memory kind carried the in-kernel hand-offs between the %d ranks: the distance solve uses the per-pass kernels + one all-reduce per pass\n", R);
     return 0;
 }
 
@@ -470,7 +469,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     hipIpcMemHandle_t hx{}, hb{}, hh{};
     c->hx_ready = false; c->hx_peer[0] = c->hx_peer[1] = nullptr;
     int Gs, Rs;
-    bool ok = c->xr_enable && c->pcg_persist && c->xr_mem_kind > 0 && c->rec_mem;
+    bool ok = c->knob.xr_enable && c->knob.pcg_persist && c->xr_mem_kind > 0 && c->rec_mem;
     // the region: the solve's fixed words + the frame rows' exchange area (engine.h XfTable) for this many ranks and keyframes.  (Every peer closed
     // its mapping of the old region in xr_quiesce at the top of build_band: it may be replaced here.)
     const size_t frows = (size_t)2 * R * std::max(c->F, 1);
@@ -478,7 +477,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     // halo staging: what the two neighbours push of their cut-side rows (comm_halo): [2 parities][lower side: need_lo rows | upper side: need_hi rows] x kHxWords words
     const size_t hx_par = sizeof(unsigned) * kHxWords * ((size_t)c->need[0] + c->need[1]);
     c->hx_mem.reset();
-    if (ok && c->xh_enable && hx_par) { void* q = nullptr; if (xr_alloc(c, &q, 2 * hx_par, false)) (void)hipGetLastError(); c->hx_mem.adopt(q); }
+    if (ok && c->knob.xh_enable && hx_par) { void* q = nullptr; if (xr_alloc(c, &q, 2 * hx_par, false)) (void)hipGetLastError(); c->hx_mem.adopt(q); }
     const bool hx_ok = ok && c->hx_mem && hipIpcGetMemHandle(&hh, c->hx_mem) == hipSuccess;
     if (ok && c->xr && c->xr_doubles < want) { c->xr.reset(); c->xr_doubles = 0; }
     if (ok && !c->xr) {
@@ -506,7 +505,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     handle_to_doubles(hx, mine); handle_to_doubles(hb, mine + 64);
     mine[128] = (double)((char*)c->band.rec[0] - (char*)(float4*)c->rec_mem); mine[129] = (double)((char*)c->band.rec[1] - (char*)(float4*)c->rec_mem);
     mine[130] = (double)getpid(); mine[131] = ok ? 1.0 : 0.0; mine[133] = nonce;
-    mine[132] = (hx_ok || (ok && c->xh_enable && !hx_par)) ? 1.0 : 0.0;      // (a rank that needs no halo rows has nothing to stage and is fine with the pushes)
+    mine[132] = (hx_ok || (ok && c->knob.xh_enable && !hx_par)) ? 1.0 : 0.0;      // (a rank that needs no halo rows has nothing to stage and is fine with the pushes)
     if (hx_ok) handle_to_doubles(hh, mine + 136);
     c->xr_serial += 1;               // (the same on every rank: set-ups are collective)
     c->xr_closed_off = (long long)want - R;
@@ -576,7 +575,7 @@ int xr_setup(psgsdf_ctx* c, const std::vector<double>& info) {
     // agreement: every rank or none.  (Every rank's region was zeroed above, before its handle went out: no word of an earlier band or a raised
     // abort flag survives into the solves of this one.)
     if (ok) {      // the frame rows' exchange table (the flags carry the exchange's number, which only grows: the zeroed region matches none)
-        XfTable t{}; t.n_ranks = R; t.rank = me; t.F = std::max(c->F, 1); t.spin_max = c->xwait_spins; t.pay = kXrDoubles; t.flg = (long long)kXrDoubles + (long long)frows * kFrameRow; t.spay = t.flg + (long long)frows; t.sflg = t.spay + (long long)2 * R * 8;
+        XfTable t{}; t.n_ranks = R; t.rank = me; t.F = std::max(c->F, 1); t.spin_max = c->knob.xwait_spins; t.pay = kXrDoubles; t.flg = (long long)kXrDoubles + (long long)frows * kFrameRow; t.spay = t.flg + (long long)frows; t.sflg = t.spay + (long long)2 * R * 8;
         for (int r = 0; r < R; ++r) t.region[r] = c->xr_peer[r];
         if (!c->xf_table && c->xf_table.alloc(1) != hipSuccess) ok = false;
         if (ok && hipMemcpyAsync(c->xf_table, &t, sizeof(t), hipMemcpyHostToDevice, c->stream) != hipSuccess) ok = false;

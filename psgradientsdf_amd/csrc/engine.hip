@@ -9,7 +9,7 @@ namespace psge {
 
 int wait_mapped(psgsdf_ctx* c, const std::function<bool()>& ready, const char* what) {
     using clk = std::chrono::steady_clock;
-    static const double limit_s = [] { const char* e = getenv("PSGSDF_WAIT_TIMEOUT_S"); double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 120.0; }();
+    static const double limit_s = knob_wait_timeout_s();      // (once per process)
     clk::time_point t0{}, next_query{};
     bool timing = false;
     for (unsigned spin = 1;; ++spin) {
@@ -41,9 +41,9 @@ SweepArgs make_args(psgsdf_ctx* c, int laplacian_reg) {
     a.acc.frame = c->acc_frame; a.acc.part = c->part; a.acc.PB = c->PB;
     a.acc.fpart = c->frame_part; a.acc.fcap = c->frame_cap; a.acc.fdone = c->frame_done;
     a.fold.n = 0; a.gate = nullptr; a.fuse_apply = 0;
-    a.xcd_map = c->xcd_map; a.xf = nullptr; a.xf_epoch = 0; a.fm_led_light = nullptr; a.vm_order = c->vm_order;
+    a.xcd_map = c->knob.xcd_map; a.xf = nullptr; a.xf_epoch = 0; a.fm_led_light = nullptr; a.vm_order = c->vm_order;
     a.fm_solve = 0; a.fm_frames = nullptr; a.fm_undo = nullptr; a.fm_e_out = nullptr; a.fm_e_key = 0;
-    a.pcg_part = c->pcg_part; a.pcg_fs = c->pcg_sc; a.pcg_fuse_init = 0; a.pcg_init_blocks = 0; a.pcg_gran = nullptr; a.pcg_gran_n = 0; a.pcg_asm = 0; a.pcg_epoch = 0; a.pcg_win = (c->pcg_window && c->win_G > 0 && !c->pcg_ablate) ? c->win_tab : nullptr;      /* (the timing ablations live in the gathering instance) */ a.pcg_win_G = c->win_G; a.pcg_win_rows = c->win_rows; a.pcg_win_max = c->win_max; a.pcg_apply = 0; a.pcg_ablate = c->pcg_ablate;
+    a.pcg_part = c->pcg_part; a.pcg_fs = c->pcg_sc; a.pcg_fuse_init = 0; a.pcg_init_blocks = 0; a.pcg_gran = nullptr; a.pcg_gran_n = 0; a.pcg_asm = 0; a.pcg_epoch = 0; a.pcg_win = (c->knob.pcg_window && c->win_G > 0 && !c->knob.pcg_ablate) ? c->win_tab : nullptr;      /* (the timing ablations live in the gathering instance) */ a.pcg_win_G = c->win_G; a.pcg_win_rows = c->win_rows; a.pcg_win_max = c->win_max; a.pcg_apply = 0; a.pcg_ablate = c->knob.pcg_ablate;
     a.ar = c->ar; a.ar.weight = c->reg_r;
     a.model = c->set.model; a.quirks = c->set.ref_quirks;
     a.reg_n = c->reg_n; a.reg_l = c->reg_l;
@@ -75,7 +75,7 @@ int deliver_first(psgsdf_ctx* c, size_t count, bool told_landed) {
     count = std::min(count, c->deferred.size());
     for (size_t e = 0; e < count; ++e) {
         Deferred& d = c->deferred[e];
-        if (d.key && c->mbox_check) {
+        if (d.key && c->knob.mbox_check) {
             c->mbox_checked++;
             if (!readback_landed(d)) {
                 if (told_landed) c->mbox_late++;      // (a speculation window WAITS here for its closing energy: not an event)
@@ -94,7 +94,7 @@ int deliver_first(psgsdf_ctx* c, size_t count, bool told_landed) {
     if (c->mbox && c->mbox_n && ((volatile double*)c->mbox)[c->mbox_n + 1] != 0.0) {
         const double ep = ((volatile double*)c->mbox)[c->mbox_n + 1];
         ((volatile double*)c->mbox)[c->mbox_n + 1] = 0.0;
-        return fail(c, PSGSDF_ERR_DEVICE, "rank %d of %d: halo pull %.0f gave up -- a neighbour's halo rows never arrived within the bounded wait (2^%d polls); the halo rows were filled with NaN", c->rank, c->n_ranks, ep, (int)log2((double)c->xwait_spins));
+        return fail(c, PSGSDF_ERR_DEVICE, "rank %d of %d: halo pull %.0f gave up -- a neighbour's halo rows never arrived within the bounded wait (2^%d polls); the halo rows were filled with NaN", c->rank, c->n_ranks, ep, (int)log2((double)c->knob.xwait_spins));
     }
     if (c->xf_timeout) {
         c->xf_timeout = false;
@@ -104,7 +104,7 @@ int deliver_first(psgsdf_ctx* c, size_t count, bool told_landed) {
         if (late[0] == 0 && late[1] == 0 && late[2] == 0)
             return fail(c, PSGSDF_ERR_DEVICE, "rank %d of %d: NaN came back from an exchange between the ranks' kernels, and no bounded wait of this rank expired: a peer handed on NaN (its wait expired, or the state itself is NaN)", c->rank, c->n_ranks);
         return fail(c, PSGSDF_ERR_DEVICE, "rank %d of %d: NaN came back from an exchange between the ranks' kernels -- a peer's contribution never arrived within the bounded wait (2^%d polls): frame rows of exchange %.0f (missing: rank %d's row of frame %d), scalar fold %.0f, halo pull %.0f (0 = not that one)",
-                    c->rank, c->n_ranks, (int)log2((double)c->xwait_spins), late[0], (int)late[3] / 1000, (int)late[3] % 1000, late[1], late[2]);
+                    c->rank, c->n_ranks, (int)log2((double)c->knob.xwait_spins), late[0], (int)late[3] / 1000, (int)late[3] % 1000, late[1], late[2]);
     }
     return 0;
 }
@@ -123,13 +123,13 @@ int flush(psgsdf_ctx* c) {
     // flush): it watches the LAST read-back's words, then validates all of them in deliver().  Without read-backs in flight (or with
     // PSGSDF_MBOX_CHECK=0 / PSGSDF_PCG_POLL=0 / profiling) the stream is drained the ordinary way.
     bool synced = false;
-    if (c->pcg_poll && !c->profiling && c->mbox && c->mbox_check && !c->deferred.empty() && c->deferred.back().key) {
+    if (c->knob.pcg_poll && !c->profiling && c->mbox && c->knob.mbox_check && !c->deferred.empty() && c->deferred.back().key) {
         const Deferred& d = c->deferred.back();
         const volatile double* v = d.src; const int n = d.n; const unsigned long long key = d.key;
         const int w = wait_mapped(c, [v, n, key] { for (int i = 0; i < n; ++i) if ((dbits(v[i]) ^ dbits(v[n + i])) != key + (unsigned long long)i) return false; return true; }, "flush");
         if (w < 0) return w;
         synced = w == 0;
-    } else if (c->pcg_poll && !c->profiling && c->mbox) {
+    } else if (c->knob.pcg_poll && !c->profiling && c->mbox) {
         // a marker kernel + re-reading its mapped slot instead of hipStreamSynchronize: the runtime call itself is slower and makes the
         // next dispatch wait 5.8 us behind a system-scope fence (profiles/r01_notes.md, step p)
         const double seq = (c->flush_seq += 1.0);
@@ -205,7 +205,7 @@ int read_parts_deferred(psgsdf_ctx* c, const int* slots, int n, std::function<vo
     if (staged) c->mg_segs.push_back({(unsigned)off, (unsigned)n, key});
     const XfTable* xf = xs ? c->xf_table : nullptr;
     const long long ep = xs ? ++c->xs_epoch : 0;
-    if (n <= 4 && c->fold_in_next) {
+    if (n <= 4 && c->knob.fold_in_next) {
         c->pending_fold.n = n; for (int i = 0; i < n; ++i) c->pending_fold.id[i] = slots[i];
         c->pending_fold.nblk = band_blocks(c); c->pending_fold.out = dst; c->pending_fold.key = dkey; c->pending_fold.xf = xf; c->pending_fold.xf_epoch = ep;
     } else {
@@ -293,7 +293,7 @@ int build_band(psgsdf_ctx* c) {
         HIPCHK(c, hipMemcpyAsync(&reach, c->d_total, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         b.col16 = reach <= 32767; b.reach = reach;
-        if (const char* e = getenv("PSGSDF_PCG_COL16")) if (atoi(e) == 0) b.col16 = 0;
+        if (!knob_pcg_col16()) b.col16 = 0;
     }
     // row partition.  The band is sorted by linear index, z slowest, so the rows of the OWN planes [z0, z1) are one contiguous range
     // [row0, row1); the rows before it are the lower halo plane, the rows behind it the upper one (multi-rank only).
@@ -393,7 +393,7 @@ int build_band(psgsdf_ctx* c) {
     {   // the LDS windows of the persistent solve's partition: the band is fixed until it is rebuilt, and so is what every workgroup's rows reference
         c->win_G = c->win_rows = c->win_max = 0;
         int Gs = 0, Rs = 0;
-        if (c->pcg_window && c->n_ranks <= 1 && cgf_solve_shape(c, &Gs, &Rs)) {
+        if (c->knob.pcg_window && c->n_ranks <= 1 && cgf_solve_shape(c, &Gs, &Rs)) {
             if (!c->win_tab) HIPCHK(c, c->win_tab.alloc(6 * kSolveMaxBlocksHost + 1));
             int* d_max = c->win_tab + 6 * kSolveMaxBlocksHost;
             launch_solve_windows(b, c->row0, c->row1, Gs, Rs, c->win_tab, d_max, c->stream);

@@ -20,6 +20,7 @@
 #pragma once
 #include "engine.h"
 #include "device_own.h"
+#include "knobs.h"
 #include "../../include/psgsdf.h"
 
 #include <math.h>
@@ -75,6 +76,7 @@ using DensePlanes = psge::DensePlanesOf<DenseView>;   // the dense planes and th
 
 struct psgsdf_ctx {
     int device = 0;
+    psge::Knobs knob;                    // what the environment asked for when the context was created (knobs.h)
     hipStream_t stream = nullptr;
     psgsdf_settings set{};
     float reg_n = 0, reg_l = 0;
@@ -118,11 +120,6 @@ struct psgsdf_ctx {
     DevBuf<double> pcg_part;             // [2][7][kPcgMaxBlocks]
     DevBuf<double> pcg_gran;             // persistent solve: [2][kSolveGranPlanes][kSolveMaxBlocksHost] tagged per-workgroup sums
     unsigned pcg_solve_serial = 0;       // distance solves launched on this context (SweepArgs::pcg_epoch)
-    int pcg_ablate = 0;                  // PSGSDF_PCG_ABLATE: timing ablations of the persistent solve, bits 1 and 4 (wrong results; tools only)
-    bool pcg_fuse_apply = true;          // PSGSDF_PCG_FUSE_APPLY=0: k_apply_dist behind it
-    bool pcg_persist = true;             // PSGSDF_PCG_PERSIST=0: always the per-pass kernels
-    bool pcg_window = true;              // PSGSDF_PCG_WINDOW=0: the single-rank pipelined solve gathers per thread instead of reading an LDS window (pcg_solve.h k_cgp_solve<.., WIN>)
-    int pcg_solve_rows = 0;              // PSGSDF_PCG_SOLVE_ROWS: rows per workgroup of the persistent solve on one rank (0: as many workgroups as CUs); tests shape the partition with it
     DevBuf<int> win_tab;                 // [6 kSolveMaxBlocksHost + 1] window table of this band and partition (pcg.hip k_solve_windows) + its largest total
     int win_G = 0, win_rows = 0, win_max = 0;      // ... the partition it was computed for (0: no table) and the largest window in doubles
     int last_solve_windowed = -1;        // the last persistent distance solve ran the windowed instance (1) or not (0); -1: none yet
@@ -137,16 +134,14 @@ struct psgsdf_ctx {
     size_t mbox_alloc = 0; double flush_seq = 0;    // the last slot of the allocation is the flush marker
     std::vector<psge::Deferred> deferred;
     unsigned long long mbox_serial = 0;  // key generator of the read-back slots
-    bool mbox_check = true;              // PSGSDF_MBOX_CHECK=0: take read-backs on the marker's / status word's say-so (round-2 behaviour; reproduces its flake)
     // speculative start of an iteration (loop.hip run_loop): albedo / light updates applied before the stop decision of the previous iteration is
     // known keep what they overwrite, so that the loop can still end on exactly the state the reference ends on
     psgsdf_iter_cb observer = nullptr; void* observer_user = nullptr;   // psgsdf_set_record_observer
     int on_iter_period = 1;              // psgsdf_set_on_iter_period
-    bool speculate = true;               // PSGSDF_SPECULATE=0: always wait for the decision first (round 2)
     bool spec_undo = false, spec_albedo_saved = false, spec_light_saved = false;
     DevBuf<float> frames_undo;           // device: the [F] frame records as floats + 4 floats (LED light)
     long long spec_windows = 0, spec_undos = 0;
-    int fault_solve = 0, solves_seen = 0;   // PSGSDF_FAULT_SOLVE=n: fault injection into the n-th persistent solve of this context
+    int solves_seen = 0;                 // persistent solves counted towards knob.fault_solve (fault injection into the n-th of this context)
     long long persist_fallbacks = 0;     // distance steps re-run on the per-pass kernels after the persistent solve gave up (loop.hip)
     long long mbox_checked = 0, mbox_late = 0;   // read-backs validated / of those: not complete yet when the host was told everything had landed
     // cached energies
@@ -157,7 +152,6 @@ struct psgsdf_ctx {
     psge::Comm* comm = nullptr;          // transport of the multi-rank exchanges (comm.hip); null on a single-rank context
     // cross-rank persistent solve (comm.hip xr_setup, pcg_solve.h k_cgp_solve<.., MR>): this rank's mailbox region, every rank's region and the two
     // neighbours' band arenas mapped through IPC handles; rebuilt with every band
-    bool xr_enable = true;               // PSGSDF_XR=0: multi-rank contexts always use the per-pass kernels + RCCL all-reduce (round 2)
     bool xr_ready = false; long long xr_solves = 0;
     DevBuf<double> xr;
     int xr_mem_kind = -1;                // memory kind of xr / rec_mem chosen by xr_probe: 1 fine-grained records + uncached region, 2 both uncached, 0 none passed (cross-rank solve off); -1 not probed yet
@@ -174,7 +168,6 @@ struct psgsdf_ctx {
     void* band_peer[2] = {nullptr, nullptr};   // lower / upper neighbour's record planes: IPC mappings
     std::vector<void*> xr_opened;        // every IPC mapping this context opened: closed, not freed (comm.hip xr_release)
     XrArgs xr_args{};
-    int cu_mask_lo = -1, cu_mask_hi = -1;      // PSGSDF_CU_MASK=lo:hi: the context's stream only uses CUs [lo, hi) (two ranks sharing one GPU)
     DevBuf<double> mg_scal;              // [kMgScal] set-up exchange (what each slab needs of its neighbours)
     DevBuf<double> mg_ext;               // [8] PCG: local sums of a pass out, globally reduced sums in
     // multi-rank: deferred scalar read-backs are folded into a DEVICE shadow of the mailbox; before the host waits on the mailbox the
@@ -186,48 +179,30 @@ struct psgsdf_ctx {
     long long n_collectives = 0;
     float reg_r = 0.f;                   // "reg albedo" (never normalised, PsOptimizer.cpp:279)
     DevBuf<char> areg_mem; AlbedoReg ar{};   // planes of the albedo regulariser (ar points into areg_mem), allocated with the band when reg_r != 0
-    bool areg_device = true; int areg_last_iters = 0;      // PSGSDF_AREG_DEVICE=0: the regularised albedo solve driven by the host (two read-backs per CG iteration: what multi-rank contexts run)
+    int areg_last_iters = 0;             // CG iterations of the last device-driven regularised albedo solve (sizes the next one's first chunk)
     double er_sum = 0;                   // sum over the band of sum_c ||grad rho_c|| at the last evaluation
     FoldReq pending_fold{};              // scalar fold waiting for the next kernel (read_parts_deferred / take_fold)
-    bool fuse_pcg_init = true;           // PSGSDF_FUSE_PCG_INIT=0: separate k_cgf_init launch
-    bool fuse_albedo = true;             // PSGSDF_FUSE_ALBEDO=0: separate k_apply_albedo launch
-    bool fold_in_next = true;            // PSGSDF_FOLD_IN_NEXT=0: always a k_sum_parts launch
-    int xwait_spins = 1 << 24;           // polls of a wait inside a kernel for a peer's flag (PSGSDF_XWAIT_LOG2)
-    long long fault_halo = 0;            // PSGSDF_FAULT_HALO
-    bool xh_enable = true;               // PSGSDF_XH=0: halo rows through RCCL send / recv (round 3)
     DevBuf<char> hx_mem;                 // halo staging the two neighbours push into (fine-grained, IPC-exported): [2 parities][lower | upper side]
     char* hx_peer[2] = {nullptr, nullptr};   // the neighbours' stagings (lower, upper): IPC mappings
     size_t hx_peer_par[2] = {0, 0}, hx_peer_off[2] = {0, 0}, hx_par = 0;
     long long hx_flag_off = 0, hx_epoch = 0, n_halo_pushes = 0;
     bool hx_ready = false;
-    bool xs_enable = true;               // PSGSDF_XS=0: multi-rank scalar read-backs staged in the mailbox shadow and all-reduced over RCCL (round 3)
     long long xs_epoch = 0;              // scalar folds exchanged so far (the same on every rank)
-    bool xf_enable = true;               // PSGSDF_XF=0: multi-rank frame rows through an RCCL all-reduce + solve kernels (round 3)
     DevBuf<XfTable> xf_table;            // device copy of the exchange table (valid while xr_ready)
     long long xf_epoch = 0;              // exchanges so far (the same on every rank)
     size_t xr_doubles = 0;               // size of this rank's mailbox region
     bool any_empty_slab = false;         // some rank's slab has no observation at all (agreed at band build)
     bool xf_timeout = false;             // a frame row came back NaN: a rank's row never arrived
-    bool img_compact = true;             // PSGSDF_IMG_COMPACT=0: float keyframes stay float even when every value is (float)byte / 255
     bool img_compacted = false;          // the float keyframes of this context are held as RGBA8 words
-    bool speculate_mr = true;            // PSGSDF_SPECULATE_MR=0: no speculative start of the next iteration on multi-rank contexts (round 3's loop)
     DevBuf<int> vm_order;                // distance sweep: physical workgroup -> logical block, heaviest first (build_band)
-    int xcd_map = 163;                   // PSGSDF_XCD_MAP: logical workgroup ids -- bit 0 frame-major sweeps XCD-contiguous, bit 1 k_sweep_albedo / k_energy / k_derive XCD-contiguous, bit 2 k_sweep_dist XCD-contiguous (off: 68 -> 76 us), bit 5 (32) k_sweep_dist heaviest block first (70 -> 62 us), bit 6 (64) albedo / energy heaviest first (no gain), bit 7 (128) the per-pass distance solve k_cgf_pass XCD-contiguous (round 6); PSGSDF_XCD_STRIPE=T: stripes of T ids instead of eighths
-    bool fm_solve = true;                // PSGSDF_FM_SOLVE=0: k_solve_light / k_solve_pose as kernels of their own behind the frame-major sweeps
-    bool fm_solve_led = true;            // ... also the LED light vector (by the sweep's very last workgroup); PSGSDF_FM_SOLVE=2 keeps k_solve_light for it
     bool fm_solved = false;              // the sweep just launched solves its frames itself (step_begin -> step_finish)
-    int frame_solve = 0;                 // PSGSDF_FRAME_SOLVE / psgsdf_set_frame_solver: 0 = LDL^T per frame in double (default), 1 = the reference's solver: ONE Eigen-style float Jacobi-PCG over the block-diagonal system of all frames (frame_solve.hip)
     DevBuf<double> fs_stats;             // device [2][4]: {iterations, ||r||/||b||, Success, applied} of the last eigen light / pose solve
     double fs_last[2][4] = {{0, 0, 1, 1}, {0, 0, 1, 1}};   // host copy, refreshed by the synchronous steps (psgsdf_step, psgsdf_get_frame_solver_stats)
     bool albedo_applied = false;         // the last albedo sweep already applied its update (step_begin -> step_finish)
     DevBuf<unsigned> img8; float img_scale = 0.f;   // keyframes uploaded as 8-bit RGB (psgsdf_set_keyframes_u8): RGBA8 words, c->img stays null
     double* frame_e_slot = nullptr; unsigned long long frame_e_key = 0;   // slot of mbox, as the device addresses it (and its key), the next per-frame solve writes its sweep's energy sums to
-    bool ao_cut = true;                  // PSGSDF_AO_CUT=0: the rays of include/psgsdf_occlusion.h walk on past their radius (what the cut buys: tools/time_mesh.py; the same bits)
-    long long compare_chunk = 1ll << 24; // PSGSDF_COMPARE_CHUNK: queries per launch of include/psgsdf_compare.h's search (1 .. 2^24; the same bits)
-    long long query_chunk = 1ll << 30;   // PSGSDF_QUERY_CHUNK: queries per launch of include/psgsdf_query.h's kernels (a multiple of 64 up to 2^30; the same bits)
     long long cmp_pairs[2] = {0, 0}, cmp_queries[2] = {0, 0};   // the last psgsdf_compare_reference: candidate pairs evaluated and queries, per direction (psgsdf_get_tuning "last_compare"; tools/time_compare.py)
     long long aln_evals = 0, aln_iters = 0, aln_pairs[2] = {0, 0}, aln_queries[2] = {0, 0};   // the last psgsdf_align_reference: evaluations, steps, and per direction the queries searched and candidate pairs evaluated over all evaluations (psgsdf_get_tuning "last_align"; tools/time_align.py)
-    bool pcg_poll = true;                // PCG stop test by watching the mapped mailbox (PSGSDF_PCG_POLL=0: drain the stream instead)
     int need[2] = {0, 0}; DevBuf<int> d_need;   // halo rows needed below row0 / from row1 up
     bool own_stream = true;
     // profiling
@@ -320,6 +295,7 @@ int xr_alloc(psgsdf_ctx* c, void** p, size_t bytes, bool polled);     // comm.hi
 int mg_commit(psgsdf_ctx* c);                                          // engine.hip: all-reduce + deliver the staged scalar read-backs
 int set_local_grid(psgsdf_ctx* c, int z0, int z1);                     // engine.hip: this context owns global planes [z0, z1) (+ halo planes)
 
+std::string knobs_effective_json(const psgsdf_ctx* c);   // api.hip: the knobs' members of psgsdf_get_tuning's "effective" (the one unit that holds the table of knobs.h)
 int host_stage(psgsdf_ctx* c, size_t bytes, void** p);   // api.hip: engine-owned pinned host memory of at least `bytes` (grows; valid until the next call)
 int frontend_normals_dev(psgsdf_ctx* c, const float* d_depth, int width, int height, float* d_normals);   // api_frontend.hip: FALS normals, device to device
 // ---- engine.hip
@@ -328,7 +304,7 @@ SweepArgs make_args(psgsdf_ctx* c, int laplacian_reg);
 // the RCCL path is exercised on a one-GPU box and how its overhead is measured, bench.py --force-slab)
 inline bool slab_mode(const psgsdf_ctx* c) { return c->comm != nullptr || c->n_ranks > 1; }
 // the scalar folds exchange their sums between the ranks themselves (device_common.h fold_exchange): no staging, no all-reduce
-inline bool xs_active(const psgsdf_ctx* c) { return c->n_ranks > 1 && c->xs_enable && c->xr_ready && c->xf_table != nullptr; }
+inline bool xs_active(const psgsdf_ctx* c) { return c->n_ranks > 1 && c->knob.xs_enable && c->xr_ready && c->xf_table != nullptr; }
 inline int band_blocks(const psgsdf_ctx* c) { return (c->row1 - c->row0 + kBlock - 1) / kBlock; }
 inline double band_mean(const psgsdf_ctx* c, double sum) { return c->S_global ? sum / (double)c->S_global : 0.0; }   // (1/S) sum over the band of the WHOLE volume
 inline float total_energy(const psgsdf_ctx* c, float E, float E_n, float E_l, float E_r = 0.f) { return E + c->reg_n * E_n + c->reg_l * E_l + c->reg_r * E_r; }   // OptimizerAux.cpp:261

@@ -111,7 +111,7 @@ int ao_run(psgsdf_ctx* c, DevMem& mem, const char* me, const psgsdf_ao_params& p
     a.radius = p.radius; a.bias = p.bias; a.vs = (double)c->grid.vs;
     a.t_max = (float)p.radius;      // rounded up if the conversion rounded down: no hit within the radius is cut off
     if ((double)a.t_max < p.radius) a.t_max = nextafterf(a.t_max, INFINITY);
-    if (!c->ao_cut) a.t_max = FLT_MAX;      // (PSGSDF_AO_CUT=0; tools/time_mesh.py: what the cut buys -- the same bits)
+    if (!c->knob.ao_cut) a.t_max = FLT_MAX;      // (PSGSDF_AO_CUT=0; tools/time_mesh.py: what the cut buys -- the same bits)
     double* d_dirs = nullptr;
     const size_t n = (size_t)a.n;
     if (!mem.get(&d_dirs, 3 * (size_t)K) || !mem.get(&a.mask, n) || !mem.get(&a.occ, n) || !mem.get(&a.counts, (size_t)psg::kAoCounts))

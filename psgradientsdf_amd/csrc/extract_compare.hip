@@ -117,7 +117,7 @@ int compare_direction(psgsdf_ctx* c, DevMem& mem, const char* me, psg::CompareAr
     if (hipMemsetAsync(a.stats, 0, sizeof(unsigned long long) * psg::kCmpStats, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: memset", me);
     if (int rc = compare_grid(c, mem, me, a, box, cell)) return rc;
     hipError_t e = hipSuccess;
-    timed(c, dir ? "compare_query_rec" : "compare_query_ref", [&] { e = psg::launch_compare_query(a, c->compare_chunk, c->stream); });
+    timed(c, dir ? "compare_query_rec" : "compare_query_ref", [&] { e = psg::launch_compare_query(a, c->knob.compare_chunk, c->stream); });
     if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld queries: %s", me, a.nq, hipGetErrorString(e));
     timed(c, "compare_stats", [&] { e = psg::launch_compare_stats(a, c->stream); });
     if (e != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch: %s", me, hipGetErrorString(e));
@@ -318,12 +318,12 @@ extern "C" int psgsdf_align_reference(psgsdf_ctx* c, const psgsdf_mesh_filter* f
         }
         if (e == hipSuccess && nb1 > 0) {
             R1.s.max_dist = radius;
-            timed(c, "align_query_1", [&] { e = psg::launch_compare_query(R1.s, c->compare_chunk, c->stream); });
+            timed(c, "align_query_1", [&] { e = psg::launch_compare_query(R1.s, c->knob.compare_chunk, c->stream); });
             if (e == hipSuccess) timed(c, "align_rows_1", [&] { e = psg::launch_align_rows(R1, 1, c->stream); });
         }
         if (e == hipSuccess && nb2 > 0) {
             R2.s.max_dist = radius; memcpy(R2.T, T, sizeof(T));
-            timed(c, "align_query_2", [&] { e = psg::launch_compare_query(R2.s, c->compare_chunk, c->stream); });
+            timed(c, "align_query_2", [&] { e = psg::launch_compare_query(R2.s, c->knob.compare_chunk, c->stream); });
             if (e == hipSuccess) timed(c, "align_rows_2", [&] { e = psg::launch_align_rows(R2, 2, c->stream); });
         }
         if (e == hipSuccess) timed(c, "align_fold", [&] { e = psg::launch_align_fold(R1.partial, nb1, R2.partial, nb2, d_sys, c->stream); });

@@ -54,7 +54,7 @@ extern "C" int psgsdf_query_points(psgsdf_ctx* c, const float* xyz, int64_t n, i
     if (!mem.get(&a.status, N) || !mem.get(&a.dist, N) || !mem.get(&a.normal, 3 * N) || !mem.get(&a.rgb, 3 * N) || !mem.get(&a.weight, N) || !mem.get(&a.voxel, N))
         return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld points)", me, (long long)n);
     hipError_t launched = hipSuccess;
-    timed(c, "k_query_points", [&] { launched = psg::launch_query_points(a, model, c->query_chunk, c->stream); });
+    timed(c, "k_query_points", [&] { launched = psg::launch_query_points(a, model, c->knob.query_chunk, c->stream); });
     if (launched != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld points: %s", me, (long long)n, hipGetErrorString(launched));
     unsigned long long cnt[psg::kQueryCounts] = {};
     if (hipMemcpyAsync(cnt, a.counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the counts", me);
@@ -90,7 +90,7 @@ extern "C" int psgsdf_project_points(psgsdf_ctx* c, const float* xyz, int64_t n,
     if (!mem.get(&a.status, N) || !mem.get(&a.xyz, 3 * N) || !mem.get(&a.dist, N) || !mem.get(&a.normal, 3 * N) || !mem.get(&a.voxel, N) || !mem.get(&a.iters, N) || !mem.get(&a.moved, N))
         return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld points)", me, (long long)n);
     hipError_t launched = hipSuccess;
-    timed(c, "k_query_project", [&] { launched = psg::launch_query_project(a, p->model, c->query_chunk, c->stream); });
+    timed(c, "k_query_project", [&] { launched = psg::launch_query_project(a, p->model, c->knob.query_chunk, c->stream); });
     if (launched != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld points: %s", me, (long long)n, hipGetErrorString(launched));
     unsigned long long cnt[psg::kQueryCounts] = {};
     if (hipMemcpyAsync(cnt, a.counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the counts", me);
@@ -126,7 +126,7 @@ extern "C" int psgsdf_cast_rays(psgsdf_ctx* c, const float* origins, const float
     if (!mem.get(&a.status, N) || !mem.get(&a.t, N) || !mem.get(&a.xyz, 3 * N) || !mem.get(&a.normal, 3 * N) || !mem.get(&a.rgb, 3 * N) || !mem.get(&a.voxel, N))
         return fail(c, PSGSDF_ERR_DEVICE, "%s: out of memory (%lld rays)", me, (long long)n);
     hipError_t launched = hipSuccess;
-    timed(c, "k_query_rays", [&] { launched = psg::launch_query_rays(a, c->query_chunk, c->stream); });
+    timed(c, "k_query_rays", [&] { launched = psg::launch_query_rays(a, c->knob.query_chunk, c->stream); });
     if (launched != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: launch of %lld rays: %s", me, (long long)n, hipGetErrorString(launched));
     unsigned long long cnt[psg::kQueryRayCounts] = {};
     if (hipMemcpyAsync(cnt, a.counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return fail(c, PSGSDF_ERR_DEVICE, "%s: download of the counts", me);

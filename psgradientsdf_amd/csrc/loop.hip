@@ -14,9 +14,7 @@ namespace psge {
 constexpr int kCgfSumsHost = 7;   // = kCgfSums (device_common.h): P, B, C, D, E, Z, R of a pass
 void cgf_shape(int nblk, int* G, int* rows) {
     nblk = std::max(1, nblk);
-    int r = 1, cap = kCgfMaxBlocks;
-    if (const char* e = getenv("PSGSDF_PCG_ROWS")) { int v = atoi(e); if (v >= 1 && v <= 2) r = v; }       // tuning knobs
-    if (const char* e = getenv("PSGSDF_PCG_BLOCKS")) { int v = atoi(e); if (v > 0 && v <= kCgfMaxBlocks) cap = v; }
+    const int r = knob_pcg_rows(), cap = knob_pcg_blocks(kCgfMaxBlocks);      // PSGSDF_PCG_ROWS / _BLOCKS, read at every solve
     const int per = (nblk + r - 1) / r;                 // workgroups if every thread took r rows once
     const int trips = (per + cap - 1) / cap;
     *G = (per + trips - 1) / trips; *rows = r;
@@ -27,7 +25,7 @@ void cgf_shape(int nblk, int* G, int* rows) {
 // which is the per-pass kernels' all-reduce -- and only with 16-bit column deltas and the assembly kernel's fused initialisation.
 bool cgf_solve_shape(psgsdf_ctx* c, int* G, int* rows_per_wg, bool any_ranks) {
     // (multi-rank: only with the cross-rank mappings of comm.hip xr_setup in place -- all ranks or none, agreed there)
-    if (!c->pcg_persist || c->persist_off || (c->n_ranks > 1 && !c->xr_ready && !any_ranks) || !c->band.col16 || !c->fuse_pcg_init || c->num_cu <= 0 || band_blocks(c) > kPcgMaxBlocks) return false;
+    if (!c->knob.pcg_persist || c->persist_off || (c->n_ranks > 1 && !c->xr_ready && !any_ranks) || !c->band.col16 || !c->knob.fuse_pcg_init || c->num_cu <= 0 || band_blocks(c) > kPcgMaxBlocks) return false;
     const int n = c->row1 - c->row0, cap = std::min(c->num_cu, kSolveMaxBlocksHost);
     if (n <= 0) return false;
     // as many workgroups as CUs (in multiples of 8: every XCD owns a contiguous range of rows) unless the band is so small that a workgroup
@@ -36,8 +34,8 @@ bool cgf_solve_shape(psgsdf_ctx* c, int* G, int* rows_per_wg, bool any_ranks) {
     g = std::max(8, g / 8 * 8);
     if (g > cap) g = cap;
     int per = ((n + g - 1) / g + 63) / 64 * 64;
-    if (c->pcg_solve_rows > 0 && c->n_ranks <= 1) {      // PSGSDF_PCG_SOLVE_ROWS: the rows per workgroup are given, the workgroups follow
-        per = (c->pcg_solve_rows + 63) / 64 * 64;
+    if (c->knob.pcg_solve_rows > 0 && c->n_ranks <= 1) {      // PSGSDF_PCG_SOLVE_ROWS: the rows per workgroup are given, the workgroups follow
+        per = (c->knob.pcg_solve_rows + 63) / 64 * 64;
         g = (n + per - 1) / per;
         if (g > cap) return false;
     }
@@ -75,7 +73,7 @@ int pcg_solve(psgsdf_ctx* c, SweepArgs& a, int* iters_out, int* success_out, dou
         volatile double* st = c->mbox + off;
         const unsigned long long key = (++c->mbox_serial << 8) | 0x80u;
         st[3] = NAN; st[4] = 0.0;
-        const int inject = (c->fault_solve > 0 && ++c->solves_seen == c->fault_solve) ? -7 : 0;      // PSGSDF_FAULT_SOLVE=n: one workgroup of the n-th solve stops publishing (tests the fallback below)
+        const int inject = (c->knob.fault_solve > 0 && ++c->solves_seen == c->knob.fault_solve) ? -7 : 0;      // PSGSDF_FAULT_SOLVE=n: one workgroup of the n-th solve stops publishing (tests the fallback below)
         const XrArgs* xr = (c->n_ranks > 1 && c->xr_ready) ? &c->xr_args : nullptr;
         if (xr) {
             // the solve's epoch (the same on every rank: all ranks run the same solves) goes into every cross-rank tag, so nothing in the mailbox
@@ -93,7 +91,7 @@ int pcg_solve(psgsdf_ctx* c, SweepArgs& a, int* iters_out, int* success_out, dou
         timed(c, "pcg_solve", [&] { c->last_solve_windowed = launch_cgf_solve(as, c->pcg_sc, c->pcg_gran, G, rows, cap, c->mbox_dev + off, key, inject, c->stream, xr); });
         if (tail && !c->profiling) { tail(c->pcg_sc + (gate_on_converged ? 2 : 1)); if (tail_ran) *tail_ran = true; }
         // the four status words are taken only together with their check word (engine.h FoldReq)
-        const bool chk = c->mbox_check;
+        const bool chk = c->knob.mbox_check;
         auto landed = [st, key, chk] {
             const double s3 = st[3];
             if (std::isnan(s3)) return false;
@@ -162,11 +160,11 @@ int pcg_solve(psgsdf_ctx* c, SweepArgs& a, int* iters_out, int* success_out, dou
                 int rc = comm_allreduce(c, c->mg_ext, kCgfSumsHost); if (rc) return rc;
             }
         }
-        if (tail && c->pcg_poll && !c->profiling) { tail(c->pcg_sc + (gate_on_converged ? 2 : 1)); if (tail_ran) *tail_ran = true; }
+        if (tail && c->knob.pcg_poll && !c->profiling) { tail(c->pcg_sc + (gate_on_converged ? 2 : 1)); if (tail_ran) *tail_ran = true; }
         // Watch the mapped slots instead of waiting for the stream to drain: the kernel that detects convergence publishes
         // at its START, so the host learns the outcome while that kernel and the surplus (no-op) kernels of the chunk are
         // still running, and enqueues the rest of the iteration behind them without a bubble.
-        bool drained = !c->pcg_poll;
+        bool drained = !c->knob.pcg_poll;
         if (drained) { int rc = flush(c); if (rc) return rc; }
         for (int q = 0; q < n && iters < 0; ++q) {
             const int kk = k + q;
@@ -237,7 +235,7 @@ int albedo_reg_solve(psgsdf_ctx* c, const SweepArgs& a, int* iters_out, int* ok_
     float res2 = rhsN, absNew = (float)s[1];
     const int maxIters = c->set.cg_max_it > 0 ? c->set.cg_max_it : (int)std::min<long long>(6 * c->S_global, INT_MAX);
     int i = 0;
-    if (res2 >= thr && c->areg_device && !slab_mode(c)) {
+    if (res2 >= thr && c->knob.areg_device && !slab_mode(c)) {
         // ---- device-driven (round 6, single rank): chunks of iterations enqueued back to back, alpha / beta / the stop test derived on the device from the
         // kernels' own partial sums (albedo_reg.hip); ONE look at the five scalars per chunk instead of two read-backs per iteration.  The first chunk is
         // sized from the previous solve (the count is stable between Gauss-Newton iterations); a converged solve makes the rest of its chunk no-ops.
@@ -295,7 +293,7 @@ int step_begin(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* s
             if (block == PSGSDF_ALBEDO) {
                 // without the albedo regulariser the system is diagonal: the sweep applies the update itself (may_apply = false: the caller
                 // has a stop decision pending on this sweep's input energy and nothing may be modified yet)
-                c->albedo_applied = may_apply && c->reg_r == 0.f && c->fuse_albedo;
+                c->albedo_applied = may_apply && c->reg_r == 0.f && c->knob.fuse_albedo;
                 a.fuse_apply = c->albedo_applied ? (c->spec_undo ? 2 : 1) : 0;      // (2: speculative, the old albedo is kept for an undo)
                 if (c->albedo_applied && c->spec_undo) c->spec_albedo_saved = true;
                 take_fold(c, a, (1u << SC_ENERGY) | (1u << SC_NOBS) | (c->albedo_applied ? (1u << SC_ACCEPT) : 0u));
@@ -303,7 +301,7 @@ int step_begin(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* s
             }
             else {
                 materialize_fold(c);
-                { int Gs, Rs; if (c->fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; } }   // the sweep clears the LOCAL tags of the persistent solve behind it (the cross-rank words carry the solve's epoch and are never cleared)
+                { int Gs, Rs; if (c->knob.fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; } }   // the sweep clears the LOCAL tags of the persistent solve behind it (the cross-rank words carry the solve's epoch and are never cleared)
                 timed(c, "sweep_dist", [&] { launch_sweep_dist(a, c->stream); });
             }   // (LED: the fused albedo sweep's sums are still pending and this sweep writes the same slots)
             const int slots[2] = {SC_ENERGY, SC_NOBS}; double s[2];
@@ -321,8 +319,8 @@ int step_begin(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* s
             // Multi-rank (round 4): the slabs' rows of a frame meet inside the sweep (engine.h XfTable: through the ranks' mailbox regions, where the
             // cross-rank persistent solve is set up), so the same epilogue serves -- no RCCL all-reduce of the rows, no solve launch.  A one-rank
             // communicator has nothing to exchange.  (An empty slab still has to deliver its -- zero -- rows: it keeps the all-reduce path, on every rank.)
-            const bool xf = c->n_ranks > 1 && c->xf_enable && c->xr_ready && c->xf_table && !c->any_empty_slab;
-            const bool fuse = deferred_consumer && c->fm_solve && c->frame_solve == 0 && (!slab_mode(c) || c->n_ranks == 1 || xf) && !c->profiling && (block == PSGSDF_POSE || !led || c->fm_solve_led) && c->row1 > c->row0 && c->band.obs_max > 0;
+            const bool xf = c->n_ranks > 1 && c->knob.xf_enable && c->xr_ready && c->xf_table && !c->any_empty_slab;
+            const bool fuse = deferred_consumer && c->knob.fm_solve && c->knob.frame_solve == 0 && (!slab_mode(c) || c->n_ranks == 1 || xf) && !c->profiling && (block == PSGSDF_POSE || !led || c->knob.fm_solve_led) && c->row1 > c->row0 && c->band.obs_max > 0;
             double* fm_slot = nullptr; unsigned long long fm_key = 0;
             if (fuse) {      // (the mailbox slot first: reserving may flush, and a flush must not find the pending fold already handed to `a`)
                 if ((rc = reserve_frame_energy_deferred(c, xf ? std::function<void(double, double)>([c, deferred_consumer](double e, double n) { if (std::isnan(e)) c->xf_timeout = true; deferred_consumer(e, n); }) : deferred_consumer, &fm_slot, &fm_key))) return rc;
@@ -392,7 +390,7 @@ int step_finish(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* 
         case PSGSDF_LIGHT:
             // (a speculative light update keeps the coefficients it overwrites: the solve kernel copies them to frames_undo first)
             if (c->fm_solved) c->fm_solved = false;      // (the sweep's last workgroups solved their frames: step_begin)
-            else if (c->frame_solve == 1) {             // the reference's global float Jacobi-PCG over all frames' blocks (frame_solve.hip)
+            else if (c->knob.frame_solve == 1) {             // the reference's global float Jacobi-PCG over all frames' blocks (frame_solve.hip)
                 if (!frames_eigen_fits(c->set.model, c->F)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "PSGSDF_FRAME_SOLVE=eigen holds at most 2048 unknowns in its one workgroup (%d keyframes)", c->F);
                 timed(c, "solve_light_eigen", [&] { launch_frames_eigen_light(a, c->frames, c->led_light, c->frame_e_slot, c->frame_e_key, c->spec_undo ? (float*)c->frames_undo : nullptr, c->fs_stats, c->stream); });
             }
@@ -400,24 +398,24 @@ int step_finish(psgsdf_ctx* c, int block, int laplacian_reg, psgsdf_step_stats* 
             if (c->spec_undo) c->spec_light_saved = true;
             c->frame_e_slot = nullptr; c->frame_e_key = 0;
             st->cg_converged = 1; st->applied = 1; st->n_accepted = led ? 1 : c->F;
-            if (c->frame_solve == 1 && c->want_counts) { if ((rc = read_frame_solver_stats(c, 0, st))) return rc; }
+            if (c->knob.frame_solve == 1 && c->want_counts) { if ((rc = read_frame_solver_stats(c, 0, st))) return rc; }
             break;
         case PSGSDF_POSE:
             if (c->fm_solved) c->fm_solved = false;
-            else if (c->frame_solve == 1) {
+            else if (c->knob.frame_solve == 1) {
                 if (!frames_eigen_fits(c->set.model, c->F)) return fail(c, PSGSDF_ERR_UNSUPPORTED, "PSGSDF_FRAME_SOLVE=eigen holds at most 2048 unknowns in its one workgroup (%d keyframes)", c->F);
                 timed(c, "solve_pose_eigen", [&] { launch_frames_eigen_pose(a, c->frames, c->frame_e_slot, c->frame_e_key, c->fs_stats + 4, c->stream); });
             }
             else timed(c, "solve_pose", [&] { launch_solve_pose(a, c->frames, c->frame_e_slot, c->frame_e_key, c->stream); });
             c->frame_e_slot = nullptr; c->frame_e_key = 0;
             st->cg_converged = 1; st->applied = 1; st->n_accepted = c->F;
-            if (c->frame_solve == 1 && c->want_counts) { if ((rc = read_frame_solver_stats(c, 1, st))) return rc; st->n_accepted = st->applied ? c->F : 0; }
+            if (c->knob.frame_solve == 1 && c->want_counts) { if ((rc = read_frame_solver_stats(c, 1, st))) return rc; st->n_accepted = st->applied ? c->F : 0; }
             break;
         case PSGSDF_DIST: {
             take_fold(c, a, 0u);
-            if (c->fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks) { a.pcg_fuse_init = 1; a.pcg_init_blocks = band_blocks(c); }   // the assembly kernel initialises the PCG
+            if (c->knob.fuse_pcg_init && band_blocks(c) <= kPcgMaxBlocks) { a.pcg_fuse_init = 1; a.pcg_init_blocks = band_blocks(c); }   // the assembly kernel initialises the PCG
             bool apply_in_solve = false;      // (the accepted count goes to the first G entries of a partial slot that holds one entry per 256 rows)
-            { int Gs, Rs; if (a.pcg_fuse_init && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; apply_in_solve = c->pcg_fuse_apply && Gs <= band_blocks(c); } }   // the assembly kernel also clears the persistent solve's tags
+            { int Gs, Rs; if (a.pcg_fuse_init && cgf_solve_shape(c, &Gs, &Rs)) { a.pcg_gran = c->pcg_gran; a.pcg_gran_n = 2 * kSolveGranPlanes * kSolveMaxBlocksHost; a.pcg_asm = 1; apply_in_solve = c->knob.pcg_fuse_apply && Gs <= band_blocks(c); } }   // the assembly kernel also clears the persistent solve's tags
             if ((rc = comm_halo(c, c->band.blk, 14, 1))) return rc;   // multi-rank: rows of H next to a cut take contributions from the neighbour slab's voxel blocks
             if (!a.pcg_asm) { timed(c, "assemble", [&] { launch_assemble(a, c->stream); }); a.fold.n = 0; }      // (pcg_asm: the persistent solve assembles its rows itself; the distance sweep cleared its tags)
             int iters = 0, ok = 1; double err = 0;
@@ -538,7 +536,7 @@ int run_loop(psgsdf_ctx* c, int flags, LoopState& L, int max_iters, bool full, p
     // host wait, and the window is only ever closed at the same program point on every rank (the blocking poll in front of the first block that
     // cannot be undone): no "has it landed yet?" polls, whose answer could differ from rank to rank and with it the order of the collectives.
     const bool mr_spec = slab_mode(c);
-    const bool spec_base = full && c->speculate && (!mr_spec || c->speculate_mr) && c->reg_r == 0.f && !c->profiling;
+    const bool spec_base = full && c->knob.speculate && (!mr_spec || c->knob.speculate_mr) && c->reg_r == 0.f && !c->profiling;
     auto can_spec_at = [&](int it_closing) { return spec_base && (!on_iter || (it_closing + 1) % c->on_iter_period != 0); };      // (a due on_iter must see the state of the iteration it reports)
     c->spec_undo = false; c->spec_albedo_saved = false; c->spec_light_saved = false;
     const double* close_src = nullptr;   // mailbox address of the closing energy's read-back while a speculation window is open
@@ -585,7 +583,7 @@ int run_loop(psgsdf_ctx* c, int flags, LoopState& L, int max_iters, bool full, p
             const int blk = order[q];
             if (!(flags & blk)) continue;
             psgsdf_step_stats st;
-            const bool undoable = (blk == PSGSDF_ALBEDO && !c->spec_albedo_saved && c->fuse_albedo) || (blk == PSGSDF_LIGHT && !c->spec_light_saved);
+            const bool undoable = (blk == PSGSDF_ALBEDO && !c->spec_albedo_saved && c->knob.fuse_albedo) || (blk == PSGSDF_LIGHT && !c->spec_light_saved);
             if (spec_open && !undoable) { int rc = window_poll(true); if (rc) return rc; if (stop) break; }   // the decision is due now (it arrived long ago: no bubble)
             const int qi = lt.n;
             lt.blk_of[qi] = blk; lt.e_in[qi] = NAN; lt.n++;

@@ -2,6 +2,7 @@
 // the photometric sweeps (initial albedo, PS energy, albedo / light / pose normal equations) and the small per-frame solves.  No CUDA compatibility layer, no other back end.
 // Shared device helpers: device_common.h; the launchers are declared in engine.h.
 #include "device_common.h"
+#include "knobs.h"      // (host: fm_rows reads PSGSDF_FM_ROWS)
 
 namespace psg {
 
@@ -197,7 +198,7 @@ void launch_apply_albedo(const SweepArgs& a, hipStream_t s) {
 // are VALU-bound per SIMD, so the grid should fill the resident workgroup slots of the chip evenly in ONE generation; a fixed 16
 // left 13 % of the pose sweep's workgroups for a second, nearly empty generation (fm_rows below).
 static int fm_rows(const SweepArgs& a, int slots_per_cu) {
-    if (const char* e = getenv("PSGSDF_FM_ROWS")) { int v = atoi(e); if (v >= 4 && v <= 64) return v; }   // tuning knob (>= 4: the partial-row buffer is sized for that; <= 64: fm_for_each_obs keeps one bit per observation of a thread)
+    if (const int v = psge::knob_fm_rows()) return v;      // PSGSDF_FM_ROWS, read at every launch
     const long long total = a.b.obs_ptr_total > 0 ? a.b.obs_ptr_total : (long long)a.b.obs_max * a.F;
     const long long slots = 256LL * slots_per_cu;                       // resident workgroups on the chip
     // every frame wastes half a chunk on average: aim at ~92 % of the slots

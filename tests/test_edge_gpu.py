@@ -230,6 +230,37 @@ def test_persistent_solve_falls_back_to_the_per_pass_kernels(built, name, mid, m
         assert abs(a["e_total"] - b["e_total"]) <= 2e-4 * abs(b["e_total"])
 
 
+def test_tuning_report_follows_the_knob_table(built, monkeypatch):
+    """psgsdf_get_tuning on contexts that are only created (no volume, no kernel): a knob the report used to leave out (PSGSDF_AREG_DEVICE), the two
+    variables that share one member (PSGSDF_XCD_MAP first, PSGSDF_XCD_STRIPE on top), the one variable that sets two members (PSGSDF_FM_SOLVE), and
+    a refused CU mask (lo < hi is the table's rule; hi <= the device's CUs is psgsdf_create's)."""
+    grid = capi.GridDesc(); grid.dim[:] = [8, 8, 8]; grid.voxel_size = 0.01
+    K = np.array([100, 0, 4, 0, 100, 4, 0, 0, 1], np.float32)
+
+    def tuning():
+        eng = capi.load_engine(grid, K, capi.default_settings(capi.SH1), 0)
+        t = eng.get_tuning(); eng.close()
+        return t
+    t = tuning()
+    assert t["env"] == {} and t["ignored_dev_only"] == {} and t["effective"]["areg_device"] == 1
+    assert t["effective"]["xcd_map"] == 163 and t["effective"]["fm_solve"] == 1 and t["effective"]["fm_solve_led"] == 1 and t["effective"]["cu_mask"] == [-1, -1]
+    monkeypatch.setenv("PSGSDF_AREG_DEVICE", "0")
+    t = tuning()
+    assert t["env"] == {"PSGSDF_AREG_DEVICE": "0"} and t["effective"]["areg_device"] == 0
+    monkeypatch.delenv("PSGSDF_AREG_DEVICE")
+    monkeypatch.setenv("PSGSDF_XCD_MAP", "3"); monkeypatch.setenv("PSGSDF_XCD_STRIPE", "2")
+    t = tuning()
+    assert t["effective"]["xcd_map"] == 515 and t["env"] == {"PSGSDF_XCD_MAP": "3", "PSGSDF_XCD_STRIPE": "2"}
+    monkeypatch.delenv("PSGSDF_XCD_MAP"); monkeypatch.delenv("PSGSDF_XCD_STRIPE")
+    monkeypatch.setenv("PSGSDF_FM_SOLVE", "2")
+    t = tuning()
+    assert t["effective"]["fm_solve"] == 1 and t["effective"]["fm_solve_led"] == 0
+    monkeypatch.delenv("PSGSDF_FM_SOLVE")
+    monkeypatch.setenv("PSGSDF_CU_MASK", "8:8")
+    with pytest.raises(capi.PsgsdfError, match=r"create failed rc=-1\b"):      # PSGSDF_ERR_ARG
+        tuning()
+
+
 @pytest.mark.parametrize("name,mid", [("SH1", capi.SH1), ("LED", capi.LED)])
 def test_exact_state_callback_between_speculative_iterations(built, name, mid, monkeypatch):
     """psgsdf_set_on_iter_period(3): `on_iter` -- the callback voxelPS writes its meshes from -- is invoked for every 3rd iteration only and must see exactly

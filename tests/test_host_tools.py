@@ -288,3 +288,49 @@ def test_memory_owners_on_their_failure_paths(tmp_path):
     # (no device for the sanitized program, wherever this runs: it is about the paths on which allocations fail)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1"))
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-500:], r.stderr[-2000:])
+
+
+@pytest.mark.parametrize("variant", ["product", "dev"])
+def test_knob_table_parses_as_the_lines_it_replaced(tmp_path, variant):
+    """csrc/knobs.h on made-up environments: defaults, every parse rule at its edges, the accessors of the variables read at use, and the
+    development-only variables honoured (-DPSGSDF_DEV) or reported as ignored.  tests/knobs_check.cpp is a program of its own that includes
+    nothing but that header, built with the host's address and undefined-behaviour sanitizers and run directly."""
+    import shutil
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "knobs_check")
+    b = subprocess.run([cxx, "-std=c++17", "-Wall", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *(["-DPSGSDF_DEV"] if variant == "dev" else []),
+                        "-I", os.path.join(ROOT, "psgradientsdf_amd", "csrc"), os.path.join(ROOT, "tests", "knobs_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == variant + " ok", (r.stdout[-500:], r.stderr[-2000:])
+
+
+def test_knob_table_header_and_sources_agree():
+    """One row of the table in csrc/knobs.h per variable the knob comment of include/psgsdf.h names, and the reverse; a * there is exactly the
+    table's at_use, "NOT in libpsgsdf.so" exactly its dev_only; and the environment is read nowhere in the engine but through that header."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, "psgradientsdf_amd", "csrc")
+    rows = re.findall(r'^\s*\{"(PSGSDF_[A-Z0-9_]+)",\s*(at_create|at_use),\s*(product|dev_only),', open(os.path.join(csrc, "knobs.h")).read(), flags=re.M)
+    table = {n for n, _, _ in rows}
+    assert len(rows) == len(table) >= 38
+    hdr = open(os.path.join(ROOT, "include", "psgsdf.h")).read()
+    block = hdr[hdr.index("---- tuning knobs"):hdr.index("int psgsdf_get_tuning(")]
+    not_knobs = {"PSGSDF_ERR_ARG", "PSGSDF_DEV"}      # (the status a refused value gives, the macro of the development build)
+    named = [(n, star) for n, star in re.findall(r"\b(PSGSDF_[A-Z0-9_]+)(\*?)", block) if n not in not_knobs]
+    assert {n for n, _ in named} == table
+    assert {n for n, star in named if star} == {n for n, when, _ in rows if when == "at_use"}
+    for n in {n for n, star in named if star}:
+        assert all(star for m, star in named if m == n), n      # (marked wherever it is named)
+    dev_block = block[block.index("NOT in libpsgsdf.so"):]
+    dev_block = dev_block[:dev_block.index("*/")]
+    assert set(re.findall(r"\bPSGSDF_[A-Z0-9_]+", dev_block)) - not_knobs == {n for n, _, build in rows if build == "dev_only"}
+    assert all(when == "at_create" for _, when, build in rows if build == "dev_only")
+    for f in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        text = open(f).read()
+        if os.path.basename(f) == "knobs.h":
+            assert text.count("getenv(") == 1      # (process_env, which every accessor and the parse go through)
+            continue
+        assert 'getenv("PSGSDF_' not in text and "getenv(" not in text, f
